@@ -185,8 +185,8 @@ def test_bench_dist_path_one_rank():
     gather) at one rank on a reduced cfg2: 24 streams verified against the
     oracle for chr21/chr22 (the verify leg) and a well-formed line."""
     env = dict(os.environ, MASTER_PORT=str(_free_port()))
-    r = subprocess.run([sys.executable, "bench.py", "--dist-path", "--steps", "2", "--warmup", "1", "--lines",
-                        "3000000"], cwd=ROOT, capture_output=True, timeout=600, env=env)
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--dist-path", "--steps", "2", "--warmup", "1",
+                        "--lines", "3000000"], cwd=ROOT, capture_output=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.decode().strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["config"]["lines"] == 3_000_000

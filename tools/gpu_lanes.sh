@@ -11,7 +11,7 @@ run() {   # name env... -- bench args
   local envs=()
   while [ "$1" != "--" ]; do envs+=("$1"); shift; done
   shift
-  env "${envs[@]}" timeout -k 10 300 python bench.py --no-cpu-baseline --no-e2e "$@" > $O/$name.json 2> $O/$name.err \
+  env "${envs[@]}" timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-e2e "$@" > $O/$name.json 2> $O/$name.err \
     || { tail -20 $O/$name.err; exit 1; }
   python3 -c "import json;d=json.load(open('$O/$name.json'));print('$name', d['ms_per_step'], d['value'], d['verify']['match'] if d.get('verify') else '-', d['stage_ms'])"
 }

@@ -11,7 +11,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 export PYTHONUNBUFFERED=1
 BA=${BENCH_ARGS:---steps 2 --warmup 1}
-env $ENVS timeout -k 10 ${TB:-300} python3 $ROOT/bench.py $BA --no-cpu-baseline --no-e2e > $O/$TAG.json 2> $O/$TAG.err \
+env $ENVS timeout -k 10 ${TB:-300} python3 $ROOT/bench.py --full $BA --no-cpu-baseline --no-e2e > $O/$TAG.json 2> $O/$TAG.err \
     || { tail -20 $O/$TAG.err; exit 1; }
 cat $O/$TAG.json
 if [ -z "${NOPROF:-}" ]; then
