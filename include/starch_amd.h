@@ -365,6 +365,56 @@ int starch_untransform_host(starch_ctx* ctx, const void* text, uint64_t n, const
 /* A whole archive of this library (magic, streams, index, footer) back to BED:
  * every stream decoded and inverse-transformed on the GPU, in index order. */
 int starch_unstarch_host(starch_ctx* ctx, const void* archive, uint64_t n);
+/* ---- indexed extraction (BEDOPS `unstarch chr21 x.starch`) -----------------
+ * A query is a list of regions: a chromosome name (exact bytes: "chr1" does
+ * not match "chr10") and either the whole chromosome (whole != 0; start/stop
+ * ignored) or the half-open range [start, stop), start < stop.  The result
+ * (starch_output_*) is the lines starch_unstarch_host would give, in archive
+ * order, each at most once, whose segment has a queried name and is either
+ * queried whole or has line_start < stop && line_stop > start for one of its
+ * regions (so a zero-length element x..x needs start < x < stop).  Only the
+ * index entries with a queried name are read from the archive, decoded and
+ * scanned; the coordinate filter runs on the GPU.  A chromosome revisited
+ * later in the archive contributes every one of its segments.  nregions == 0:
+ * the whole archive.  An absent chromosome or an empty result is STARCH_OK
+ * with output size 0.  STARCH_ERR_ARG: start >= stop, a NULL name with a
+ * non-zero length, or an archive whose index says compressionFormat "gzip"
+ * (gzip members are not decoded; starch_archive_index still lists them). */
+typedef struct {
+    const char* chr;
+    uint64_t chr_len;
+    int64_t start, stop;
+    int whole;
+} starch_region;
+int starch_extract_host(starch_ctx* ctx, const void* archive, uint64_t n, const starch_region* regions,
+                        uint64_t nregions);
+typedef struct {
+    uint64_t streams_total;             /* index entries */
+    uint64_t streams_decoded;           /* ... with a queried name */
+    uint64_t compressed_bytes_decoded;  /* their stream bytes */
+    uint64_t lines_scanned;             /* BED lines in the decoded segments */
+    uint64_t lines_out;                 /* ... that were kept */
+} starch_extract_stats;
+int starch_extract_get_stats(starch_ctx* ctx, starch_extract_stats* out);
+
+/* The archive's index as records (host only: no context, no GPU).  names
+ * receives the chromosome names back to back (entry k: names[name_off,
+ * name_off + name_len)).  out == NULL and names == NULL: *count / *names_len
+ * alone.  STARCH_ERR_MEM when cap or names_cap is short; STARCH_ERR_DATA for
+ * a damaged footer or index, or a stream outside [4, index offset).
+ * compression_method: STARCH_METHOD_*. */
+typedef struct {
+    uint64_t name_off, name_len, offset, size, line_count, text_bytes;
+    uint32_t n_blocks, combined_crc;
+    int has_base_counts;
+    int64_t base_count_unique, base_count_nonunique;
+} starch_index_entry;
+int starch_archive_index(const void* archive, uint64_t n, starch_index_entry* out, uint64_t cap, uint64_t* count,
+                         char* names, uint64_t names_cap, uint64_t* names_len, int* compression_method,
+                         int* block_size_100k);
+/* The index's note as UTF-8 (buf == NULL: *len alone). */
+int starch_archive_note(const void* archive, uint64_t n, char* buf, uint64_t cap, uint64_t* len);
+
 int starch_output_size(starch_ctx* ctx, uint64_t* n);
 int starch_output_copy(starch_ctx* ctx, void* dst, uint64_t cap);
 int starch_output_device(starch_ctx* ctx, const void** d_ptr);

@@ -16,7 +16,8 @@ import json
 import os
 
 __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_archive", "plan_units", "assign_shards",
-           "archive_layout", "compress_multi", "Unit", "Segment", "Comm", "gather_host", "MAGIC", "HG38", "HG38_LEN"]
+           "archive_layout", "compress_multi", "Unit", "Segment", "Comm", "gather_host", "MAGIC", "HG38", "HG38_LEN",
+           "list_archive"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STARCH_AMD_LIB") or os.path.join(_HERE, "_build", "libstarch_amd.so")
@@ -89,6 +90,25 @@ class DecStream(ctypes.Structure):
     _fields_ = [("in_beg", ctypes.c_uint64), ("in_end", ctypes.c_uint64), ("out_off", ctypes.c_uint64),
                 ("out_len", ctypes.c_uint64), ("level", ctypes.c_uint32), ("n_blocks", ctypes.c_uint32),
                 ("combined_crc", ctypes.c_uint32)]
+
+
+class Region(ctypes.Structure):
+    """starch_region: a chromosome, whole or the half-open range [start, stop)."""
+    _fields_ = [("chr", ctypes.c_char_p), ("chr_len", ctypes.c_uint64), ("start", ctypes.c_int64),
+                ("stop", ctypes.c_int64), ("whole", ctypes.c_int)]
+
+
+class ExtractStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("streams_total", "streams_decoded", "compressed_bytes_decoded",
+                                               "lines_scanned", "lines_out")]
+
+
+class IndexEntry(ctypes.Structure):
+    """starch_index_entry: one stream of an archive's index."""
+    _fields_ = [("name_off", ctypes.c_uint64), ("name_len", ctypes.c_uint64), ("offset", ctypes.c_uint64),
+                ("size", ctypes.c_uint64), ("line_count", ctypes.c_uint64), ("text_bytes", ctypes.c_uint64),
+                ("n_blocks", ctypes.c_uint32), ("combined_crc", ctypes.c_uint32), ("has_base_counts", ctypes.c_int),
+                ("base_count_unique", ctypes.c_int64), ("base_count_nonunique", ctypes.c_int64)]
 
 
 def load():
@@ -171,6 +191,11 @@ def load():
         "starch_bz2_streams": ([vp, ctypes.POINTER(DecStream), u64], ctypes.c_int),
         "starch_untransform_host": ([vp, ctypes.c_char_p, u64, ctypes.c_char_p, u64], ctypes.c_int),
         "starch_unstarch_host": ([vp, ctypes.c_char_p, u64], ctypes.c_int),
+        "starch_extract_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(Region), u64], ctypes.c_int),
+        "starch_extract_get_stats": ([vp, ctypes.POINTER(ExtractStats)], ctypes.c_int),
+        "starch_archive_index": ([ctypes.c_char_p, u64, ctypes.POINTER(IndexEntry), u64, pu64, vp, u64, pu64,
+                                  ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
+        "starch_archive_note": ([ctypes.c_char_p, u64, vp, u64, pu64], ctypes.c_int),
         "starch_output_size": ([vp, pu64], ctypes.c_int),
         "starch_output_copy": ([vp, vp, u64], ctypes.c_int),
         "starch_output_device": ([vp, ctypes.POINTER(vp)], ctypes.c_int),
@@ -508,6 +533,65 @@ class Starch:
         """An archive of this library back to BED (decode + inverse transform on the GPU)."""
         _check(self._L.starch_unstarch_host(self._h, archive, len(archive)), self._h)
         return self._output()
+
+    def extract(self, archive: bytes, regions) -> bytes:
+        """The archive's lines on the given regions, in archive order: a region
+        is a chromosome name (``b"chr1"``: all of it) or ``(b"chr1", start,
+        stop)``: the lines overlapping [start, stop).  Only the streams of the
+        named chromosomes are decoded (the archive's index picks them); the
+        coordinate filter runs on the GPU.  No regions: the whole archive."""
+        regions = list(regions)
+        arr = (Region * max(1, len(regions)))()
+        names = []                                   # keeps the name bytes alive for the call
+        for k, r in enumerate(regions):
+            if isinstance(r, (bytes, bytearray)):
+                names.append(bytes(r))
+                arr[k] = Region(names[-1], len(names[-1]), 0, 0, 1)
+            else:
+                names.append(bytes(r[0]))
+                arr[k] = Region(names[-1], len(names[-1]), int(r[1]), int(r[2]), 0)
+        _check(self._L.starch_extract_host(self._h, archive, len(archive), arr, len(regions)), self._h)
+        return self._output()
+
+    def extract_stats(self) -> dict:
+        """Of the last extract(): streams_total / streams_decoded /
+        compressed_bytes_decoded / lines_scanned / lines_out."""
+        s = ExtractStats()
+        _check(self._L.starch_extract_get_stats(self._h, ctypes.byref(s)), self._h)
+        return {k: getattr(s, k) for k, _ in ExtractStats._fields_}
+
+
+def list_archive(blob: bytes):
+    """An archive's index without a GPU (starch_archive_index) ->
+    (archive info, [entry dicts]), with the index's own JSON field names;
+    chromosome names are bytes."""
+    L = load()
+    n, nb = ctypes.c_uint64(), ctypes.c_uint64()
+    method, bs = ctypes.c_int(), ctypes.c_int()
+    rc = L.starch_archive_index(blob, len(blob), None, 0, ctypes.byref(n), None, 0, ctypes.byref(nb),
+                                ctypes.byref(method), ctypes.byref(bs))
+    if rc:
+        raise StarchError(rc, (L.starch_strerror(rc) or b"").decode())
+    arr = (IndexEntry * max(1, n.value))()
+    names = ctypes.create_string_buffer(max(1, nb.value))
+    _check(L.starch_archive_index(blob, len(blob), arr, n.value, ctypes.byref(n), names, nb.value, ctypes.byref(nb),
+                                  ctypes.byref(method), ctypes.byref(bs)))
+    k = ctypes.c_uint64()
+    _check(L.starch_archive_note(blob, len(blob), None, 0, ctypes.byref(k)))
+    note = ctypes.create_string_buffer(max(1, k.value))
+    _check(L.starch_archive_note(blob, len(blob), note, k.value, ctypes.byref(k)))
+    info = {"compressionFormat": "gzip" if method.value == K_GZIP else "bzip2", "blockSize100k": bs.value,
+            "note": note.raw[:k.value].decode("utf-8", errors="replace")}
+    out = []
+    for e in arr[:n.value]:
+        d = {"chromosome": names.raw[e.name_off:e.name_off + e.name_len], "offset": e.offset, "size": e.size,
+             "uncompressedLineCount": e.line_count, "transformedBytes": e.text_bytes, "blocks": e.n_blocks,
+             "combinedCRC": e.combined_crc}
+        if e.has_base_counts:
+            d["uniqueBaseCount"] = e.base_count_unique
+            d["nonUniqueBaseCount"] = e.base_count_nonunique
+        out.append(d)
+    return info, out
 
 
 def gen_bed(kind, total_lines, chroms=None, seed=20261015, into=None):

@@ -201,6 +201,8 @@ struct starch_ctx {
     uint64_t out_bytes = 0;
     bool have_out = false;
     std::vector<bz::DecStream> dstreams;
+    starch_extract_stats xstats{};   // the last starch_extract_host
+    bool have_xstats = false;
     std::string err;
     // last result
     bool have = false;

@@ -2351,12 +2351,56 @@ int starch_build_index_opt(const starch_segment* segs, const char* const* names,
 namespace {
 
 // Reader of this library's archive index (build_index above): the footer's
-// index offset, then per stream its chromosome (JSON string, \u00XX escapes
-// byte-wise), offset and size.  Only what unstarch needs; anything else is
-// skipped.  Throws on a layout build_index does not write.
-struct IndexEntry { std::string chr; uint64_t offset, size; };
+// index offset, the archive fields, then per stream its chromosome (JSON
+// string, \u00XX escapes byte-wise) and every field build_index writes.
+// offset and size are required; the other fields are 0 when absent.  Throws
+// on a layout build_index does not write.
+struct IndexEntry {
+    std::string chr;
+    uint64_t offset, size;
+    uint64_t line_count = 0, text_bytes = 0;
+    uint32_t n_blocks = 0, combined_crc = 0;
+    bool has_base_counts = false;
+    int64_t base_unique = 0, base_nonunique = 0;
+};
+struct ArchiveInfo {
+    std::string format;          // "compressionFormat"
+    int block_size_100k = 0;
+    std::string note;            // UTF-8
+};
 
-std::vector<IndexEntry> read_index(const uint8_t* a, uint64_t n, uint64_t* index_off)
+// JSON string body at j[q] (after the opening quote) up to `end`; q is left on
+// the closing quote.  bytewise: \u00XX is one byte (chromosome names), else
+// the code point as UTF-8 (the note).
+bool json_unescape(const std::string& j, size_t& q, size_t end, bool bytewise, std::string& out)
+{
+    for (;;) {
+        if (q >= end) return false;
+        const char ch = j[q];
+        if (ch == '"') return true;
+        if (ch != '\\') { out += ch; ++q; continue; }
+        if (q + 1 >= end) return false;
+        const char x = j[q + 1];
+        if (x == 'u') {
+            if (q + 6 > end) return false;
+            unsigned v = 0;
+            for (int k = 2; k < 6; ++k) {
+                const char h = j[q + k];
+                v = v * 16 + (unsigned)(h >= '0' && h <= '9' ? h - '0' : h >= 'a' && h <= 'f' ? h - 'a' + 10
+                                         : h >= 'A' && h <= 'F' ? h - 'A' + 10 : 0);
+            }
+            if (bytewise || v < 0x80) out += (char)v;
+            else if (v < 0x800) { out += (char)(0xc0 | (v >> 6)); out += (char)(0x80 | (v & 63)); }
+            else { out += (char)(0xe0 | (v >> 12)); out += (char)(0x80 | ((v >> 6) & 63)); out += (char)(0x80 | (v & 63)); }
+            q += 6;
+        } else {
+            out += x == 'n' ? '\n' : x == 't' ? '\t' : x == 'r' ? '\r' : x == 'b' ? '\b' : x == 'f' ? '\f' : x;
+            q += 2;
+        }
+    }
+}
+
+std::vector<IndexEntry> read_index(const uint8_t* a, uint64_t n, uint64_t* index_off, ArchiveInfo* info = nullptr)
 {
     auto bad = [](const char* m) { throw StarchError(STARCH_ERR_DATA, std::string("archive: ") + m); };
     if (n < 4 + 32 || memcmp(a, kMagic, 4) != 0) bad("no magic / footer");
@@ -2372,49 +2416,111 @@ std::vector<IndexEntry> read_index(const uint8_t* a, uint64_t n, uint64_t* index
     std::vector<IndexEntry> out;
     size_t p = j.find("\"streams\":[");
     if (p == std::string::npos) bad("index without streams");
+    if (info) {   // the archive object precedes the streams; its note is the last field
+        auto str = [&](const char* key, bool bytewise, std::string& dst) {
+            const std::string k = std::string("\"") + key + "\":\"";
+            size_t q = j.find(k);
+            if (q == std::string::npos || q > p) return;
+            q += k.size();
+            if (!json_unescape(j, q, p, bytewise, dst)) bad("index string");
+        };
+        str("compressionFormat", true, info->format);
+        str("note", false, info->note);
+        const size_t q = j.find("\"blockSize100k\":");
+        if (q != std::string::npos && q < p) info->block_size_100k = atoi(j.c_str() + q + 16);
+    }
     p += 11;
-    auto num = [&](const char* key, size_t from, size_t to) -> uint64_t {
+    // from: the end of the entry's chromosome string, so a name's bytes are never taken for a key
+    auto find_num = [&](const char* key, size_t from, size_t to, bool need, bool* neg) -> std::pair<bool, uint64_t> {
         const std::string k = std::string("\"") + key + "\":";
         size_t q = j.find(k, from);
-        if (q == std::string::npos || q > to) bad("index field missing");
+        if (q == std::string::npos || q > to) {
+            if (need) bad("index field missing");
+            return {false, 0};
+        }
         q += k.size();
+        if (neg) {
+            *neg = q < j.size() && j[q] == '-';
+            if (*neg) ++q;
+        }
         uint64_t v = 0;
         if (q >= j.size() || j[q] < '0' || j[q] > '9') bad("index number");
         while (q < j.size() && j[q] >= '0' && j[q] <= '9') v = v * 10 + (uint64_t)(j[q++] - '0');
-        return v;
+        return {true, v};
     };
     while (p < j.size() && j[p] == '{') {
-        const size_t e = j.find('}', p);   // entries hold no nested objects
-        if (e == std::string::npos) bad("index entry");
         size_t q = j.find("\"chromosome\":\"", p);
-        if (q == std::string::npos || q > e) bad("index chromosome");
+        if (q != p + 1) bad("index chromosome");
         q += 14;
-        std::string chr;
-        for (;;) {
-            if (q >= e) bad("index string");
-            const char ch = j[q];
-            if (ch == '"') break;
-            if (ch != '\\') { chr += ch; ++q; continue; }
-            const char x = j[q + 1];
-            if (x == 'u') {
-                unsigned v = 0;
-                for (int k = 2; k < 6; ++k) {
-                    const char h = j[q + k];
-                    v = v * 16 + (unsigned)(h >= '0' && h <= '9' ? h - '0' : h >= 'a' && h <= 'f' ? h - 'a' + 10
-                                             : h >= 'A' && h <= 'F' ? h - 'A' + 10 : 0);
-                }
-                chr += (char)v;
-                q += 6;
-            } else {
-                chr += x == 'n' ? '\n' : x == 't' ? '\t' : x == 'r' ? '\r' : x == 'b' ? '\b' : x == 'f' ? '\f' : x;
-                q += 2;
-            }
+        IndexEntry en;
+        if (!json_unescape(j, q, j.size(), true, en.chr)) bad("index string");
+        const size_t e = j.find('}', q);   // entries hold no nested objects
+        if (e == std::string::npos) bad("index entry");
+        en.offset = find_num("offset", q, e, true, nullptr).second;
+        en.size = find_num("size", q, e, true, nullptr).second;
+        en.line_count = find_num("uncompressedLineCount", q, e, false, nullptr).second;
+        en.text_bytes = find_num("transformedBytes", q, e, false, nullptr).second;
+        en.n_blocks = (uint32_t)find_num("blocks", q, e, false, nullptr).second;
+        en.combined_crc = (uint32_t)find_num("combinedCRC", q, e, false, nullptr).second;
+        bool neg = false;
+        const auto u = find_num("uniqueBaseCount", q, e, false, &neg);
+        if (u.first) {
+            en.has_base_counts = true;
+            en.base_unique = (int64_t)(neg ? 0ull - u.second : u.second);
+            const auto v = find_num("nonUniqueBaseCount", q, e, false, &neg);
+            en.base_nonunique = (int64_t)(neg ? 0ull - v.second : v.second);
         }
-        out.push_back(IndexEntry{chr, num("offset", p, e), num("size", p, e)});
+        out.push_back(en);
         p = e + 1;
         if (p < j.size() && j[p] == ',') ++p;
     }
     return out;
+}
+
+// every stream inside [4, index offset)
+void check_bounds(const std::vector<IndexEntry>& idx, uint64_t index_off)
+{
+    for (size_t k = 0; k < idx.size(); ++k)
+        if (idx[k].offset < 4 || idx[k].offset > index_off || idx[k].size > index_off - idx[k].offset)
+            throw StarchError(STARCH_ERR_DATA, "archive: stream " + std::to_string(k) + " lies outside the stream region");
+}
+
+// A query per chromosome: whole, or disjoint ranges with increasing qstart.
+// Ranges merge only when they strictly overlap: touching [a,b) [b,c) stay
+// apart, since their union would select a zero-length element at b that
+// neither selects.
+struct ChrQuery {
+    bool whole = false;
+    std::vector<std::pair<int64_t, int64_t>> r;
+};
+
+std::vector<std::pair<std::string, ChrQuery>> normalise_regions(const starch_region* regions, uint64_t nregions)
+{
+    std::vector<std::pair<std::string, ChrQuery>> q;
+    for (uint64_t k = 0; k < nregions; ++k) {
+        const starch_region& g = regions[k];
+        if (g.chr_len && !g.chr) throw StarchError(STARCH_ERR_ARG, "extract: region with a NULL chromosome name");
+        if (!g.whole && g.start >= g.stop)
+            throw StarchError(STARCH_ERR_ARG, "extract: region " + std::to_string(k) + " has start >= stop");
+        const std::string name(g.chr ? g.chr : "", g.chr_len);
+        size_t i = 0;
+        while (i < q.size() && q[i].first != name) ++i;
+        if (i == q.size()) q.emplace_back(name, ChrQuery{});
+        if (g.whole) q[i].second.whole = true;
+        else q[i].second.r.emplace_back(g.start, g.stop);
+    }
+    for (auto& e : q) {
+        ChrQuery& c = e.second;
+        if (c.whole) { c.r.clear(); continue; }
+        std::sort(c.r.begin(), c.r.end());
+        size_t w = 0;
+        for (size_t k = 1; k < c.r.size(); ++k) {
+            if (c.r[k].first < c.r[w].second) c.r[w].second = std::max(c.r[w].second, c.r[k].second);
+            else c.r[++w] = c.r[k];
+        }
+        if (!c.r.empty()) c.r.resize(w + 1);
+    }
+    return q;
 }
 
 }  // namespace
@@ -2514,6 +2620,160 @@ int starch_unstarch_host(starch_ctx* c, const void* archive, uint64_t n)
     c->have_out = true;
     return STARCH_OK;
     END_GUARD(c)
+}
+
+int starch_extract_host(starch_ctx* c, const void* archive, uint64_t n, const starch_region* regions,
+                        uint64_t nregions)
+{
+    GUARD(c)
+    if (!archive || (nregions && !regions)) return STARCH_ERR_ARG;
+    c->have_out = false;
+    c->have_xstats = false;
+    const auto query = normalise_regions(regions, nregions);
+    const uint8_t* a = static_cast<const uint8_t*>(archive);
+    uint64_t index_off = 0;
+    ArchiveInfo info;
+    const std::vector<IndexEntry> idx = read_index(a, n, &index_off, &info);
+    if (info.format == "gzip")
+        throw StarchError(STARCH_ERR_ARG, "extract: gzip archives are not decoded (compressionFormat \"gzip\")");
+    check_bounds(idx, index_off);
+    // the index entries whose chromosome is queried, in archive order
+    std::vector<size_t> pick, qof;
+    for (size_t k = 0; k < idx.size(); ++k) {
+        if (query.empty()) { pick.push_back(k); qof.push_back(0); continue; }
+        for (size_t i = 0; i < query.size(); ++i)
+            if (query[i].first == idx[k].chr) { pick.push_back(k); qof.push_back(i); break; }
+    }
+    starch_extract_stats xs{};
+    xs.streams_total = idx.size();
+    xs.streams_decoded = pick.size();
+    if (pick.empty()) {
+        c->ut_out.as<uint8_t>(64);
+        c->dstreams.clear();
+        c->out_bytes = 0;
+    } else {
+        // their bytes back to back in dec_in: one copy per run of adjacent entries
+        uint64_t m = 0;
+        for (size_t k : pick) m += idx[k].size;
+        xs.compressed_bytes_decoded = m;
+        uint8_t* d = c->dec_in.as<uint8_t>(m + 256);
+        struct Run { uint64_t src, dst, len; };
+        std::vector<Run> runs;
+        uint64_t pos = 0;
+        for (size_t k : pick) {
+            if (!runs.empty() && runs.back().src + runs.back().len == idx[k].offset) runs.back().len += idx[k].size;
+            else runs.push_back(Run{idx[k].offset, pos, idx[k].size});
+            pos += idx[k].size;
+        }
+        for (const Run& r : runs)
+            if (r.len) HIP_CHECK(hipMemcpyAsync(d + r.dst, a + r.src, r.len, hipMemcpyHostToDevice, c->st));
+        HIP_CHECK(hipMemsetAsync(d + m, 0, 256, c->st));
+        // the decoder's host view of the same bytes: the archive itself for one run, else a packed copy
+        std::vector<uint8_t> staging;
+        const uint8_t* h_in = a + runs[0].src;
+        if (runs.size() > 1) {
+            staging.resize(m);
+            for (const Run& r : runs) memcpy(staging.data() + r.dst, a + r.src, r.len);
+            h_in = staging.data();
+        }
+        const uint64_t tbytes = c->dec.decode(d, m, h_in, c->st, c->dec_out, c->dstreams);
+        if (c->dstreams.size() != pick.size()) throw StarchError(STARCH_ERR_DATA, "archive: index and streams disagree");
+        std::vector<ut::Untransform::Seg> segs;
+        ut::Untransform::Selection sel;
+        pos = 0;
+        for (size_t i = 0; i < pick.size(); ++i) {
+            const IndexEntry& en = idx[pick[i]];
+            const bz::DecStream& s = c->dstreams[i];
+            if (s.in_beg != pos || s.in_end - s.in_beg != en.size)
+                throw StarchError(STARCH_ERR_DATA,
+                                  "archive: stream " + std::to_string(pick[i]) + " is not where the index says");
+            pos += en.size;
+            segs.push_back(ut::Untransform::Seg{s.out_off, s.out_len, en.chr});
+            const bool whole = query.empty() || query[qof[i]].second.whole;
+            sel.whole.push_back(whole ? 1u : 0u);
+            sel.q_lo.push_back((uint32_t)sel.qs.size());
+            if (!whole)
+                for (const auto& r : query[qof[i]].second.r) {
+                    sel.qs.push_back(r.first);
+                    sel.qe.push_back(r.second);
+                }
+            sel.q_hi.push_back((uint32_t)sel.qs.size());
+        }
+        c->out_bytes = c->untf.run(c->tf, static_cast<const uint8_t*>(c->dec_out.p), tbytes, segs, c->st, c->ut_out, &sel);
+        xs.lines_scanned = sel.lines_scanned;
+        xs.lines_out = sel.lines_out;
+    }
+    c->out_dev = static_cast<const uint8_t*>(c->ut_out.p);
+    c->have_out = true;
+    c->xstats = xs;
+    c->have_xstats = true;
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_extract_get_stats(starch_ctx* c, starch_extract_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_xstats) return STARCH_ERR_STATE;
+    *out = c->xstats;
+    return STARCH_OK;
+}
+
+// host only: no context, no GPU
+int starch_archive_index(const void* archive, uint64_t n, starch_index_entry* out, uint64_t cap, uint64_t* count,
+                         char* names, uint64_t names_cap, uint64_t* names_len, int* compression_method,
+                         int* block_size_100k)
+{
+    if (!archive || !count) return STARCH_ERR_ARG;
+    try {
+        uint64_t index_off = 0;
+        ArchiveInfo info;
+        const std::vector<IndexEntry> idx =
+            read_index(static_cast<const uint8_t*>(archive), n, &index_off, &info);
+        check_bounds(idx, index_off);
+        uint64_t nb = 0;
+        for (const IndexEntry& e : idx) nb += e.chr.size();
+        *count = idx.size();
+        if (names_len) *names_len = nb;
+        if (compression_method) *compression_method = info.format == "gzip" ? STARCH_METHOD_GZIP : STARCH_METHOD_BZIP2;
+        if (block_size_100k) *block_size_100k = info.block_size_100k;
+        if (!out && !names) return STARCH_OK;   // sizing call
+        if ((out && cap < idx.size()) || (names && names_cap < nb)) return STARCH_ERR_MEM;
+        uint64_t no = 0;
+        for (size_t k = 0; k < idx.size(); ++k) {
+            const IndexEntry& e = idx[k];
+            if (out)
+                out[k] = starch_index_entry{no, e.chr.size(), e.offset, e.size, e.line_count, e.text_bytes,
+                                            e.n_blocks, e.combined_crc, e.has_base_counts ? 1 : 0,
+                                            e.base_unique, e.base_nonunique};
+            if (names && !e.chr.empty()) memcpy(names + no, e.chr.data(), e.chr.size());
+            no += e.chr.size();
+        }
+        return STARCH_OK;
+    } catch (const StarchError& e) {
+        return e.code;
+    } catch (const std::exception&) {
+        return STARCH_ERR_INTERNAL;
+    }
+}
+
+int starch_archive_note(const void* archive, uint64_t n, char* buf, uint64_t cap, uint64_t* len)
+{
+    if (!archive || !len) return STARCH_ERR_ARG;
+    try {
+        uint64_t index_off = 0;
+        ArchiveInfo info;
+        read_index(static_cast<const uint8_t*>(archive), n, &index_off, &info);
+        *len = info.note.size();
+        if (!buf) return STARCH_OK;
+        if (cap < info.note.size()) return STARCH_ERR_MEM;
+        if (!info.note.empty()) memcpy(buf, info.note.data(), info.note.size());
+        return STARCH_OK;
+    } catch (const StarchError& e) {
+        return e.code;
+    } catch (const std::exception&) {
+        return STARCH_ERR_INTERNAL;
+    }
 }
 
 int starch_output_size(starch_ctx* c, uint64_t* n)

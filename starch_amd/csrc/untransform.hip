@@ -150,17 +150,51 @@ __global__ void __launch_bounds__(kT) k_ut_len(const LineRec* __restrict__ rec, 
     olen[i] = name_len[s] + 1 + dec_len_i64(st) + 1 + dec_len_i64(sp) + ((r.flags & L_TAB) ? 1 + r.rem_len : 0) + 1;
 }
 
-__global__ void __launch_bounds__(kT) k_ut_write(const uint8_t* __restrict__ t, const LineRec* __restrict__ rec,
-                                                 const int64_t* __restrict__ cd, const int64_t* __restrict__ stop,
-                                                 const uint64_t* __restrict__ ooff, const uint32_t* __restrict__ seg_first,
-                                                 const uint64_t* __restrict__ name_off, const uint64_t* __restrict__ name_len,
-                                                 const uint8_t* __restrict__ names, uint32_t nseg, uint64_t nl,
-                                                 uint8_t* __restrict__ out)
+// Indexed extraction: keep a value line iff its segment is selected whole or
+// [start, stop) overlaps one of the segment's ranges: the first range k with
+// qe[k] > start is the only candidate (earlier ones end at or before start,
+// later ones begin after qs[k]), kept iff qs[k] < stop.  A dropped line gets
+// olen 0.  seg_q: (q_lo, q_hi, whole) per segment; counts: value lines seen,
+// lines kept -- one atomic per wave each.
+__global__ void __launch_bounds__(kT) k_ut_select(const LineRec* __restrict__ rec, const int64_t* __restrict__ cd,
+                                                  const int64_t* __restrict__ stop,
+                                                  const uint32_t* __restrict__ seg_first, uint32_t nseg, uint64_t nl,
+                                                  const int64_t* __restrict__ qs, const int64_t* __restrict__ qe,
+                                                  const uint32_t* __restrict__ seg_q, uint64_t* __restrict__ olen,
+                                                  unsigned long long* __restrict__ counts)
 {
     const uint64_t i = (uint64_t)blockIdx.x * kT + threadIdx.x;
-    if (i >= nl) return;
-    const LineRec r = rec[i];
-    if (r.flags & L_P) return;
+    bool value = false, keep = false;
+    if (i < nl && !(rec[i].flags & L_P)) {
+        value = true;
+        const uint32_t s = seg_of(seg_first, nseg, i);
+        if (seg_q[3 * s + 2]) keep = true;
+        else {
+            const int64_t sp = stop[i];
+            const int64_t st = (int64_t)((uint64_t)sp - (uint64_t)cd[i]);
+            const uint32_t hi = seg_q[3 * s + 1];
+            uint32_t a = seg_q[3 * s], b = hi;
+            while (a < b) {
+                const uint32_t mid = a + ((b - a) >> 1);
+                if (qe[mid] > st) b = mid; else a = mid + 1;
+            }
+            keep = a < hi && qs[a] < sp;
+        }
+        if (!keep) olen[i] = 0;
+    }
+    const uint64_t bv = __ballot(value), bk = __ballot(keep);
+    if ((threadIdx.x & 63) == 0) {
+        if (bv) atomicAdd(&counts[0], (unsigned long long)__popcll(bv));
+        if (bk) atomicAdd(&counts[1], (unsigned long long)__popcll(bk));
+    }
+}
+
+__device__ __forceinline__ void write_line(const uint8_t* __restrict__ t, const LineRec& r, uint64_t i,
+                                           const int64_t* __restrict__ cd, const int64_t* __restrict__ stop,
+                                           const uint64_t* __restrict__ ooff, const uint32_t* __restrict__ seg_first,
+                                           const uint64_t* __restrict__ name_off, const uint64_t* __restrict__ name_len,
+                                           const uint8_t* __restrict__ names, uint32_t nseg, uint8_t* __restrict__ out)
+{
     const uint32_t s = seg_of(seg_first, nseg, i);
     uint8_t* o = out + ooff[i];
     const uint8_t* nm = names + name_off[s];
@@ -180,16 +214,55 @@ __global__ void __launch_bounds__(kT) k_ut_write(const uint8_t* __restrict__ t, 
     *o = '\n';
 }
 
+__global__ void __launch_bounds__(kT) k_ut_write(const uint8_t* __restrict__ t, const LineRec* __restrict__ rec,
+                                                 const int64_t* __restrict__ cd, const int64_t* __restrict__ stop,
+                                                 const uint64_t* __restrict__ ooff, const uint32_t* __restrict__ seg_first,
+                                                 const uint64_t* __restrict__ name_off, const uint64_t* __restrict__ name_len,
+                                                 const uint8_t* __restrict__ names, uint32_t nseg, uint64_t nl,
+                                                 uint8_t* __restrict__ out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kT + threadIdx.x;
+    if (i >= nl) return;
+    const LineRec r = rec[i];
+    if (r.flags & L_P) return;
+    write_line(t, r, i, cd, stop, ooff, seg_first, name_off, name_len, names, nseg, out);
+}
+
+// the selected path: a dropped line has olen 0 and its ooff is the next kept
+// line's, so it must not write
+__global__ void __launch_bounds__(kT) k_ut_write_sel(const uint8_t* __restrict__ t, const LineRec* __restrict__ rec,
+                                                     const int64_t* __restrict__ cd, const int64_t* __restrict__ stop,
+                                                     const uint64_t* __restrict__ ooff, const uint64_t* __restrict__ olen,
+                                                     const uint32_t* __restrict__ seg_first,
+                                                     const uint64_t* __restrict__ name_off,
+                                                     const uint64_t* __restrict__ name_len,
+                                                     const uint8_t* __restrict__ names, uint32_t nseg, uint64_t nl,
+                                                     uint8_t* __restrict__ out)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kT + threadIdx.x;
+    if (i >= nl || olen[i] == 0) return;
+    write_line(t, rec[i], i, cd, stop, ooff, seg_first, name_off, name_len, names, nseg, out);
+}
+
 }  // namespace
 
 uint64_t Untransform::run(TransformWorkspace& tf, const uint8_t* d_text, uint64_t n, const std::vector<Seg>& segs,
-                          hipStream_t st, DevBuf& out)
+                          hipStream_t st, DevBuf& out, Selection* sel)
 {
+    if (sel) sel->lines_scanned = sel->lines_out = 0;
     if (n == 0 || segs.empty()) {
         out.as<uint8_t>(64);
         return 0;
     }
     const uint32_t nseg = (uint32_t)segs.size();
+    if (sel) {
+        if (sel->q_lo.size() != nseg || sel->q_hi.size() != nseg || sel->whole.size() != nseg ||
+            sel->qs.size() != sel->qe.size() || sel->qs.size() > 0xFFFFFFFFull)
+            throw StarchError(-2, "untransform: selection does not match the segments");
+        for (uint32_t s = 0; s < nseg; ++s)
+            if (sel->q_lo[s] > sel->q_hi[s] || sel->q_hi[s] > sel->qs.size())
+                throw StarchError(-2, "untransform: selection range list out of bounds");
+    }
     for (uint32_t s = 0; s < nseg; ++s) {
         if (s && segs[s].text_off < segs[s - 1].text_off + segs[s - 1].text_len)
             throw StarchError(-2, "untransform: segments must be in text order");
@@ -258,12 +331,48 @@ uint64_t Untransform::run(TransformWorkspace& tf, const uint8_t* d_text, uint64_
         throw StarchError(-12, "untransform: segments must cover the text, every line ending in a newline");
     hipLaunchKernelGGL(k_ut_len, dim3(g), dim3(kT), 0, st, d_rec, d_cd, d_excl, d_contrib, d_segfirst, d_nlen, nseg,
                        nl, d_stop, d_olen);
+    unsigned long long* d_counts = nullptr;
+    if (sel) {
+        // counts[2] | qs[nq] | qe[nq] | (q_lo, q_hi, whole)[nseg]
+        const uint64_t nq = sel->qs.size();
+        uint64_t* base = b_sel.as<uint64_t>(2 + 2 * nq + (3ull * nseg + 1) / 2 + 2);
+        d_counts = reinterpret_cast<unsigned long long*>(base);
+        int64_t* d_qs = reinterpret_cast<int64_t*>(base + 2);
+        int64_t* d_qe = d_qs + nq;
+        uint32_t* d_segq = reinterpret_cast<uint32_t*>(d_qe + nq);
+        std::vector<uint32_t> segq(3ull * nseg);
+        for (uint32_t s = 0; s < nseg; ++s) {
+            segq[3 * s] = sel->q_lo[s];
+            segq[3 * s + 1] = sel->q_hi[s];
+            segq[3 * s + 2] = sel->whole[s] ? 1u : 0u;
+        }
+        HIP_CHECK(hipMemsetAsync(d_counts, 0, 2 * sizeof(uint64_t), st));
+        if (nq) {
+            HIP_CHECK(hipMemcpyAsync(d_qs, sel->qs.data(), nq * sizeof(int64_t), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(d_qe, sel->qe.data(), nq * sizeof(int64_t), hipMemcpyHostToDevice, st));
+        }
+        HIP_CHECK(hipMemcpyAsync(d_segq, segq.data(), segq.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(k_ut_select, dim3(g), dim3(kT), 0, st, d_rec, d_cd, d_stop, d_segfirst, nseg, nl, d_qs, d_qe,
+                           d_segq, d_olen, d_counts);
+        HIP_CHECK(hipStreamSynchronize(st));   // segq is read by the copy until here
+    }
     uint64_t* d_ooff = d_key;                          // the keys are dead
     scan::excl_sum_u64(d_olen, d_ooff, nl, d_olen + nl, b_tmp, st);
     uint64_t total = 0;
     HIP_CHECK(hipMemcpyAsync(&total, d_olen + nl, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     uint8_t* d_out = out.as<uint8_t>(total + 64);
+    if (sel) {
+        unsigned long long cnt[2] = {0, 0};
+        HIP_CHECK(hipMemcpyAsync(cnt, d_counts, sizeof(cnt), hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(k_ut_write_sel, dim3(g), dim3(kT), 0, st, d_text, d_rec, d_cd, d_stop, d_ooff, d_olen,
+                           d_segfirst, d_noff, d_nlen, d_names, nseg, nl, d_out);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
+        sel->lines_scanned = cnt[0];
+        sel->lines_out = cnt[1];
+        return total;
+    }
     hipLaunchKernelGGL(k_ut_write, dim3(g), dim3(kT), 0, st, d_text, d_rec, d_cd, d_stop, d_ooff, d_segfirst, d_noff,
                        d_nlen, d_names, nseg, nl, d_out);
     HIP_CHECK(hipGetLastError());

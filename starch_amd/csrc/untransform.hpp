@@ -16,13 +16,23 @@ public:
         uint64_t text_off, text_len;   // the segment's transformed text in d_text
         std::string name;              // its chromosome
     };
+    // Which lines to keep (indexed extraction): segment s keeps every line
+    // when whole[s], else the lines with start < qe[k] && stop > qs[k] for
+    // some k in [q_lo[s], q_hi[s]).  Each segment's ranges are disjoint with
+    // qs and qe increasing (touching ranges stay separate).
+    struct Selection {
+        std::vector<int64_t> qs, qe;
+        std::vector<uint32_t> q_lo, q_hi, whole;    // one per segment
+        uint64_t lines_scanned = 0, lines_out = 0;   // out: value lines seen / kept
+    };
     // BED lines of every segment, in order, into `out`; returns their bytes.
     // Throws StarchError(-12) on text the forward transform cannot have made.
+    // sel == nullptr: every line.
     uint64_t run(TransformWorkspace& tf, const uint8_t* d_text, uint64_t n, const std::vector<Seg>& segs,
-                 hipStream_t st, DevBuf& out);
+                 hipStream_t st, DevBuf& out, Selection* sel = nullptr);
 
 private:
-    DevBuf b_seg, b_names, b_segfirst, b_rec, b_key, b_cd, b_contrib, b_excl, b_stop, b_olen, b_tmp;
+    DevBuf b_seg, b_names, b_segfirst, b_rec, b_key, b_cd, b_contrib, b_excl, b_stop, b_olen, b_tmp, b_sel;
 };
 
 }  // namespace ut
