@@ -415,6 +415,76 @@ int starch_archive_index(const void* archive, uint64_t n, starch_index_entry* ou
 /* The index's note as UTF-8 (buf == NULL: *len alone). */
 int starch_archive_note(const void* archive, uint64_t n, char* buf, uint64_t cap, uint64_t* len);
 
+/* ---- starchcat: merge archives (BEDOPS `starchcat a.starch b.starch`) -------
+ * Inputs are narch >= 1 bzip2 archives of this library, in argument order.
+ * All index entries with the same chromosome name (exact bytes) form a group;
+ * its entries are its runs, ordered by input number, then by position in
+ * that input's index.  The output holds one stream per group, the groups in
+ * bytewise (memcmp, shorter first) order of their names.  A group is COPIED
+ * when it has exactly one run, its archive's blockSize100k equals
+ * opt->block_size_100k and, if opt->base_counts, its entry carries base
+ * counts: the stream bytes and index fields are carried over and nothing of
+ * it is decoded (so a damaged copied stream is not detected).  Every other
+ * group is MERGED on the GPU: its runs are decoded, inverse-transformed,
+ * merged by (start, stop) as signed 64-bit integers -- equal keys stay in run
+ * order and, within a run, in their original order -- and encoded again.  In
+ * a group with two or more runs every run must be non-decreasing in
+ * (start, stop), as sort-bed writes it: a violation is STARCH_ERR_DATA and
+ * starch_last_error names the input number (from 0), the chromosome and the
+ * line (from 1, counting that stream's BED lines) of the first offending
+ * line of the lowest offending run.  A single-run group that is re-encoded
+ * only for its level or base counts keeps its order unchecked.  The result is
+ * byte for byte the archive starch_encode_host writes for the merged BED
+ * under the same options.
+ * opt: emit_index must be 1, reference_compat 0 and compression_method
+ * STARCH_METHOD_BZIP2 (NULL: the defaults); anything else, narch == 0 or an
+ * input whose index says compressionFormat "gzip" is STARCH_ERR_ARG; a blob
+ * that is not an archive is STARCH_ERR_DATA, as starch_archive_index has it. */
+typedef struct {
+    uint64_t name_off, name_len;   /* the chromosome, in `names` */
+    uint64_t first_run;            /* its runs: runs[first_run, first_run + n_runs) */
+    uint32_t n_runs;
+    uint32_t merge;                /* 0 copy, 1 decode + encode */
+    uint64_t lines, text_bytes;    /* sums over the runs, from the indexes */
+} starch_cat_group;
+typedef struct {
+    uint32_t input, entry;         /* index entry `entry` of archive `input` */
+} starch_cat_run;
+/* The plan alone (host only: no context, no GPU): the groups in output order.
+ * groups, runs and names all NULL: the three counts alone; STARCH_ERR_MEM
+ * when a capacity is short (the counts are still set). */
+int starch_cat_plan(const void* const* archives, const uint64_t* lens, uint64_t narch, const starch_options* opt,
+                    starch_cat_group* groups, uint64_t gcap, uint64_t* ngroups, starch_cat_run* runs, uint64_t rcap,
+                    uint64_t* nruns, char* names, uint64_t names_cap, uint64_t* names_len);
+typedef struct {
+    uint64_t streams_in;       /* index entries over all inputs */
+    uint64_t streams_copied;   /* groups copied */
+    uint64_t groups_merged;    /* groups decoded and encoded again */
+    uint64_t runs_decoded;     /* their runs */
+    uint64_t lines_merged;     /* BED lines of the merged groups */
+    uint64_t bytes_copied;     /* stream bytes carried over */
+    uint64_t bytes_decoded;    /* stream bytes decoded */
+} starch_cat_stats;
+/* The merged archive in *out (host memory; free with starch_free).  What is
+ * copied is decided by starch_cat_plan and nothing else.  Merge groups go
+ * through the GPU in batches, in output order: a batch takes groups while the
+ * sum of their transformedBytes stays within 1 GiB (environment variable
+ * STARCH_CAT_BATCH_BYTES overrides it), and always at least one; a batch of
+ * 2^32 lines or more, or one whose buffers cannot be allocated, is
+ * STARCH_ERR_MEM naming its first chromosome.  ctx may be NULL: a plan
+ * without a merge group completes on the host alone, one with a merge group
+ * is STARCH_ERR_ARG.  With a context, a plan without a merge group launches
+ * nothing and leaves the context's results as they were.  When a merge group
+ * runs, the call overwrites the decode and encode buffers: starch_output_* and
+ * the encode accessors (starch_archive_*, starch_streams_*, starch_segment*)
+ * report STARCH_ERR_STATE afterwards, as after a failed call, and
+ * starch_get_stats holds the last batch's encode; the extract stats
+ * (starch_extract_get_stats) are left untouched. */
+int starch_cat_host(starch_ctx* ctx, const void* const* archives, const uint64_t* lens, uint64_t narch,
+                    const starch_options* opt, void** out, uint64_t* out_len);
+/* Of the last successful starch_cat_host on this context. */
+int starch_cat_get_stats(starch_ctx* ctx, starch_cat_stats* out);
+
 int starch_output_size(starch_ctx* ctx, uint64_t* n);
 int starch_output_copy(starch_ctx* ctx, void* dst, uint64_t cap);
 int starch_output_device(starch_ctx* ctx, const void** d_ptr);

@@ -17,7 +17,7 @@ import os
 
 __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_archive", "plan_units", "assign_shards",
            "archive_layout", "compress_multi", "Unit", "Segment", "Comm", "gather_host", "MAGIC", "HG38", "HG38_LEN",
-           "list_archive"]
+           "list_archive", "cat_plan", "cat_host"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STARCH_AMD_LIB") or os.path.join(_HERE, "_build", "libstarch_amd.so")
@@ -101,6 +101,22 @@ class Region(ctypes.Structure):
 class ExtractStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("streams_total", "streams_decoded", "compressed_bytes_decoded",
                                                "lines_scanned", "lines_out")]
+
+
+class CatGroup(ctypes.Structure):
+    """starch_cat_group: one output stream of a cat plan."""
+    _fields_ = [("name_off", ctypes.c_uint64), ("name_len", ctypes.c_uint64), ("first_run", ctypes.c_uint64),
+                ("n_runs", ctypes.c_uint32), ("merge", ctypes.c_uint32), ("lines", ctypes.c_uint64),
+                ("text_bytes", ctypes.c_uint64)]
+
+
+class CatRun(ctypes.Structure):
+    _fields_ = [("input", ctypes.c_uint32), ("entry", ctypes.c_uint32)]
+
+
+class CatStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("streams_in", "streams_copied", "groups_merged", "runs_decoded",
+                                               "lines_merged", "bytes_copied", "bytes_decoded")]
 
 
 class IndexEntry(ctypes.Structure):
@@ -196,6 +212,12 @@ def load():
         "starch_archive_index": ([ctypes.c_char_p, u64, ctypes.POINTER(IndexEntry), u64, pu64, vp, u64, pu64,
                                   ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
         "starch_archive_note": ([ctypes.c_char_p, u64, vp, u64, pu64], ctypes.c_int),
+        "starch_cat_plan": ([ctypes.POINTER(ctypes.c_char_p), pu64, u64, ctypes.POINTER(Options),
+                             ctypes.POINTER(CatGroup), u64, pu64, ctypes.POINTER(CatRun), u64, pu64, vp, u64, pu64],
+                            ctypes.c_int),
+        "starch_cat_host": ([vp, ctypes.POINTER(ctypes.c_char_p), pu64, u64, ctypes.POINTER(Options),
+                             ctypes.POINTER(vp), pu64], ctypes.c_int),
+        "starch_cat_get_stats": ([vp, ctypes.POINTER(CatStats)], ctypes.c_int),
         "starch_output_size": ([vp, pu64], ctypes.c_int),
         "starch_output_copy": ([vp, vp, u64], ctypes.c_int),
         "starch_output_device": ([vp, ctypes.POINTER(vp)], ctypes.c_int),
@@ -559,6 +581,76 @@ class Starch:
         s = ExtractStats()
         _check(self._L.starch_extract_get_stats(self._h, ctypes.byref(s)), self._h)
         return {k: getattr(s, k) for k, _ in ExtractStats._fields_}
+
+    def cat(self, archives) -> bytes:
+        """starchcat: the archives (bytes, in order) merged into one, with this
+        instance's note, block_size_100k and base_counts.  A chromosome held
+        by one input at the same level is copied byte for byte; the others
+        are decoded, merged by (start, stop) and encoded again on the GPU.
+        The result is the archive compress() writes for the merged BED."""
+        return _cat(self._L, self._h, archives, self._opts())
+
+    def cat_stats(self) -> dict:
+        """Of the last cat(): streams_in / streams_copied / groups_merged /
+        runs_decoded / lines_merged / bytes_copied / bytes_decoded."""
+        s = CatStats()
+        _check(self._L.starch_cat_get_stats(self._h, ctypes.byref(s)), self._h)
+        return {k: getattr(s, k) for k, _ in CatStats._fields_}
+
+
+def _cat_args(archives):
+    archives = [bytes(a) for a in archives]
+    n = len(archives)
+    ptrs = (ctypes.c_char_p * max(1, n))(*archives)
+    lens = (ctypes.c_uint64 * max(1, n))(*[len(a) for a in archives])
+    return archives, ptrs, lens, n
+
+
+def _cat_opts(L, note, level, base_counts):
+    o = Options()
+    L.starch_options_init(ctypes.byref(o))
+    o.block_size_100k = int(level)
+    o.base_counts = 1 if base_counts else 0
+    note_b = note.encode() if isinstance(note, str) else note
+    o.note = note_b or None
+    return o, note_b
+
+
+def _cat(L, h, archives, o) -> bytes:
+    keep, ptrs, lens, n = _cat_args(archives)
+    out, k = ctypes.c_void_p(), ctypes.c_uint64()
+    _check(L.starch_cat_host(h, ptrs, lens, n, ctypes.byref(o), ctypes.byref(out), ctypes.byref(k)), h)
+    try:
+        return ctypes.string_at(out, k.value)
+    finally:
+        L.starch_free(out)
+
+
+def cat_host(archives, note=None, level=9, base_counts=False) -> bytes:
+    """starchcat without a context (and without a GPU): every chromosome must
+    be a copy in cat_plan(); one that has to be merged or re-encoded is
+    StarchError -2."""
+    L = load()
+    o, _keep = _cat_opts(L, note, level, base_counts)
+    return _cat(L, None, archives, o)
+
+
+def cat_plan(archives, level=9, base_counts=False):
+    """What cat() would do, without a GPU (starch_cat_plan): the output's
+    chromosomes in order as (name: bytes, "copy" | "merge", [(input, entry), ...])."""
+    L = load()
+    o, _keep = _cat_opts(L, None, level, base_counts)
+    keep, ptrs, lens, n = _cat_args(archives)
+    ng, nr, nb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    _check(L.starch_cat_plan(ptrs, lens, n, ctypes.byref(o), None, 0, ctypes.byref(ng), None, 0, ctypes.byref(nr),
+                             None, 0, ctypes.byref(nb)))
+    groups = (CatGroup * max(1, ng.value))()
+    runs = (CatRun * max(1, nr.value))()
+    names = ctypes.create_string_buffer(max(1, nb.value))
+    _check(L.starch_cat_plan(ptrs, lens, n, ctypes.byref(o), groups, ng.value, ctypes.byref(ng), runs, nr.value,
+                             ctypes.byref(nr), names, nb.value, ctypes.byref(nb)))
+    return [(names.raw[g.name_off:g.name_off + g.name_len], "merge" if g.merge else "copy",
+             [(r.input, r.entry) for r in runs[g.first_run:g.first_run + g.n_runs]]) for g in groups[:ng.value]]
 
 
 def list_archive(blob: bytes):

@@ -203,6 +203,8 @@ struct starch_ctx {
     std::vector<bz::DecStream> dstreams;
     starch_extract_stats xstats{};   // the last starch_extract_host
     bool have_xstats = false;
+    starch_cat_stats cstats{};       // the last starch_cat_host
+    bool have_cstats = false;
     std::string err;
     // last result
     bool have = false;

@@ -244,12 +244,128 @@ __global__ void __launch_bounds__(kT) k_ut_write_sel(const uint8_t* __restrict__
     write_line(t, rec[i], i, cd, stop, ooff, seg_first, name_off, name_len, names, nseg, out);
 }
 
+// ---- merge of sorted runs (starchcat) ---------------------------------------
+// A value line's ordinal is its index among the value lines (p-lines carry no
+// output line).  Segments are contiguous in line space, so run s owns the
+// ordinals [run_first[s], run_first[s + 1]); run_first[nseg] is their count.
+// Keys are dense SoA arrays indexed by ordinal; ordinals grow with the line
+// index, so a wave's key reads and writes stay coalesced.
+
+__global__ void __launch_bounds__(kT) k_mg_flag(const LineRec* __restrict__ rec, uint64_t nl, uint32_t* __restrict__ flag)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kT + threadIdx.x;
+    if (i < nl) flag[i] = (rec[i].flags & L_P) ? 0u : 1u;
+}
+
+__global__ void __launch_bounds__(kT) k_mg_runs(const uint64_t* __restrict__ ord, const uint32_t* __restrict__ seg_first,
+                                                uint32_t nseg, uint64_t nl, uint32_t* __restrict__ run_first)
+{
+    const uint32_t s = blockIdx.x * kT + threadIdx.x;
+    if (s > nseg) return;
+    run_first[s] = (uint32_t)(s < nseg ? ord[seg_first[s]] : ord[nl]);   // ord[nl]: the scan's total
+}
+
+__global__ void __launch_bounds__(kT) k_mg_keys(const LineRec* __restrict__ rec, const int64_t* __restrict__ cd,
+                                                const int64_t* __restrict__ stop, const uint64_t* __restrict__ ord,
+                                                uint64_t nl, int64_t* __restrict__ kstart, int64_t* __restrict__ kstop)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kT + threadIdx.x;
+    if (i >= nl || (rec[i].flags & L_P)) return;
+    const uint64_t o = ord[i];
+    const int64_t sp = stop[i];
+    kstart[o] = (int64_t)((uint64_t)sp - (uint64_t)cd[i]);
+    kstop[o] = sp;
+}
+
+__device__ __forceinline__ bool key_less(int64_t as, int64_t ae, int64_t bs, int64_t be)
+{
+    return as < bs || (as == bs && ae < be);
+}
+
+// a run of a group with two or more runs must be non-decreasing: the smallest
+// ordinal whose key sorts before its predecessor's in the run goes to *bad
+__global__ void __launch_bounds__(kT) k_mg_check(const LineRec* __restrict__ rec, const uint64_t* __restrict__ ord,
+                                                 const uint32_t* __restrict__ seg_first, uint32_t nseg, uint64_t nl,
+                                                 const uint32_t* __restrict__ run_first,
+                                                 const uint32_t* __restrict__ grp_lo, const uint32_t* __restrict__ grp_hi,
+                                                 const int64_t* __restrict__ kstart, const int64_t* __restrict__ kstop,
+                                                 uint32_t* __restrict__ bad)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kT + threadIdx.x;
+    if (i >= nl || (rec[i].flags & L_P)) return;
+    const uint32_t s = seg_of(seg_first, nseg, i);
+    if (grp_hi[s] - grp_lo[s] < 2) return;
+    const uint32_t o = (uint32_t)ord[i];
+    if (o == run_first[s]) return;
+    if (key_less(kstart[o], kstop[o], kstart[o - 1], kstop[o - 1])) atomicMin(bad, o);
+}
+
+// rank of a value line in its group's merged order: the lines before it are
+// its predecessors in its own run, the lines of EARLIER runs with key <= its
+// key (an upper bound: on a tie the earlier run goes first) and the lines of
+// LATER runs with key < its key (a lower bound).  Two lines with equal keys in
+// runs q < r thus count each other exactly once (r counts q's line, q does not
+// count r's), so ranks are a permutation of the group's ordinals.
+__global__ void __launch_bounds__(kT) k_mg_rank(const LineRec* __restrict__ rec, const uint64_t* __restrict__ ord,
+                                                const uint32_t* __restrict__ seg_first, uint32_t nseg, uint64_t nl,
+                                                const uint32_t* __restrict__ run_first,
+                                                const uint32_t* __restrict__ grp_lo, const uint32_t* __restrict__ grp_hi,
+                                                const int64_t* __restrict__ kstart, const int64_t* __restrict__ kstop,
+                                                const uint64_t* __restrict__ olen, uint32_t* __restrict__ rank,
+                                                uint64_t* __restrict__ len_ranked)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kT + threadIdx.x;
+    if (i >= nl || (rec[i].flags & L_P)) return;
+    const uint32_t s = seg_of(seg_first, nseg, i);
+    const uint32_t o = (uint32_t)ord[i];
+    const uint32_t g0 = grp_lo[s], g1 = grp_hi[s];
+    uint32_t r = run_first[g0] + (o - run_first[s]);
+    if (g1 - g0 > 1) {
+        const int64_t ks = kstart[o], ke = kstop[o];
+        for (uint32_t q = g0; q < g1; ++q) {
+            if (q == s) continue;
+            const uint32_t base = run_first[q];
+            uint32_t a = base, b = run_first[q + 1];
+            while (a < b) {   // first ordinal of run q that does not go before this line
+                const uint32_t mid = a + ((b - a) >> 1);
+                const int64_t ms = kstart[mid], me = kstop[mid];
+                const bool before = q < s ? !key_less(ks, ke, ms, me) : key_less(ms, me, ks, ke);
+                if (before) a = mid + 1; else b = mid;
+            }
+            r += a - base;
+        }
+    }
+    rank[i] = r;
+    len_ranked[r] = olen[i];
+}
+
+__global__ void __launch_bounds__(kT) k_mg_ooff(const LineRec* __restrict__ rec, const uint32_t* __restrict__ rank,
+                                                const uint64_t* __restrict__ off_ranked, uint64_t nl,
+                                                uint64_t* __restrict__ ooff)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * kT + threadIdx.x;
+    if (i >= nl || (rec[i].flags & L_P)) return;
+    ooff[i] = off_ranked[rank[i]];
+}
+
 }  // namespace
 
 uint64_t Untransform::run(TransformWorkspace& tf, const uint8_t* d_text, uint64_t n, const std::vector<Seg>& segs,
-                          hipStream_t st, DevBuf& out, Selection* sel)
+                          hipStream_t st, DevBuf& out, Selection* sel, Merge* mg)
 {
     if (sel) sel->lines_scanned = sel->lines_out = 0;
+    if (mg) {
+        mg->lines_out = 0;
+        mg->bad_seg = Merge::kNone;
+        mg->bad_line = 0;
+        if (sel) throw StarchError(-2, "untransform: a merge takes no selection");
+        if (mg->group.size() != segs.size()) throw StarchError(-2, "untransform: merge does not match the segments");
+        for (size_t s = 1; s < segs.size(); ++s) {
+            if (mg->group[s] < mg->group[s - 1]) throw StarchError(-2, "untransform: merge groups must be in order");
+            if (mg->group[s] == mg->group[s - 1] && segs[s].name != segs[s - 1].name)
+                throw StarchError(-2, "untransform: a merge group with two names");
+        }
+    }
     if (n == 0 || segs.empty()) {
         out.as<uint8_t>(64);
         return 0;
@@ -357,6 +473,69 @@ uint64_t Untransform::run(TransformWorkspace& tf, const uint8_t* d_text, uint64_
         HIP_CHECK(hipStreamSynchronize(st));   // segq is read by the copy until here
     }
     uint64_t* d_ooff = d_key;                          // the keys are dead
+    if (mg) {
+        if (nl >= 0xFFFFFFFFull) throw StarchError(-3, "untransform: a merge handles fewer than 2^32 lines");
+        // contrib and excl are dead after k_ut_len: the value-line flags and their scan (ordinals) reuse them
+        uint32_t* d_flag = reinterpret_cast<uint32_t*>(d_contrib);
+        uint64_t* d_ord = d_excl;                      // [nl]: the number of value lines
+        int64_t* d_kstart = b_mkey.as<int64_t>(2 * (nl + 1));
+        int64_t* d_kstop = d_kstart + nl + 1;
+        // run_first[nseg + 1] | grp_lo[nseg] | grp_hi[nseg] | bad
+        uint32_t* d_runfirst = b_mtab.as<uint32_t>(3ull * nseg + 8);
+        uint32_t* d_glo = d_runfirst + nseg + 1;
+        uint32_t* d_ghi = d_glo + nseg;
+        uint32_t* d_mbad = d_ghi + nseg;
+        uint32_t* d_rank = b_mrank.as<uint32_t>(nl + 1);
+        uint64_t* d_lenr = b_mlen.as<uint64_t>(nl + 2);
+        std::vector<uint32_t> tab(2ull * nseg + 1);
+        for (uint32_t s = 0, lo = 0; s < nseg; ++s) {
+            if (s && mg->group[s] != mg->group[s - 1]) lo = s;
+            tab[s] = lo;
+        }
+        for (uint32_t s = nseg, hi = nseg; s-- > 0;) {
+            if (s + 1 < nseg && mg->group[s] != mg->group[s + 1]) hi = s + 1;
+            tab[nseg + s] = hi;
+        }
+        tab[2ull * nseg] = Merge::kNone;
+        HIP_CHECK(hipMemcpyAsync(d_glo, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemsetAsync(d_lenr, 0, (nl + 2) * sizeof(uint64_t), st));   // ranks cover only the value lines
+        hipLaunchKernelGGL(k_mg_flag, dim3(g), dim3(kT), 0, st, d_rec, nl, d_flag);
+        scan::excl_sum_u32_to_u64(d_flag, d_ord, nl, d_ord + nl, b_tmp, st);
+        hipLaunchKernelGGL(k_mg_runs, dim3((unsigned)ceil_div(nseg + 1ull, kT)), dim3(kT), 0, st, d_ord, d_segfirst,
+                           nseg, nl, d_runfirst);
+        hipLaunchKernelGGL(k_mg_keys, dim3(g), dim3(kT), 0, st, d_rec, d_cd, d_stop, d_ord, nl, d_kstart, d_kstop);
+        hipLaunchKernelGGL(k_mg_check, dim3(g), dim3(kT), 0, st, d_rec, d_ord, d_segfirst, nseg, nl, d_runfirst, d_glo,
+                           d_ghi, d_kstart, d_kstop, d_mbad);
+        hipLaunchKernelGGL(k_mg_rank, dim3(g), dim3(kT), 0, st, d_rec, d_ord, d_segfirst, nseg, nl, d_runfirst, d_glo,
+                           d_ghi, d_kstart, d_kstop, d_olen, d_rank, d_lenr);
+        scan::excl_sum_u64(d_lenr, d_lenr, nl, d_lenr + nl, b_tmp, st);
+        hipLaunchKernelGGL(k_mg_ooff, dim3(g), dim3(kT), 0, st, d_rec, d_rank, d_lenr, nl, d_ooff);
+        HIP_CHECK(hipGetLastError());
+        // one round trip (the one the plain path spends on the total): total, value lines, first unsorted ordinal
+        uint64_t total = 0, nv = 0;
+        uint32_t mbad = Merge::kNone;
+        HIP_CHECK(hipMemcpyAsync(&total, d_lenr + nl, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(&nv, d_ord + nl, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(&mbad, d_mbad, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));           // (tab is read by its copy until here)
+        if (mbad != Merge::kNone) {                    // ranks and total mean nothing: name the run and stop
+            std::vector<uint32_t> rf(nseg + 1);
+            HIP_CHECK(hipMemcpy(rf.data(), d_runfirst, rf.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            uint32_t s = 0;
+            while (s + 1 < nseg && rf[s + 1] <= mbad) ++s;
+            mg->bad_seg = s;
+            mg->bad_line = mbad - rf[s];
+            out.as<uint8_t>(64);
+            return 0;
+        }
+        uint8_t* d_out = out.as<uint8_t>(total + 64);
+        hipLaunchKernelGGL(k_ut_write, dim3(g), dim3(kT), 0, st, d_text, d_rec, d_cd, d_stop, d_ooff, d_segfirst, d_noff,
+                           d_nlen, d_names, nseg, nl, d_out);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(st));
+        mg->lines_out = nv;
+        return total;
+    }
     scan::excl_sum_u64(d_olen, d_ooff, nl, d_olen + nl, b_tmp, st);
     uint64_t total = 0;
     HIP_CHECK(hipMemcpyAsync(&total, d_olen + nl, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
