@@ -193,28 +193,9 @@ __device__ __forceinline__ uint64_t lanemask_lt()
     return lane ? (~0ull >> (64 - lane)) : 0ull;
 }
 
-// Rotation values (SA / V) and last-column bytes stream through the sorts:
-// read once per group, written once.  Non-temporal access keeps them from
-// evicting the blocks' packed symbol streams (the random key gathers) from
-// the XCD's 4 MB L2.  STARCH_NT=0: plain accesses.
-#ifndef STARCH_NT
-#define STARCH_NT 0   // 1: non-temporal SA/LL/value streams (measured: cfg2 sort 23.5 -> 34.3 ms, cfg4 110 -> 130 ms)
-#endif
 #ifndef STARCH_W_UNROLL
 #define STARCH_W_UNROLL 0   // k3_sort_w's rank loops unrolled by 4 (experiment)
 #endif
-template <class T>
-__device__ __forceinline__ T ld_nt(const T* p)
-{
-    if constexpr (STARCH_NT != 0) return __builtin_nontemporal_load(p);
-    else return *p;
-}
-template <class T>
-__device__ __forceinline__ void st_nt(T* p, T v)
-{
-    if constexpr (STARCH_NT != 0) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
 
 // Append `item` for every lane with pred to list/ctr; one atomic per wave.
 // Must be reached by all 64 lanes of the wave.
@@ -680,6 +661,13 @@ __global__ void __launch_bounds__(SCT) k3_scatter(Ctx c)
 // out in local order, so consecutive threads store consecutive SA positions
 // of a bucket's run instead of one scattered 4-byte store per rotation (the
 // direct scatter's writes cost ~2.5-3.5x their bytes in HBM traffic).
+//
+// Thread t owns bins [t * BPT, (t + 1) * BPT): it scans their local counts and
+// keeps their SA cursors in registers.  The scan leaves one word per bin for
+// the write-out, (cursor - local start) mod 2^RBITS | flags, so a staged entry
+// j of bin d goes to SA position (ent[d] + j) mod 2^RBITS and the write-out
+// reads two LDS words per rotation.  The last stage of a job pops the next
+// job and loads its cursor row and first PSS words while it writes out.
 // ---------------------------------------------------------------------------
 template <int NB, bool MAT>
 __global__ void __launch_bounds__(SCT) k3_scatter_lds(Ctx c)
@@ -688,14 +676,19 @@ __global__ void __launch_bounds__(SCT) k3_scatter_lds(Ctx c)
     constexpr uint32_t SH_HALF = NB == PNB ? PTILE / 2 : PTILE / 4;
     constexpr int SU = (int)(SH_HALF / SCT);       // consecutive rotations per thread
     constexpr int BPT = NB / SCT;                  // bins per thread in the local scan
-    __shared__ uint32_t cur[NB], tot[NB], lst[NB + 1];
+    constexpr uint32_t NONE = 0xFFFFFFFFu;
+    constexpr uint32_t PMASK = (1u << RBITS) - 1u;
+    constexpr uint32_t F_ONE = 1u << 30, F_L = 1u << 31;   // ent flags: singleton bucket, L-class bucket
+    static_assert(BPT % 4 == 0 && BPT * 2 <= 32, "cursor rows load as uint4; two flag bits per owned bin");
+    __shared__ uint32_t lst[NB];                   // local counts, then local bucket starts
+    __shared__ uint32_t ent[NB];
     __shared__ uint32_t stage[SH_HALF];
-    // the next 8 key bits below the top-level digit, staged beside each entry:
-    // written next to the SA entries of the heavy (L-class) buckets, where
-    // k3_part_l's first partition reads them instead of gathering each
-    // rotation's key again (the plain instantiation only)
-    __shared__ uint8_t stage8[MAT ? 4 : SH_HALF];
-    __shared__ uint32_t scan_sh[SCT / 64 + 1];
+    // the next 8 key bits below the top-level digit of every staged rotation,
+    // by rotation: written next to the SA entries of the heavy (L-class)
+    // buckets, where k3_part_l's first partition reads them instead of
+    // gathering each rotation's key again (the plain instantiation only)
+    __shared__ __attribute__((aligned(16))) uint8_t stage8[MAT ? 16 : SH_HALF];
+    __shared__ uint32_t scan_sh[SCT / 64];
     __shared__ uint32_t qs[8];
     __shared__ uint32_t job_sh;
     // round 0 writes every rotation's key window and last-column symbol next to
@@ -704,32 +697,69 @@ __global__ void __launch_bounds__(SCT) k3_scatter_lds(Ctx c)
     constexpr uint32_t PWN = MAT ? (SH_HALF + 1) * 8 / 64 + 4 : 1;   // words for B <= 8
     __shared__ uint64_t pw[PWN];
     constexpr bool mat = MAT;
-    const int tid = threadIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const uint32_t x = xcc_id();
     if (tid < 8) qs[tid] = ((uint32_t)tid < c.nb ? (c.nb - tid + 7) / 8 : 0u) * MAXT;
+    for (int i = tid; i < NB; i += SCT) lst[i] = 0;   // (every stage leaves the counts cleared)
     __syncthreads();
-    for (;;) {
-        const uint32_t job = wg_pop(c, qs, &job_sh, x);
-        if (job == 0xFFFFFFFFu) break;
+    uint32_t job = wg_pop(c, qs, &job_sh, x);
+    uint32_t curv[BPT];                            // SA cursors of this thread's bins
+    uint64_t w0[4];                                // the first stage's PSS words
+    bool pre = false;                              // curv / w0 hold this job's (loaded by the job before)
+    uint32_t flv = 0, fslot = NONE;                // flag bits of this thread's bins, and the slot they belong to
+    auto load_row = [&](const uint32_t* th, uint32_t tile) {
+        const uint4* row = reinterpret_cast<const uint4*>(th + (uint64_t)tile * NB + tid * BPT);
+#pragma unroll
+        for (int q = 0; q < BPT / 4; ++q) {
+            const uint4 v = row[q];
+            curv[4 * q] = v.x; curv[4 * q + 1] = v.y; curv[4 * q + 2] = v.z; curv[4 * q + 3] = v.w;
+        }
+    };
+    auto load_w0 = [&](const uint64_t* pss, uint32_t t0, uint32_t B) {
+        const uint64_t qw = ((uint64_t)(t0 + tid * SU) * B) >> 6;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) w0[q] = pss[qw + q];
+    };
+    while (job != NONE) {
         const uint32_t y = job >> 28, k = job & 0x0FFFFFFFu;
         const uint32_t slot = y + 8u * (k / MAXT), tile = k % MAXT;
         const uint32_t b = c.b0 + slot;
         const uint32_t n = c.blocks[b].n;
         const uint32_t t0 = tile * PTILE;
-        if (t0 >= n) continue;                       // uniform
+        if (t0 >= n) {                               // uniform
+            job = wg_pop(c, qs, &job_sh, x);
+            pre = false;
+            continue;
+        }
         const uint64_t so = (uint64_t)slot * c.scr.stride;
         const uint32_t* th = tile_hist(c, slot);
-        for (int i = tid; i < NB; i += SCT) { cur[i] = th[(uint64_t)tile * NB + i]; tot[i] = th[(uint64_t)MAXT * NB + i]; }
         const Geo geo = c.L.geo[slot];
         const uint32_t B = geo.B;
         const uint64_t* pss = c.scr.K + so;
         uint32_t* SA = c.scr.SA + so;
+        uint8_t* LL = c.scr.LL + so;
         uint64_t* KM = c.kA + so;
         uint8_t* LS = c.lA ? c.lA + so : nullptr;
+        if (!pre) {
+            load_row(th, tile);
+            load_w0(pss, t0, B);
+        }
+        if (slot != fslot) {                         // bucket totals are per block: their flags once per slot
+            const uint32_t* tot = th + (uint64_t)MAXT * NB + tid * BPT;
+            flv = 0;
+#pragma unroll
+            for (int q = 0; q < BPT; ++q) {
+                const uint32_t t = tot[q];
+                flv |= (t == 1u ? 1u : t > L_MIN ? 2u : 0u) << (2 * q);
+            }
+            fslot = slot;
+        }
         const uint32_t e = n - t0 < (uint32_t)PTILE ? n - t0 : (uint32_t)PTILE;
+        uint32_t njob = NONE;
+        pre = false;
         for (uint32_t h0 = 0; h0 < e; h0 += SH_HALF) {
             const uint32_t he = e - h0 < SH_HALF ? e - h0 : SH_HALF;
-            for (int i = tid; i < NB; i += SCT) lst[i] = 0;
+            const bool last = h0 + SH_HALF >= e;
             // PSS words of this stage's keys and last symbols: rotations
             // [t0 + h0 - 1, t0 + h0 + he) plus one key window
             const uint32_t rs = t0 + h0;
@@ -738,40 +768,58 @@ __global__ void __launch_bounds__(SCT) k3_scatter_lds(Ctx c)
                 const uint64_t wend = (((uint64_t)(rs + he) * B + 64) >> 6) + 2;
                 for (uint64_t w = wbase + tid; w < wend; w += SCT) pw[w - wbase] = pss[w];
             }
-            __syncthreads();
+            // the next job's number travels through job_sh behind this stage's barriers
+            if (last && tid == 0) job_sh = xq_pop(c.qhead, qs, x);
             // digits of SU consecutive rotations from four PSS words; local counts
             const uint32_t q0 = tid * SU;                // SCT * SU == SH_HALF
             uint32_t d[SU], p[SU];
-            uint8_t sd[SU];
             {
                 const uint64_t bit0 = (uint64_t)(t0 + h0 + q0) * B;
                 const uint64_t qw = bit0 >> 6;
                 const uint32_t p0 = (uint32_t)(bit0 & 63u);
-                const uint64_t w[4] = {pss[qw], pss[qw + 1], pss[qw + 2], pss[qw + 3]};
+                if (h0 != 0) {                           // (the first stage's words are loaded already)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) w0[q] = pss[qw + q];
+                }
                 const uint32_t sds = 64u - geo.SH - 8u;       // (the key window's bits [SH, SH + 8))
+                uint32_t sdw[SU / 4] = {};
 #pragma unroll
                 for (int u = 0; u < SU; ++u) {
                     const uint32_t bit = p0 + (uint32_t)u * B;
                     const uint32_t ix = bit >> 6, pb = bit & 63u;
-                    const uint64_t a = ix == 0 ? w[0] : ix == 1 ? w[1] : w[2];
-                    const uint64_t nx = ix == 0 ? w[1] : ix == 1 ? w[2] : w[3];
+                    const uint64_t a = ix == 0 ? w0[0] : ix == 1 ? w0[1] : w0[2];
+                    const uint64_t nx = ix == 0 ? w0[1] : ix == 1 ? w0[2] : w0[3];
                     const uint64_t v = (a << pb) | ((nx >> 1) >> (63u - pb));
                     d[u] = top_digit(v, geo);
-                    sd[u] = (uint8_t)(v >> sds);
+                    sdw[u / 4] |= ((uint32_t)(v >> sds) & 0xFFu) << (8 * (u % 4));
+                }
+                if constexpr (!MAT) {                    // SU bytes per thread, in rotation order
+                    uint32_t* s8 = reinterpret_cast<uint32_t*>(stage8 + q0);
+#pragma unroll
+                    for (int q = 0; q < SU / 4; ++q) s8[q] = sdw[q];
                 }
             }
 #pragma unroll
             for (int u = 0; u < SU; ++u) p[u] = (q0 + u < he) ? atomicAdd(&lst[d[u]], 1u) : 0u;
             __syncthreads();
-            // local bucket starts (exclusive scan, BPT bins per thread)
+            if (last) njob = job_sh;
+            // local bucket starts (exclusive scan, BPT bins per thread), the
+            // write-out words, and the cursors moved past this stage
             {
                 uint32_t v[BPT], sum = 0;
 #pragma unroll
                 for (int q = 0; q < BPT; ++q) { v[q] = lst[tid * BPT + q]; sum += v[q]; }
-                uint32_t run = block_excl_scan_add<uint32_t>(sum, scan_sh, (uint32_t*)nullptr);
+                const uint32_t inc = wave_incl_scan_add(sum);
+                if (lane == 63) scan_sh[wid] = inc;
+                __syncthreads();
+                uint32_t run = wave_reduce_add<uint32_t>(lane < wid ? scan_sh[lane] : 0u) + inc - sum;
 #pragma unroll
-                for (int q = 0; q < BPT; ++q) { lst[tid * BPT + q] = run; run += v[q]; }
-                if (tid == SCT - 1) lst[NB] = run;
+                for (int q = 0; q < BPT; ++q) {
+                    lst[tid * BPT + q] = run;
+                    ent[tid * BPT + q] = ((curv[q] - run) & PMASK) | (((flv >> (2 * q)) & 3u) << 30);
+                    curv[q] += v[q];
+                    run += v[q];
+                }
             }
             __syncthreads();
 #pragma unroll
@@ -779,21 +827,46 @@ __global__ void __launch_bounds__(SCT) k3_scatter_lds(Ctx c)
                 if (q0 + u < he) {
                     const uint32_t j = lst[d[u]] + p[u];
                     stage[j] = (d[u] << 15) | (h0 + q0 + u);   // 13 + 15 bits
-                    if constexpr (!MAT) stage8[j] = sd[u];
                 }
             __syncthreads();
+#pragma unroll
+            for (int q = 0; q < BPT; ++q) lst[tid * BPT + q] = 0;
+            // the next job's cursor row and first PSS words load while this stage writes out
+            if (njob != NONE) {                          // uniform
+                const uint32_t nk = njob & 0x0FFFFFFFu;
+                const uint32_t nslot = (njob >> 28) + 8u * (nk / MAXT), ntile = nk % MAXT;
+                if (ntile * (uint32_t)PTILE < c.blocks[c.b0 + nslot].n) {
+                    load_row(tile_hist(c, nslot), ntile);
+                    load_w0(c.scr.K + (uint64_t)nslot * c.scr.stride, ntile * (uint32_t)PTILE, c.L.geo[nslot].B);
+                    pre = true;
+                }
+            }
             // write out in local (bucket) order: runs of a bucket land on consecutive SA slots
-            for (uint32_t j = tid; j < he; j += SCT) {
-                const uint32_t v = stage[j];
-                const uint32_t dg = v >> 15, r = t0 + (v & 0x7FFFu);
-                const uint32_t pos = cur[dg] + (j - lst[dg]);
-                st_nt(SA + pos, r);
+            // (four entries' LDS reads in flight per step)
+            for (int u0 = 0; u0 < SU && (uint32_t)tid + (uint32_t)u0 * SCT < he; u0 += 4) {
+                uint32_t sv[4], se[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t j = (uint32_t)tid + (uint32_t)(u0 + i) * SCT;
+                    sv[i] = stage[j < he ? j : (uint32_t)tid];
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) se[i] = ent[sv[i] >> 15];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                const uint32_t j = (uint32_t)tid + (uint32_t)(u0 + i) * SCT;
+                if (j >= he) break;
+                const uint32_t v = sv[i];
+                const uint32_t r = t0 + (v & 0x7FFFu);
+                const uint32_t en = se[i];
+                const uint32_t pos = (en + j) & PMASK;
+                SA[pos] = r;
                 uint32_t ls = 0;
                 if (mat && r) {   // (MAT: compile-time)
                     const uint64_t bit = (uint64_t)(r - 1) * B - (wbase << 6);
                     const uint32_t q = (uint32_t)(bit >> 6), p = (uint32_t)(bit & 63u);
                     ls = (uint32_t)(((pw[q] << p) | ((pw[q + 1] >> 1) >> (63u - p))) >> (64u - B));
-                } else if (mat || tot[dg] == 1u) {
+                } else if (mat || (en & F_ONE)) {
                     ls = (uint32_t)pss_bits(pss, (uint64_t)(r ? r - 1u : n - 1u) * B, B);
                 }
                 if (mat) {
@@ -802,17 +875,17 @@ __global__ void __launch_bounds__(SCT) k3_scatter_lds(Ctx c)
                     KM[pos] = ((pw[q] << p) | ((pw[q + 1] >> 1) >> (63u - p))) >> (64u - geo.KB);
                     LS[pos] = (uint8_t)ls;
                 }
-                if (tot[dg] == 1u) {                   // singleton bucket: final
-                    c.scr.LL[so + pos] = (uint8_t)ls;
+                if (en & F_ONE) {                      // singleton bucket: final
+                    LL[pos] = (uint8_t)ls;
                     if (r == 0) c.blocks[b].orig_ptr = pos;
-                } else if (!mat && tot[dg] > L_MIN) {  // L class: its first partition digit (LL is free there until then)
-                    c.scr.LL[so + pos] = stage8[j];
+                } else if (!mat && (en & F_L)) {       // L class: its first partition digit (LL is free there until then)
+                    LL[pos] = stage8[(v & 0x7FFFu) - h0];
+                }
                 }
             }
             __syncthreads();
-            for (int i = tid; i < NB; i += SCT) cur[i] += lst[i + 1] - lst[i];
-            __syncthreads();
         }
+        job = njob;
     }
 }
 
@@ -1034,7 +1107,7 @@ __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restric
 #pragma unroll
                 for (int u = 0; u < PU; ++u) {
                     const uint32_t i = i0 + u * LT + tid;
-                    vv[u] = ld_nt(sv + (i < m ? i : 0u));
+                    vv[u] = sv[i < m ? i : 0u];
                 }
 #pragma unroll
                 for (int u = 0; u < PU; ++u) {
@@ -1069,7 +1142,7 @@ __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restric
 #pragma unroll
             for (int u = 0; u < PU; ++u) {
                 const uint32_t i = i0 + u * LT + tid;
-                v[u] = ld_nt(sv + (i < m ? i : 0u));
+                v[u] = sv[i < m ? i : 0u];
             }
             if (!DBL && m <= PL_CAP) {                 // only the digit is used below
 #pragma unroll
@@ -1100,7 +1173,7 @@ __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restric
                 if (i0 + u * LT + tid < m) {
                     const uint32_t p = atomicAdd(&cur[(uint32_t)((k[u] >> sh2) & dmask)], 1u);
                     if (!DBL && staged) stg[p] = v[u];
-                    else st_nt(dv + p, v[u]);
+                    else dv[p] = v[u];
                     if constexpr (DBL) dk[p] = k[u];
                     if (dl) dl[p] = lsy[u];
                 }
@@ -1108,7 +1181,7 @@ __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restric
         }
         __syncthreads();
         if (!DBL && staged) {
-            for (uint32_t i = tid; i < m; i += LT) st_nt(dv + i, stg[i]);
+            for (uint32_t i = tid; i < m; i += LT) dv[i] = stg[i];
             __syncthreads();
         }
         PLT(t4);
@@ -1712,8 +1785,8 @@ __device__ __forceinline__ void emit_sorted(const Ctx& c, uint32_t slot, uint32_
 {
     const uint64_t so = (uint64_t)slot * c.scr.stride;
     if (valid) {
-        st_nt(c.scr.SA + so + s + j, v);
-        st_nt(c.scr.LL + so + s + j, (uint8_t)lsym);
+        c.scr.SA[so + s + j] = v;
+        c.scr.LL[so + s + j] = (uint8_t)lsym;
         if (c.mode) c.scr.RK[so + v] = s + hp;
         if (v == 0) c.blocks[c.b0 + slot].orig_ptr = s + j;
     }
@@ -1734,8 +1807,8 @@ __device__ __forceinline__ void emit_vals(const Ctx& c, uint32_t slot, uint32_t 
 {
     if (valid) {
         const uint64_t so = (uint64_t)slot * c.scr.stride;
-        st_nt(c.scr.SA + so + s + j, v);
-        st_nt(c.scr.LL + so + s + j, (uint8_t)lsym);
+        c.scr.SA[so + s + j] = v;
+        c.scr.LL[so + s + j] = (uint8_t)lsym;
         if (c.mode) c.scr.RK[so + v] = s + hp;
         if (v == 0) c.blocks[c.b0 + slot].orig_ptr = s + j;
     }
@@ -1842,7 +1915,7 @@ __global__ void __launch_bounds__(256) k3_sort_w(Ctx c, const uint64_t* __restri
             const uint32_t j = valid ? lane - gstart : 0u;
             const uint32_t* sv = (par ? c.scr.V : c.scr.SA) + (uint64_t)slot * c.scr.stride + s;
             const KeySrc ks = key_src(c, slot, par);
-            const uint32_t v = ld_nt(sv + j);
+            const uint32_t v = sv[j];
             uint32_t ls;
             uint64_t k = elem_key<DBL>(c, ks, slot, s + j, v, ls);
             if (!valid) k = ~0ull;
@@ -1969,7 +2042,7 @@ __device__ __forceinline__ void grp_load_vals(const Ctx& c, GrpIn<E>& x, bool ok
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         const uint32_t i = (uint32_t)(wid * 64 * E + e * 64 + lane);
-        x.v[e] = ld_nt(sv + (i < m ? i : 0u));
+        x.v[e] = sv[i < m ? i : 0u];
     }
     x.v0 = sv[0];
 }
@@ -2175,38 +2248,23 @@ k3_sort_lds(Ctx c, const uint64_t* __restrict__ items,
     uint32_t* wcnt = ur_all[g] + wid * 256;
     uint32_t* sc = sc_all[g];
     const uint64_t lt = lanemask_lt();
-    // binned list: dynamic pops from the XCD's queue (a workgroup per group for
-    // NW = 4, a wave per group for NW = 1), so an XCD's groups are worked in
-    // list order (neighbouring groups share a block's PSS in its L2).
+    // binned list: workgroup L walks the per-XCD segment L mod 8 with a fixed
+    // stride (a workgroup per group for NW >= 4, a wave per group for NW = 1),
+    // so an XCD's groups are worked in list order (neighbouring groups share
+    // a block's PSS in its L2).
     // hard_n: an unbinned list of *hard_n groups, grid-strided.
     constexpr uint32_t NONE = 0xFFFFFFFFu;
-    __shared__ uint32_t qs[8];
-    __shared__ uint32_t job_sh;
-    const uint32_t xs = xcc_id();
-    if (!hard_n) load_qsizes_binned(c, qs);
     const uint32_t nwk = gridDim.x * (uint32_t)IPW;
     const uint32_t e_end = hard_n ? *hard_n : 0u;
-    WaveQueue<1> wq;
     uint32_t it_s = blockIdx.x * (uint32_t)IPW + (uint32_t)g;   // hard_n walk
-#ifndef STARCH_LDS_DYN
-#define STARCH_LDS_DYN 0
-#endif
     const uint32_t xs8 = blockIdx.x & 7u;                        // static: segment L mod 8
     const uint32_t s_end = hard_n ? e_end : c.qseg[xs8 + 1];
     const uint32_t s_nwk = hard_n ? nwk : (gridDim.x >> 3) * (uint32_t)IPW;
     if (!hard_n) it_s = c.qseg[xs8] + (blockIdx.x >> 3) * (uint32_t)IPW + (uint32_t)g;
     auto next_item = [&]() -> uint32_t {
-        if (hard_n || !STARCH_LDS_DYN) {
-            const uint32_t r = it_s < s_end ? it_s : NONE;
-            it_s += s_nwk;
-            return r;
-        }
-        if constexpr (NW == 1) {
-            return wq.next(c.qhead, qs, c.qseg, xs);
-        } else {
-            const uint32_t j = wg_pop(c, qs, &job_sh, xs);
-            return j == NONE ? NONE : c.qseg[j >> 28] + (j & 0x0FFFFFFFu);
-        }
+        const uint32_t r = it_s < s_end ? it_s : NONE;
+        it_s += s_nwk;
+        return r;
     };
     // software pipeline (as k3_sort_grp): while a group sorts, the next
     // group's keys are in flight, and the rotations of the one after it
@@ -3602,17 +3660,11 @@ bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blk
             }
             if (ns2) {
                 bin(c.L.s2, ns2, bout);
-#ifdef STARCH_S2_LDS   // experiment: S2 groups by four waves of one rotation per lane
-                static const dim3 gs2l = resident(reinterpret_cast<const void*>(&k3_sort_lds<4, 1, D>));
-                hipLaunchKernelGGL((k3_sort_lds<4, 1, D>), gs2l, dim3(256), 0, st, c, bout, nullptr);
-                sstat("S2");
-#else
                 clear_h();
                 hipLaunchKernelGGL((k3_sort_grp<1, 4, D>), gs2, dim3(256), 0, st, c, bout, c.L.s2);
                 sstat("S2");
                 hipLaunchKernelGGL((k3_sort_lds<1, 4, D>), dim3(ncu / 2), dim3(256), 0, st, c, c.L.s2, hard_n);
                 sstat("S2-hard");
-#endif
             }
             if (nw) {
                 bin(c.L.w, nw, bout);
