@@ -4,13 +4,9 @@
 
 namespace bz {
 
-struct BwtScratch {            // 40 (+18 with bwt_kmat) bytes per rotation per batch slot
+struct BwtScratch {            // 40 bytes per rotation per batch slot (+ 1 for LL)
     uint64_t* K;
     uint64_t* K2;
-    uint64_t* KM0;             // round 0 (bwt3, bwt_kmat() only, else null): every rotation's key window next to SA, and the
-    uint64_t* KM1;             //   partition ping-pong copy (no key gathers in the round-0 sorts)
-    uint8_t* LS0;              // round 0: the rotation's last-column symbol next to SA, ping-pong
-    uint8_t* LS1;
     uint32_t* V;
     uint32_t* V2;
     uint32_t* SA;              // sorted rotation order (ptr[] of bz:blocksort.c)
@@ -21,15 +17,10 @@ struct BwtScratch {            // 40 (+18 with bwt_kmat) bytes per rotation per 
     uint64_t stride;           // elements per slot
 };
 
-// STARCH_KMAT=1: round 0 materialises keys + last symbols next to SA (measured
-// slower on cfg2: 25.9 vs 23.7 ms, the extra 18 B/rotation of writes cost more
-// than the gathers they save); the encoder allocates KM0..LS1 only when set
-bool bwt_kmat();
-bool bwt_kgather();
 void launch_bwt(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blkbytes, uint64_t stride,
                 const BwtScratch& scr, unsigned long long* stats, hipStream_t st);
 // v3 (default): batch-wide segmented sort + doubling on ties (bz2_bwt3.hip).
-// hctr: pinned host memory of >= 16 u32; stats[0..2] += rounds, periodic, tied rotations.
+// hctr: pinned host memory of >= 32 u32; stats[0..2] += rounds, periodic, tied rotations.
 // Returns false when no block needed prefix doubling (then none is periodic).
 bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blkbytes, uint64_t stride,
                  const BwtScratch& scr, DevBuf& meta, uint32_t* hctr, unsigned long long* stats, hipStream_t st,

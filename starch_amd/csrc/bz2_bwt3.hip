@@ -21,9 +21,9 @@
 //               and a shift, so keys are never stored
 //   k3_hist     per 32k-rotation tile: 4096-bucket histogram of the top 12 bits
 //   k3_scan     per block: bucket starts, per-tile cursors, size-class lists
-//   k3_scatter  rotations -> bucket order in SA.  Persistent, per-XCD queues:
-//               each XCD streams ITS blocks one at a time, so the scattered
-//               4-B writes of a block meet in that XCD's 4 MB L2
+//   k3_scatter_lds  rotations -> bucket order in SA, staged in LDS.  Persistent,
+//               per-XCD queues: each XCD streams ITS blocks one at a time, so
+//               the writes of a block meet in that XCD's 4 MB L2
 //   k3_bin_*    every work list is binned by block into 8 per-XCD segments
 //               (blocks x, x+8, ... in order), so the persistent kernels below
 //               touch ~one block's PSS per XCD at a time (L2-resident)
@@ -51,12 +51,8 @@
 #include "bz2_int.hpp"
 #include "bz2_bwt.hpp"
 
-#include <stdio.h>
-#include <string.h>
-
 #include <algorithm>
 #include <type_traits>
-#include <vector>
 
 namespace bz {
 namespace {
@@ -88,8 +84,8 @@ constexpr uint32_t RBITS = 20;          // rank bits (n <= 899,985 < 2^20)
 constexpr uint32_t TEXT_ROUNDS = 4;     // max text-extension rounds before doubling
 
 // counters (u32) in the meta buffer
-enum { C_W = 0, C_S, C_S2, C_M1, C_M2, C_M3, C_L0, C_L1, C_T0, C_T1, C_TIE_ELEMS, C_ERR, C_TS0, C_TS1, C_H, C_DBG2,
-       C_DBGL, C_M0, C_STG, C_STA, C_STW, C_STE, C_STLP, C_STH, C_HG, C_HGC, C_GB, C_LM0, C_LM1, C_N = 30 };
+enum { C_W = 0, C_S, C_S2, C_M1, C_M2, C_M3, C_L0, C_L1, C_T0, C_T1, C_TIE_ELEMS, C_ERR, C_TS0, C_TS1, C_H, C_M0,
+       C_HG, C_HGC, C_GB, C_LM0, C_LM1, C_N };
 
 // item = slot[63:52] | start[51:32] | size[31:12] | parity[7] | shift[6:0]
 __device__ __forceinline__ uint64_t mk_item(uint32_t slot, uint32_t s, uint32_t m, uint32_t shift, uint32_t par)
@@ -166,11 +162,9 @@ struct Ctx {
     uint32_t lsel;          // L list that part/classify pushes into
     uint32_t tsel;          // tie list the sorts push into
     uint32_t mode;          // 0: SA only (round 0, text rounds); 1: doubling (RK, runs)
-    uint32_t keysrc;        // 0: PSS at the text-round offset; 1: keys by group position (kA/kB)
-    uint64_t* kA;           // keysrc 1: keys of parity-0 items (round 0: KM0, doubling: K2) ...
-    uint64_t* kB;           // ... and of parity-1 items (round 0: KM1, doubling: K)
-    uint8_t* lA;            // round 0: last-column symbols by position, parity 0 / 1 (LS0 / LS1);
-    uint8_t* lB;            //   null while doubling (then read from the block bytes)
+    uint32_t keysrc;        // 0: PSS at the text-round offset; 1 (doubling): keys by group position (kA/kB)
+    uint64_t* kA;           // keysrc 1: keys of parity-0 items (K2) ...
+    uint64_t* kB;           // ... and of parity-1 items (K)
     uint32_t rtext;         // text round (0: round 0)
     uint32_t* qhead;        // 8 queue heads of the current persistent launch
     const uint32_t* qseg;   // 9 per-XCD segment offsets of the current binned list
@@ -192,10 +186,6 @@ __device__ __forceinline__ uint64_t lanemask_lt()
     const int lane = threadIdx.x & 63;
     return lane ? (~0ull >> (64 - lane)) : 0ull;
 }
-
-#ifndef STARCH_W_UNROLL
-#define STARCH_W_UNROLL 0   // k3_sort_w's rank loops unrolled by 4 (experiment)
-#endif
 
 // Append `item` for every lane with pred to list/ctr; one atomic per wave.
 // Must be reached by all 64 lanes of the wave.
@@ -264,7 +254,6 @@ __device__ __forceinline__ uint64_t pss_bits(const uint64_t* __restrict__ w, uin
 struct KeySrc {
     const uint64_t* pss;
     const uint64_t* k;      // keys by position of this group's buffer (kA or kB by parity), slot base
-    const uint8_t* l;       // last-column symbols by position (lA / lB by parity), slot base; or null
     uint32_t B, kbits, n, off, usek;
     __device__ __forceinline__ uint64_t operator()(uint64_t q, uint32_t r) const
     {
@@ -278,9 +267,6 @@ struct KeySrc {
     {
         uint32_t rr = r + off;
         rr = rr >= n ? rr - n : rr;
-#ifdef STARCH_EXP_NOGATHER   // timing experiment only: keys from a cache-resident window (wrong order)
-        rr &= 4095u;
-#endif
         const uint64_t bit = (uint64_t)rr * B;
         const uint64_t q = bit >> 6;
         const uint32_t p = (uint32_t)(bit & 63u);
@@ -292,11 +278,7 @@ struct KeySrc {
     // (rotation 0 wraps: its symbol is the block's last)
     __device__ __forceinline__ uint64_t key_pss(uint32_t r, uint32_t& ls) const
     {
-#ifdef STARCH_EXP_NOGATHER
-        const uint32_t pr = r & 4095u;
-#else
         const uint32_t pr = r ? r - 1u : n - 1u;
-#endif
         uint32_t rr = r + off;
         rr = rr >= n ? rr - n : rr;
         if (off == 0 && r != 0) {
@@ -330,7 +312,6 @@ __device__ __forceinline__ KeySrc key_src(const Ctx& c, uint32_t slot, uint32_t 
     k.usek = c.keysrc;
     k.pss = c.scr.K + so;
     k.k = (par ? c.kB : c.kA) + so;
-    k.l = c.lA ? (par ? c.lB : c.lA) + so : nullptr;
     if (c.rtext == 0) {
         k.kbits = g.KB;
         k.off = 0;
@@ -368,7 +349,7 @@ __device__ __forceinline__ uint64_t elem_key(const Ctx& c, const KeySrc& ks, uin
                                              uint32_t& ls)
 {
     if constexpr (DBL) {
-        ls = ks.l ? ks.l[q] : last_sym(c, slot, v);
+        ls = last_sym(c, slot, v);
         return ks.k[q];
     } else {
         return ks.key_pss(v, ls);
@@ -579,87 +560,13 @@ __global__ void __launch_bounds__(ST) k3_scan(Ctx c)
 }
 
 // ---------------------------------------------------------------------------
-// k3_scatter: rotations -> bucket order in SA (persistent, per-XCD block
-// streams: queue x holds the tiles of blocks x, x+8, ... in order)
-// ---------------------------------------------------------------------------
-constexpr int SCT = 1024;
-
-template <int NB>
-__global__ void __launch_bounds__(SCT) k3_scatter(Ctx c)
-{
-    __shared__ uint32_t cur[NB], tot[NB];
-    __shared__ uint32_t qs[8];
-    __shared__ uint32_t job_sh;
-    const int tid = threadIdx.x;
-    const uint32_t x = xcc_id();
-    if (tid < 8) qs[tid] = ((uint32_t)tid < c.nb ? (c.nb - tid + 7) / 8 : 0u) * MAXT;
-    __syncthreads();
-    for (;;) {
-        const uint32_t job = wg_pop(c, qs, &job_sh, x);
-        if (job == 0xFFFFFFFFu) break;
-        const uint32_t y = job >> 28, k = job & 0x0FFFFFFFu;
-        const uint32_t slot = y + 8u * (k / MAXT), tile = k % MAXT;
-        const uint32_t b = c.b0 + slot;
-        const uint32_t n = c.blocks[b].n;
-        const uint32_t t0 = tile * PTILE;
-        if (t0 >= n) continue;                       // uniform
-        const uint64_t so = (uint64_t)slot * c.scr.stride;
-        const uint32_t* th = tile_hist(c, slot);
-        for (int i = tid; i < NB; i += SCT) { cur[i] = th[(uint64_t)tile * NB + i]; tot[i] = th[(uint64_t)MAXT * NB + i]; }
-        __syncthreads();
-        const Geo geo = c.L.geo[slot];
-        const uint32_t B = geo.B;
-        const uint64_t* pss = c.scr.K + so;
-        uint32_t* SA = c.scr.SA + so;
-        const uint32_t e = n - t0 < (uint32_t)PTILE ? n - t0 : (uint32_t)PTILE;
-        // SU consecutive rotations per thread and step: digits from four PSS
-        // words (funnel shifts), then the LDS cursor atomics, then the stores,
-        // so each phase has SU in flight
-        constexpr int SU = 16;
-        for (uint32_t q0 = tid * SU; q0 < e; q0 += SU * SCT) {
-            uint32_t d[SU], p[SU];
-            {
-                const uint64_t bit0 = (uint64_t)(t0 + q0) * B;
-                const uint64_t qw = bit0 >> 6;
-                const uint32_t p0 = (uint32_t)(bit0 & 63u);
-                const uint64_t w[4] = {pss[qw], pss[qw + 1], pss[qw + 2], pss[qw + 3]};
-#pragma unroll
-                for (int u = 0; u < SU; ++u) {
-                    const uint32_t bit = p0 + (uint32_t)u * B;  // < 64 + 15 * 8
-                    const uint32_t ix = bit >> 6, pb = bit & 63u;
-                    const uint64_t a = ix == 0 ? w[0] : ix == 1 ? w[1] : w[2];
-                    const uint64_t nx = ix == 0 ? w[1] : ix == 1 ? w[2] : w[3];
-                    d[u] = top_digit((a << pb) | ((nx >> 1) >> (63u - pb)), geo);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < SU; ++u) {
-                const uint32_t q = q0 + u;
-                p[u] = q < e ? atomicAdd(&cur[d[u]], 1u) : 0u;
-            }
-#pragma unroll
-            for (int u = 0; u < SU; ++u) {
-                const uint32_t q = q0 + u;
-                if (q < e) {
-                    const uint32_t r = t0 + q;
-                    SA[p[u]] = r;
-                    if (tot[d[u]] == 1u) {           // singleton bucket: final
-                        c.scr.LL[so + p[u]] = (uint8_t)pss_bits(pss, (uint64_t)(r ? r - 1u : n - 1u) * B, B);
-                        if (r == 0) c.blocks[b].orig_ptr = p[u];
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------------------
-// k3_scatter_lds: the same scatter with the writes staged in LDS.  Each 32 K
+// k3_scatter_lds: rotations -> bucket order in SA (persistent, per-XCD block
+// streams: queue x holds the tiles of blocks x, x+8, ... in order), with the
+// writes staged in LDS.  Each 32 K
 // tile is handled in two 16 K halves: the half's rotations are counting-
 // sorted by bucket inside LDS (entry = digit << 15 | rotation in the tile), then written
 // out in local order, so consecutive threads store consecutive SA positions
-// of a bucket's run instead of one scattered 4-byte store per rotation (the
+// of a bucket's run instead of one scattered 4-byte store per rotation (a
 // direct scatter's writes cost ~2.5-3.5x their bytes in HBM traffic).
 //
 // Thread t owns bins [t * BPT, (t + 1) * BPT): it scans their local counts and
@@ -669,7 +576,9 @@ __global__ void __launch_bounds__(SCT) k3_scatter(Ctx c)
 // reads two LDS words per rotation.  The last stage of a job pops the next
 // job and loads its cursor row and first PSS words while it writes out.
 // ---------------------------------------------------------------------------
-template <int NB, bool MAT>
+constexpr int SCT = 1024;
+
+template <int NB>
 __global__ void __launch_bounds__(SCT) k3_scatter_lds(Ctx c)
 {
     // rotations staged at a time: half a tile (4096 bins), a quarter (8192 bins: LDS)
@@ -686,17 +595,11 @@ __global__ void __launch_bounds__(SCT) k3_scatter_lds(Ctx c)
     // the next 8 key bits below the top-level digit of every staged rotation,
     // by rotation: written next to the SA entries of the heavy (L-class)
     // buckets, where k3_part_l's first partition reads them instead of
-    // gathering each rotation's key again (the plain instantiation only)
-    __shared__ __attribute__((aligned(16))) uint8_t stage8[MAT ? 16 : SH_HALF];
+    // gathering each rotation's key again
+    __shared__ __attribute__((aligned(16))) uint8_t stage8[SH_HALF];
     __shared__ uint32_t scan_sh[SCT / 64];
     __shared__ uint32_t qs[8];
     __shared__ uint32_t job_sh;
-    // round 0 writes every rotation's key window and last-column symbol next to
-    // its SA entry (KM0 / LS0), from the stage's PSS words held in LDS
-    // (MAT: bwt_kmat() only; the plain instantiation keeps no PSS window in LDS)
-    constexpr uint32_t PWN = MAT ? (SH_HALF + 1) * 8 / 64 + 4 : 1;   // words for B <= 8
-    __shared__ uint64_t pw[PWN];
-    constexpr bool mat = MAT;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const uint32_t x = xcc_id();
     if (tid < 8) qs[tid] = ((uint32_t)tid < c.nb ? (c.nb - tid + 7) / 8 : 0u) * MAXT;
@@ -738,8 +641,6 @@ __global__ void __launch_bounds__(SCT) k3_scatter_lds(Ctx c)
         const uint64_t* pss = c.scr.K + so;
         uint32_t* SA = c.scr.SA + so;
         uint8_t* LL = c.scr.LL + so;
-        uint64_t* KM = c.kA + so;
-        uint8_t* LS = c.lA ? c.lA + so : nullptr;
         if (!pre) {
             load_row(th, tile);
             load_w0(pss, t0, B);
@@ -760,14 +661,6 @@ __global__ void __launch_bounds__(SCT) k3_scatter_lds(Ctx c)
         for (uint32_t h0 = 0; h0 < e; h0 += SH_HALF) {
             const uint32_t he = e - h0 < SH_HALF ? e - h0 : SH_HALF;
             const bool last = h0 + SH_HALF >= e;
-            // PSS words of this stage's keys and last symbols: rotations
-            // [t0 + h0 - 1, t0 + h0 + he) plus one key window
-            const uint32_t rs = t0 + h0;
-            const uint64_t wbase = rs ? ((uint64_t)(rs - 1) * B) >> 6 : 0;
-            if constexpr (mat) {
-                const uint64_t wend = (((uint64_t)(rs + he) * B + 64) >> 6) + 2;
-                for (uint64_t w = wbase + tid; w < wend; w += SCT) pw[w - wbase] = pss[w];
-            }
             // the next job's number travels through job_sh behind this stage's barriers
             if (last && tid == 0) job_sh = xq_pop(c.qhead, qs, x);
             // digits of SU consecutive rotations from four PSS words; local counts
@@ -793,11 +686,9 @@ __global__ void __launch_bounds__(SCT) k3_scatter_lds(Ctx c)
                     d[u] = top_digit(v, geo);
                     sdw[u / 4] |= ((uint32_t)(v >> sds) & 0xFFu) << (8 * (u % 4));
                 }
-                if constexpr (!MAT) {                    // SU bytes per thread, in rotation order
-                    uint32_t* s8 = reinterpret_cast<uint32_t*>(stage8 + q0);
+                uint32_t* s8 = reinterpret_cast<uint32_t*>(stage8 + q0);   // SU bytes per thread, in rotation order
 #pragma unroll
-                    for (int q = 0; q < SU / 4; ++q) s8[q] = sdw[q];
-                }
+                for (int q = 0; q < SU / 4; ++q) s8[q] = sdw[q];
             }
 #pragma unroll
             for (int u = 0; u < SU; ++u) p[u] = (q0 + u < he) ? atomicAdd(&lst[d[u]], 1u) : 0u;
@@ -861,24 +752,10 @@ __global__ void __launch_bounds__(SCT) k3_scatter_lds(Ctx c)
                 const uint32_t en = se[i];
                 const uint32_t pos = (en + j) & PMASK;
                 SA[pos] = r;
-                uint32_t ls = 0;
-                if (mat && r) {   // (MAT: compile-time)
-                    const uint64_t bit = (uint64_t)(r - 1) * B - (wbase << 6);
-                    const uint32_t q = (uint32_t)(bit >> 6), p = (uint32_t)(bit & 63u);
-                    ls = (uint32_t)(((pw[q] << p) | ((pw[q + 1] >> 1) >> (63u - p))) >> (64u - B));
-                } else if (mat || (en & F_ONE)) {
-                    ls = (uint32_t)pss_bits(pss, (uint64_t)(r ? r - 1u : n - 1u) * B, B);
-                }
-                if (mat) {
-                    const uint64_t bit = (uint64_t)r * B - (wbase << 6);
-                    const uint32_t q = (uint32_t)(bit >> 6), p = (uint32_t)(bit & 63u);
-                    KM[pos] = ((pw[q] << p) | ((pw[q + 1] >> 1) >> (63u - p))) >> (64u - geo.KB);
-                    LS[pos] = (uint8_t)ls;
-                }
                 if (en & F_ONE) {                      // singleton bucket: final
-                    LL[pos] = (uint8_t)ls;
+                    LL[pos] = (uint8_t)pss_bits(pss, (uint64_t)(r ? r - 1u : n - 1u) * B, B);
                     if (r == 0) c.blocks[b].orig_ptr = pos;
-                } else if (!mat && (en & F_L)) {       // L class: its first partition digit (LL is free there until then)
+                } else if (en & F_L) {                 // L class: its first partition digit (LL is free there until then)
                     LL[pos] = stage8[(v & 0x7FFFu) - h0];
                 }
                 }
@@ -1021,21 +898,9 @@ constexpr uint32_t PL_CAP = 40960;
 #endif
 constexpr uint32_t PL_STG = STARCH_PL_STG;
 
-#ifdef STARCH_PL_PROF   // timing experiment (dev builds): k3_part_l's phases, shader clocks summed over workgroups
-__device__ unsigned long long g_plprof[16];
-#define PLT(v) const uint64_t v = __builtin_readcyclecounter()
-#define PLA(i, a, b) plp[i] += (b) - (a)
-#else
-#define PLT(v)
-#define PLA(i, a, b)
-#endif
 template <bool DBL>
 __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restrict__ items)
 {
-#ifdef STARCH_PL_PROF
-    uint64_t plp[8] = {};
-    PLT(tk0);
-#endif
     __shared__ uint32_t wh[LW][256];
     __shared__ uint32_t st[256], cur[256], cntd[256];
     __shared__ uint32_t scan_sh[LW + 1];
@@ -1058,11 +923,6 @@ __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restric
         const uint32_t slot = it_slot(item), s = it_start(item), m = it_size(item), shift = it_shift(item),
                        par = it_par(item);
         if (m == 0) continue;                          // taken by the grid-wide path (k3_hg_pick); uniform
-        PLT(t0);
-#ifdef STARCH_PL_PROF
-        plp[6] += m;
-        plp[5] += 1;
-#endif
         const uint32_t b = c.b0 + slot;
         const uint64_t so = (uint64_t)slot * c.scr.stride;
         const uint64_t base = so + s;
@@ -1070,7 +930,6 @@ __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restric
         const uint32_t* sv = (par ? c.scr.V : c.scr.SA) + base;
         uint32_t* dv = (par ? c.scr.SA : c.scr.V) + base;
         uint64_t* dk = (par ? c.kA : c.kB) + base;              // keys by position (keysrc 1) only
-        uint8_t* dl = DBL && ks.l ? (par ? c.lA : c.lB) + base : nullptr;   // round 0: last symbols move too
         uint32_t* SA = c.scr.SA + base;
         uint32_t* RK = c.scr.RK + so;
         const uint32_t db = shift < 8 ? shift : 8;
@@ -1086,8 +945,6 @@ __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restric
         for (int i = tid; i < LW * 256; i += LT) (&wh[0][0])[i] = 0;
         if (tid == 0) big[256] = 0;
         __syncthreads();
-        PLT(t1);
-        PLA(0, t0, t1);
 #ifndef STARCH_PART_PU
 #define STARCH_PART_PU 24   // elements per thread and step, loads batched (cfg2 block sort: 4 -> 16 -> 24 -> 32: 21.3, 20.6, 20.4, 20.7 ms)
 #endif
@@ -1125,20 +982,15 @@ __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restric
                 if (i0 + u * LT + tid < m) atomicAdd(&wh[wid][d[u]], 1u);
         }
         __syncthreads();
-        PLT(t2);
-        PLA(1, t1, t2);
         uint32_t tcount = 0;
         if (tid < 256) for (int w = 0; w < LW; ++w) tcount += wh[w][tid];
         const uint32_t pre = block_excl_scan_add<uint32_t>(tid < 256 ? tcount : 0u, scan_sh, (uint32_t*)nullptr);
         if (tid < 256) { st[tid] = pre; cur[tid] = pre; cntd[tid] = tcount; }
         __syncthreads();
-        PLT(t3);
-        PLA(2, t2, t3);
         const bool staged = !DBL && m <= PL_STG && !(STARCH_PL_STG == 0);
         for (uint32_t i0 = 0; i0 < m; i0 += PU * LT) {
             uint32_t v[PU];
             uint64_t k[PU];
-            uint8_t lsy[PU];
 #pragma unroll
             for (int u = 0; u < PU; ++u) {
                 const uint32_t i = i0 + u * LT + tid;
@@ -1165,17 +1017,11 @@ __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restric
             }
 #pragma unroll
             for (int u = 0; u < PU; ++u) {
-                const uint32_t i = i0 + u * LT + tid;
-                lsy[u] = dl ? ks.l[s + (i < m ? i : 0u)] : (uint8_t)0;
-            }
-#pragma unroll
-            for (int u = 0; u < PU; ++u) {
                 if (i0 + u * LT + tid < m) {
                     const uint32_t p = atomicAdd(&cur[(uint32_t)((k[u] >> sh2) & dmask)], 1u);
                     if (!DBL && staged) stg[p] = v[u];
                     else dv[p] = v[u];
                     if constexpr (DBL) dk[p] = k[u];
-                    if (dl) dl[p] = lsy[u];
                 }
             }
         }
@@ -1184,15 +1030,13 @@ __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restric
             for (uint32_t i = tid; i < m; i += LT) dv[i] = stg[i];
             __syncthreads();
         }
-        PLT(t4);
-        PLA(3, t3, t4);
         uint32_t nruns = 0;
         if (tid < 256) {
             const uint32_t cc = cntd[tid], ss = st[tid];
             if (cc == 1) {
                 const uint32_t v = dv[ss];
                 if (!par) SA[ss] = v;
-                c.scr.LL[base + ss] = dl ? dl[ss] : last_sym(c, slot, v);
+                c.scr.LL[base + ss] = last_sym(c, slot, v);
                 if (c.mode) RK[v] = s + ss;
                 if (v == 0) c.blocks[b].orig_ptr = s + ss;
                 nruns = 1;
@@ -1211,8 +1055,6 @@ __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restric
             if (c.mode && (tid & 63) == 0 && r) atomicAdd(&c.L.runs[slot], r);
         }
         __syncthreads();
-        PLT(t5);
-        PLA(4, t4, t5);
         const uint32_t nbig = big[256];
         for (uint32_t q = 0; q < nbig; ++q) {
             const uint32_t d = big[q];
@@ -1220,7 +1062,7 @@ __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restric
             for (uint32_t i = tid; i < cc; i += LT) {
                 const uint32_t v = dv[ss + i];
                 if (!par) SA[ss + i] = v;
-                c.scr.LL[base + ss + i] = dl ? dl[ss + i] : last_sym(c, slot, v);
+                c.scr.LL[base + ss + i] = last_sym(c, slot, v);
                 if (c.mode) RK[v] = s + ss;
                 if (v == 0) c.blocks[b].orig_ptr = s + ss + i;
             }
@@ -1231,17 +1073,7 @@ __global__ void __launch_bounds__(LT) k3_part_l(Ctx c, const uint64_t* __restric
             }
         }
         __syncthreads();
-        PLT(t6);
-        PLA(7, t5, t6);
     }
-#ifdef STARCH_PL_PROF
-    PLT(tk1);
-    plp[4] += 0;
-    if (tid == 0) {
-        for (int q = 0; q < 8; ++q) atomicAdd(&g_plprof[q], (unsigned long long)plp[q]);
-        atomicAdd(&g_plprof[8], (unsigned long long)(tk1 - tk0));
-    }
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -1297,7 +1129,7 @@ constexpr uint32_t HG_SKIP_ALL = 1, HG_SKIP_RELABEL = 2;
 // tie group for the next round); the other two keep the shift.  One pass per
 // round instead of a digit level per 8 key bits, each moving the whole group.
 constexpr uint32_t HG_THREE = 3;
-// The three-way split in place (par 0, no last-column stream): only the
+// The three-way split in place (par 0): only the
 // elements outside their part's range move (each into a hole of its part,
 // through short lists), and the equal part -- most of the group -- stays where
 // it is.  Its rank (RK) is any position inside its range (ranks only have to
@@ -1486,8 +1318,7 @@ __global__ void __launch_bounds__(256) k3_hg_scan(Ctx c)
     if (2 * neq > g.m) {                              // uniform: three-way split around the first key
         const uint32_t ngt = g.m - neq - nlt;
         const uint32_t st3[3] = {0u, nlt, nlt + neq}, n3[3] = {nlt, neq, ngt};
-        const KeySrc ks = key_src(c, g.slot, g.par);
-        const bool ip = g.par == 0 && ks.l == nullptr;
+        const bool ip = g.par == 0;
         if (tid == 0) {
             c.L.hg_flag[q] = ip ? HG_THREE_IP : HG_THREE;
             if (ip) {
@@ -1651,7 +1482,6 @@ __global__ void __launch_bounds__(256) k3_hg_scatter(Ctx c)
         const uint32_t* sv = (g.par ? c.scr.V : c.scr.SA) + base;
         uint32_t* dv = (g.par ? c.scr.SA : c.scr.V) + base;
         uint64_t* dk = (g.par ? c.kA : c.kB) + base;
-        uint8_t* dl = DBL && ks.l ? (g.par ? c.lA : c.lB) + base : nullptr;
         uint32_t* cur = c.L.hg_info + (uint64_t)q * 512 + 256;
         cnt[tid] = 0;
         __syncthreads();
@@ -1684,7 +1514,6 @@ __global__ void __launch_bounds__(256) k3_hg_scatter(Ctx c)
                 const uint32_t p = cnt[d[u]] + r[u];
                 dv[p] = v[u];
                 if constexpr (DBL) dk[p] = k[u];
-                if (dl) dl[p] = ks.l[g.s + i];
             }
         }
         __syncthreads();
@@ -1713,7 +1542,6 @@ __global__ void __launch_bounds__(256) k3_hg_final(Ctx c)
         const uint32_t flag = c.L.hg_flag[q];
         if (flag == HG_SKIP_RELABEL) continue;
         const uint64_t so = (uint64_t)g.slot * c.scr.stride, base = so + g.s;
-        const KeySrc ks = key_src(c, g.slot, g.par);
         if (flag == HG_THREE_IP) {                    // uniform: in SA already (par 0)
             const uint32_t neq = c.L.hg_eqlt[2 * q], nlt = c.L.hg_eqlt[2 * q + 1], ngt = g.m - neq - nlt;
             const uint32_t rk = c.L.hg_rank[q];
@@ -1746,7 +1574,6 @@ __global__ void __launch_bounds__(256) k3_hg_final(Ctx c)
             continue;
         }
         const uint32_t* dv = (g.par ? c.scr.SA : c.scr.V) + base;
-        const uint8_t* dl = ks.l ? (g.par ? c.lA : c.lB) + base : nullptr;
         const uint32_t* info = c.L.hg_info + (uint64_t)q * 512;
         // final bins' sizes (bin end = next bin's start; the last ends at m)
         const uint32_t st = info[tid] & ~HG_FINAL;
@@ -1768,7 +1595,7 @@ __global__ void __launch_bounds__(256) k3_hg_final(Ctx c)
             const uint32_t v = dv[p];
             if (!g.par) c.scr.SA[base + p] = v;
             const uint32_t be = lo < 255 ? (info[lo + 1] & ~HG_FINAL) : g.m;
-            if (be - b0 == 1) c.scr.LL[base + p] = dl ? dl[p] : last_sym(c, g.slot, v);   // ties: once resolved
+            if (be - b0 == 1) c.scr.LL[base + p] = last_sym(c, g.slot, v);   // ties: once resolved
             if (c.mode) c.scr.RK[so + v] = g.s + b0;
             if (v == 0) c.blocks[c.b0 + g.slot].orig_ptr = g.s + p;
         }
@@ -1923,9 +1750,6 @@ __global__ void __launch_bounds__(256) k3_sort_w(Ctx c, const uint64_t* __restri
             // scalar broadcasts when the pass holds one group, lane shuffles otherwise
             uint32_t r = 0;
             if (ng == 1) {
-#if STARCH_W_UNROLL
-#pragma unroll 4
-#endif
                 for (uint32_t q = 0; q < total; ++q) {
                     const uint64_t kq = ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(k >> 32), (int)q) << 32) |
                                         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)k, (int)q);
@@ -1933,9 +1757,6 @@ __global__ void __launch_bounds__(256) k3_sort_w(Ctx c, const uint64_t* __restri
                 }
             } else {
                 const uint32_t maxm = wave_reduce_max(valid ? m : 0u);
-#if STARCH_W_UNROLL
-#pragma unroll 4
-#endif
                 for (uint32_t q = 0; q < maxm; ++q) {
                     const bool in = valid && q < m;
                     const uint64_t kq = shfl64(k, in ? gstart + q : lane);
@@ -2061,11 +1882,9 @@ __device__ __forceinline__ uint32_t pss_rr(const KeySrc& ks, uint32_t r)
 }
 __device__ __forceinline__ uint32_t pss_pr(const KeySrc& ks, uint32_t r) { return r ? r - 1u : ks.n - 1u; }
 
-#ifndef STARCH_DEFER
-#define STARCH_DEFER 1     // deferred key combination: 0 never, 1 one-wave sorts only (measured best), 2 all
-#endif
+// deferred key combination: the one-wave sorts of the PSS rounds only (measured best)
 template <int NW, bool DBL>
-constexpr bool defer_keys() { return !DBL && (STARCH_DEFER == 2 || (STARCH_DEFER == 1 && NW == 1)); }
+constexpr bool defer_keys() { return !DBL && NW == 1; }
 
 template <int NW, int E, bool DBL>
 __device__ __forceinline__ void grp_load_keys(const Ctx& c, GrpIn<E>& x, int wid, int lane)
@@ -2183,20 +2002,6 @@ constexpr int sort_wpe(int NW, int E)
            : (NW == 1 ? (E == 2 ? STARCH_WPE_S : STARCH_WPE_GRP) : 1);
 }
 
-// STARCH_SORT_PROF (timing experiment, dev builds only): per-wave shader-clock
-// time of the sorts' phases, summed over the launch: k3_sort_grp into
-// g_sprof, the workgroup sorts k3_sort_lds<8|16, 4> (M2/M3) and <4, 4> (M1)
-// into g_sprof2
-#ifdef STARCH_SORT_PROF
-__device__ unsigned long long g_sprof[16];
-__device__ unsigned long long g_sprof2[16];
-#define SPROF(v) const uint64_t v = __builtin_readcyclecounter()
-#define SPACC(i, a, b) pacc[i] += (b) - (a)
-#else
-#define SPROF(v)
-#define SPACC(i, a, b)
-#endif
-
 template <int NW, int E, bool DBL>
 __global__ void __launch_bounds__(NW > 4 ? 64 * NW : 256) __attribute__((amdgpu_waves_per_eu(sort_wpe(NW, E))))
 k3_sort_lds(Ctx c, const uint64_t* __restrict__ items,
@@ -2276,11 +2081,7 @@ k3_sort_lds(Ctx c, const uint64_t* __restrict__ items,
     grp_load_keys<NW, E, DBL>(c, cur, wid, lane);
     nxt.item = it1 != NONE ? items[it1] : 0ull;
     grp_load_vals<NW, E>(c, nxt, it1 != NONE, wid, lane);
-#ifdef STARCH_SORT_PROF
-    uint64_t pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
     while (it != NONE) {
-    SPROF(t0);
     const uint64_t item = cur.item;
     const uint32_t slot = it_slot(item), s = it_start(item), m = it_size(item);
     grp_finish_keys<NW, E, DBL>(cur);
@@ -2309,8 +2110,6 @@ k3_sort_lds(Ctx c, const uint64_t* __restrict__ items,
         for (int w = 0; w < NW; ++w) diff |= red_all[w0 + w];
     }
     if ((diff >> KEYB) && tid % (64 * NW) == 0) atomicOr(&c.L.ctr[C_ERR], 1u);   // top bits not shared
-    SPROF(t1);
-    SPACC(0, t0, t1);
 
     bool moved = false;
     const uint64_t kdiff = diff & KMASK;
@@ -2374,9 +2173,6 @@ k3_sort_lds(Ctx c, const uint64_t* __restrict__ items,
 #pragma unroll
             for (int e = 0; e < E; ++e) k[e] = xk[wid * 64 * E + e * 64 + lane];
         };
-#ifdef STARCH_SORT_PROF
-        pacc[1] += __builtin_readcyclecounter() - t1;
-#endif
         if (mx <= LIMIT) {                         // uniform per group
 #pragma unroll
             for (int q = 0; q < BPT; ++q) { bst[tg * BPT + q] = run; bcur[tg * BPT + q] = run; run += loc[q]; }
@@ -2390,13 +2186,7 @@ k3_sort_lds(Ctx c, const uint64_t* __restrict__ items,
                 const uint32_t d = (uint32_t)((kj >> (lo + IDXB)) & (uint64_t)(NBIN - 1));
                 rs = bst[d];
                 re = bst[d + 1];
-#ifdef STARCH_SORT_STATS
-                atomicAdd(&c.L.ctr[C_STW], re - rs);
-#endif
             });
-#ifdef STARCH_SORT_STATS
-            if (tid % (64 * NW) == 0) atomicAdd(&c.L.ctr[C_STA], 1u);
-#endif
             moved = true;
         } else if (lo > 0) {
             // Second MSD digit for the sub-buckets larger than LIMIT: the w2 bits
@@ -2508,18 +2298,11 @@ k3_sort_lds(Ctx c, const uint64_t* __restrict__ items,
                     }
                 });
                 moved = true;
-                if (tg == 0) atomicAdd(&c.L.ctr[C_DBG2], 1u);
             }
         } else {
             gsync<NW>();                           // bcur/sc reads done before the LSD passes
         }
     }
-    SPROF(t3);
-    SPACC(2, t1, t3);
-    if (!moved && kdiff && tid % (64 * NW) == 0) atomicAdd(&c.L.ctr[C_DBGL], 1u);
-#ifdef STARCH_SORT_STATS
-    if (tid % (64 * NW) == 0) { atomicAdd(&c.L.ctr[C_STG], 1u); atomicAdd(&c.L.ctr[C_STE], m); }
-#endif
     bool lsd_moved = false;
     for (int dbit = 0; dbit < KEYB && !moved; dbit += 8) {
         if ((kdiff >> dbit & 0xffull) == 0) continue;    // uniform per group
@@ -2583,9 +2366,6 @@ k3_sort_lds(Ctx c, const uint64_t* __restrict__ items,
 #pragma unroll
         for (int e = 0; e < E; ++e) k[e] = xk[wid * 64 * E + e * 64 + lane];
         lsd_moved = true;
-#ifdef STARCH_SORT_STATS
-        if (tid % (64 * NW) == 0) atomicAdd(&c.L.ctr[C_STLP], 1u);
-#endif
     }
     moved |= lsd_moved;
     if (!moved) {
@@ -2631,8 +2411,6 @@ k3_sort_lds(Ctx c, const uint64_t* __restrict__ items,
             for (int e = 0; e < E; ++e) hp[e] = hp[e] > pre ? hp[e] : pre;
         }
     }
-    SPROF(t4);
-    SPACC(3, t3, t4);
     // the group's rotations and keys were consumed into registers/LDS (their
     // loads complete) before any write of its SA range; the loads in flight
     // now belong to other groups' disjoint ranges
@@ -2662,8 +2440,6 @@ k3_sort_lds(Ctx c, const uint64_t* __restrict__ items,
             tb += (uint32_t)__popcll(tm[e]);
         }
     }
-    SPROF(t5);
-    SPACC(4, t4, t5);
     // rotate the pipeline
     const uint32_t it2 = it1 != NONE ? next_item() : NONE;
     cur = nxt;
@@ -2671,14 +2447,7 @@ k3_sort_lds(Ctx c, const uint64_t* __restrict__ items,
     grp_load_vals<NW, E>(c, nxt, it2 != NONE, wid, lane);
     it = it1;
     it1 = it2;
-    SPROF(t6);
-    SPACC(5, t5, t6);
-    SPACC(7, t0, t6);
     }
-#ifdef STARCH_SORT_PROF
-    if (lane == 0 && E == 4 && NW >= 4 && !DBL)
-        for (int q = 0; q < 8; ++q) atomicAdd(&g_sprof2[q + (NW == 4 ? 8 : 0)], (unsigned long long)pacc[q]);
-#endif
     tacc = wave_reduce_add<uint32_t>(tacc);
     if (lane == 0 && tacc) atomicAdd(c.L.ctr + C_TS0 + c.tsel, tacc);
 }
@@ -2697,11 +2466,7 @@ k3_sort_lds(Ctx c, const uint64_t* __restrict__ items,
 #ifndef STARCH_HARD_Q
 #define STARCH_HARD_Q 32
 #endif
-#ifndef STARCH_GRP_EARLY
-#define STARCH_GRP_EARLY 1   // the next group's key gathers issued before this group's sort
-#endif
 constexpr uint32_t HARD_Q = STARCH_HARD_Q;
-
 
 template <int NW, int E, bool DBL>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sort_wpe(NW, E))))
@@ -2753,13 +2518,9 @@ k3_sort_grp(Ctx c, const uint64_t* __restrict__ items,
 #endif                           // span more blocks per XCD (S2 fetch 6.5 -> 14.5 GB per cfg2 step)
     WaveQueue<E == 4 ? STARCH_GRP_CHUNK_S2 : STARCH_GRP_CHUNK> wq;
     constexpr uint32_t NONE = 0xFFFFFFFFu;
-    // software pipeline, three groups deep: while group n sorts, the keys of
-    // n + 1 are issued (its rotations arrived an iteration ago) and the
-    // rotations of n + 2 are in flight (STARCH_GRP_DEEP=0: two deep, the
-    // rotations of n + 1 issued only one iteration before its keys)
-#ifndef STARCH_GRP_DEEP
-#define STARCH_GRP_DEEP 0   // measured no faster (cfg2 sort 23.2 vs 23.3 ms, profiles/r03_v3/sweep_deep*.json)
-#endif
+    // software pipeline, two groups deep: while group n sorts, the keys of
+    // n + 1 are issued (its rotations were issued an iteration ago) and the
+    // items of n + 2 and n + 3 are fetched
     uint32_t it = wq.next(c.qhead, qs, c.qseg, xs);
     uint32_t it1 = it != NONE ? wq.next(c.qhead, qs, c.qseg, xs) : NONE;
     uint32_t it2 = it1 != NONE ? wq.next(c.qhead, qs, c.qseg, xs) : NONE;
@@ -2769,20 +2530,8 @@ k3_sort_grp(Ctx c, const uint64_t* __restrict__ items,
     grp_load_vals<NW, E>(c, cur, it != NONE, wid, lane);
     grp_load_keys<NW, E, DBL>(c, cur, wid, lane);
     grp_load_vals<NW, E>(c, nxt, it1 != NONE, wid, lane);
-#if STARCH_GRP_DEEP
-    GrpIn<E> vst;                                  // group n + 2: rotations only
-    vst.item = it2 != NONE ? items[it2] : 0ull;
-    grp_load_vals<NW, E>(c, vst, it2 != NONE, wid, lane);
-    uint32_t it3 = it2 != NONE ? wq.next(c.qhead, qs, c.qseg, xs) : NONE;
-    uint64_t nitem3 = it3 != NONE ? items[it3] : 0ull;
-#else
     uint64_t nitem2 = it2 != NONE ? items[it2] : 0ull;
-#endif
-#ifdef STARCH_SORT_PROF
-    uint64_t pacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
     while (it != NONE) {
-    SPROF(t0);
     const uint64_t item = cur.item;
     const uint32_t slot = it_slot(item), s = it_start(item), m = it_size(item);
     grp_finish_keys<NW, E, DBL>(cur);
@@ -2801,13 +2550,11 @@ k3_sort_grp(Ctx c, const uint64_t* __restrict__ items,
             k[e] = ~0ull;                              // pads: max key, last in order
         }
     }
-#if STARCH_GRP_EARLY
     // the next group's key gathers go out now, so they are in flight during
     // this group's LDS-only sort phases (issued after the sort, the emit's
     // returning atomics and the queue pops waited for them at once: every
     // vmcnt wait is in issue order)
     grp_load_keys<NW, E, DBL>(c, nxt, wid, lane);
-#endif
     diff = wave_reduce_or64(diff);
     if constexpr (NW > 1) {
         if (lane == 0) red_all[wave] = diff;
@@ -2817,8 +2564,6 @@ k3_sort_grp(Ctx c, const uint64_t* __restrict__ items,
         for (int w = 0; w < NW; ++w) diff |= red_all[w0 + w];
     }
     if ((diff >> KEYB) && tg == 0) atomicOr(&c.L.ctr[C_ERR], 1u);   // top bits not shared
-    SPROF(t1);
-    SPACC(0, t0, t1);
 
     bool is_hard = false;
     const uint64_t kdiff = diff & KMASK;
@@ -2853,11 +2598,6 @@ k3_sort_grp(Ctx c, const uint64_t* __restrict__ items,
             for (int w = 0; w < NW; ++w) sq += wsq_all[w0 + w];
         }
         is_hard = sq > HARD_Q * m;                 // uniform per group
-        SPROF(t2);
-        SPACC(1, t1, t2);
-#ifdef STARCH_SORT_STATS
-        if (tg == 0) { atomicAdd(&c.L.ctr[C_STG], 1u); atomicAdd(&c.L.ctr[C_STE], m); if (is_hard) atomicAdd(&c.L.ctr[C_STH], 1u); }
-#endif
         if (!is_hard) {
 #pragma unroll
             for (int q = 0; q < BPT; ++q) { bst[tg * BPT + q] = run; bcur[tg * BPT + q] = run; run += loc[q]; }
@@ -2879,9 +2619,6 @@ k3_sort_grp(Ctx c, const uint64_t* __restrict__ items,
                     const uint32_t d = (uint32_t)((kj >> (lo + IDXB)) & (uint64_t)(NBIN - 1));
                     const uint32_t bs = bst[d], be = bst[d + 1];
                     pos[e] = bs + rank_in(xk, bs, be, kj);
-#ifdef STARCH_SORT_STATS
-                    atomicAdd(&c.L.ctr[C_STW], be - bs);
-#endif
                     k[e] = kj;
                 }
             }
@@ -2896,21 +2633,8 @@ k3_sort_grp(Ctx c, const uint64_t* __restrict__ items,
 #pragma unroll
         for (int e = 0; e < E; ++e) xk[wid * 64 * E + e * 64 + lane] = k[e];
     }
-    SPROF(t3);
-    SPACC(2, t1, t3);
-#if !STARCH_GRP_EARLY
-    // next group's keys (its rotations were loaded one or two groups ago), a new item
-    grp_load_keys<NW, E, DBL>(c, nxt, wid, lane);
-#endif
-    SPROF(t4);
-    SPACC(3, t3, t4);
-#if STARCH_GRP_DEEP
-    const uint32_t it4 = it3 != NONE ? wq.next(c.qhead, qs, c.qseg, xs) : NONE;
-    const uint64_t nitem4 = it4 != NONE ? items[it4] : 0ull;
-#else
     const uint32_t it3 = it2 != NONE ? wq.next(c.qhead, qs, c.qseg, xs) : NONE;
     const uint64_t nitem3 = it3 != NONE ? items[it3] : 0ull;
-#endif
     if (!is_hard) {
     gsync<NW>();
 #pragma unroll
@@ -2953,8 +2677,6 @@ k3_sort_grp(Ctx c, const uint64_t* __restrict__ items,
             for (int e = 0; e < E; ++e) hp[e] = hp[e] > pre ? hp[e] : pre;
         }
     }
-    SPROF(t5);
-    SPACC(4, t4, t5);
     // the group's SA range was read (values consumed above) before any write
     uint32_t runs = 0, tcnt = 0;
     uint64_t tm[E];
@@ -2983,24 +2705,7 @@ k3_sort_grp(Ctx c, const uint64_t* __restrict__ items,
         }
     }
     }
-    SPROF(t6);
-    SPACC(5, t4, t6);
     // rotate the pipeline
-#if STARCH_GRP_DEEP
-    cur = nxt;
-    nxt.item = vst.item;
-    nxt.ks = vst.ks;
-#pragma unroll
-    for (int e = 0; e < E; ++e) nxt.v[e] = vst.v[e];
-    nxt.v0 = vst.v0;
-    vst.item = nitem3;
-    nitem3 = nitem4;
-    grp_load_vals<NW, E>(c, vst, it3 != NONE, wid, lane);
-    it = it1;
-    it1 = it2;
-    it2 = it3;
-    it3 = it4;
-#else
     cur = nxt;
     nxt.item = nitem2;
     nitem2 = nitem3;
@@ -3008,15 +2713,7 @@ k3_sort_grp(Ctx c, const uint64_t* __restrict__ items,
     it = it1;
     it1 = it2;
     it2 = it3;
-#endif
-    SPROF(t7);
-    SPACC(6, t6, t7);
-    SPACC(7, t0, t7);
     }
-#ifdef STARCH_SORT_PROF
-    if (lane == 0)
-        for (int q = 0; q < 8; ++q) atomicAdd(&g_sprof[q + (E == 2 ? 0 : 8)], (unsigned long long)pacc[q]);
-#endif
     tacc = wave_reduce_add<uint32_t>(tacc);
     if (lane == 0 && tacc) atomicAdd(c.L.ctr + C_TS0 + c.tsel, tacc);
 }
@@ -3291,40 +2988,6 @@ __global__ void __launch_bounds__(256) k3_period(Ctx c)
     }
 }
 
-// round 0 (STARCH_KGATHER): every rotation's key window and last-column
-// symbol next to its SA entry, in SA order (KM0 / LS0), 4 per thread with
-// every gather issued before any is used
-__global__ void __launch_bounds__(256) k3_keys(Ctx c)
-{
-    const uint32_t slot = blockIdx.y;
-    const uint32_t n = c.blocks[c.b0 + slot].n;
-    const uint64_t so = (uint64_t)slot * c.scr.stride;
-    const KeySrc ks = key_src(c, slot, 0);
-    const uint32_t* SA = c.scr.SA + so;
-    uint64_t* KM = c.kA + so;
-    uint8_t* LS = c.lA + so;
-    constexpr uint32_t U = 4;
-    for (uint32_t i0 = blockIdx.x * 256u * U; i0 < n; i0 += gridDim.x * 256u * U) {
-        uint32_t v[U], ls[U];
-        uint64_t k[U];
-#pragma unroll
-        for (uint32_t u = 0; u < U; ++u) {
-            const uint32_t i = i0 + u * 256u + threadIdx.x;
-            v[u] = SA[i < n ? i : 0u];
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < U; ++u) k[u] = ks.key_pss(v[u], ls[u]);
-#pragma unroll
-        for (uint32_t u = 0; u < U; ++u) {
-            const uint32_t i = i0 + u * 256u + threadIdx.x;
-            if (i < n) {
-                KM[i] = k[u];
-                LS[i] = (uint8_t)ls[u];
-            }
-        }
-    }
-}
-
 }  // namespace
 
 // zero the counters whose bits are set (one launch instead of a memset each)
@@ -3335,22 +2998,6 @@ __global__ void k3_zero(uint32_t* __restrict__ ctr, uint64_t mask)
 }
 
 // Host orchestration.  A handful of host round trips per batch (list sizes).
-// STARCH_KGATHER=1: round-0 keys gathered into a position-ordered array by
-// their own pass after the top-level scatter (k3_keys: SA read and key
-// writes coalesced, the PSS gathers at the L2's random-read rate), so the
-// sorts read keys by position; STARCH_KMAT=1: the scatter writes them
-bool bwt_kgather()
-{
-    static const bool on = [] { const char* e = getenv("STARCH_KGATHER"); return e && !strcmp(e, "1"); }();
-    return on;
-}
-
-bool bwt_kmat()
-{
-    static const bool on = [] { const char* e = getenv("STARCH_KMAT"); return e && !strcmp(e, "1"); }();
-    return on || bwt_kgather();
-}
-
 bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blkbytes, uint64_t stride,
                  const BwtScratch& scr, DevBuf& meta, uint32_t* hctr, unsigned long long* stats, hipStream_t st,
                  bool wide)
@@ -3430,15 +3077,13 @@ bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blk
     c.keysrc = 0;
     c.kA = scr.K2;
     c.kB = scr.K;
-    c.lA = c.lB = nullptr;
     c.rtext = 0;
     c.qhead = nullptr;
     c.qseg = nullptr;
     c.nbins = wide ? PNB_WIDE : PNB;
     c.sdig = 0;
     HIP_CHECK(hipMemsetAsync(mw, 0, (2 * C_N + 14ull * nb + QSETS * QSET + nb_bins) * sizeof(uint32_t), st));
-    static const bool period_off = [] { const char* e = getenv("STARCH_PERIOD_CHECK"); return e && !strcmp(e, "0"); }();
-    if (!period_off) hipLaunchKernelGGL(k3_period, dim3(nb), dim3(256), 0, st, c);
+    hipLaunchKernelGGL(k3_period, dim3(nb), dim3(256), 0, st, c);
 
     static_assert(C_N <= 64, "k3_zero masks");
     auto zero = [&](uint64_t mask) { hipLaunchKernelGGL(k3_zero, dim3(1), dim3(64), 0, st, c.L.ctr, mask); };
@@ -3456,9 +3101,7 @@ bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blk
     auto read_ctr = [&]() {
         HIP_CHECK(hipMemcpyAsync(hctr, c.L.ctr, C_N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
-#ifndef STARCH_EXP_NOGATHER
         if (hctr[C_ERR]) throw StarchError(-11, "bwt3: group keys do not share 12 top bits");
-#endif
     };
     int dev = 0;
     HIP_CHECK(hipGetDevice(&dev));
@@ -3496,27 +3139,6 @@ bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blk
             if (nl == 0) break;
             if (level > 64) throw StarchError(-10, "bwt3: partition did not converge");
             const bool huge = hctr[C_LM0 + lsel] > HG_MIN;
-            static const bool ldbg = getenv("STARCH_BWT_DEBUG") != nullptr;
-            if (ldbg) {   // the L list of this level: sizes and shifts
-                std::vector<uint64_t> it(nl);
-                HIP_CHECK(hipMemcpyAsync(it.data(), c.L.l[lsel], nl * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipStreamSynchronize(st));
-                uint64_t tot = 0, big = 0, nbig = 0, mx = 0;
-                uint32_t sh[128] = {};
-                for (uint64_t v : it) {
-                    const uint64_t m = (v >> 12) & 0xFFFFFu;
-                    tot += m;
-                    mx = m > mx ? m : mx;
-                    if (m > HG_MIN) { big += m; ++nbig; }
-                    ++sh[v & 127u];
-                }
-                fprintf(stderr, "[bwt3] rtext %u mode %u level %d: L items %u elems %llu max %llu | >HG_MIN %llu items %llu elems | shifts",
-                        c.rtext, c.mode, level, nl, (unsigned long long)tot, (unsigned long long)mx,
-                        (unsigned long long)nbig, (unsigned long long)big);
-                for (int q = 0; q < 128; ++q)
-                    if (sh[q]) fprintf(stderr, " %d:%u", q, sh[q]);
-                fprintf(stderr, "\n");
-            }
             if (huge) {   // groups above HG_MIN: partitioned by the whole grid
                 zero(bit(C_HG) | bit(C_HGC));
                 const uint64_t nhm = std::min<uint64_t>(nl, HG_MAXN);   // huge groups: at most this many
@@ -3549,19 +3171,6 @@ bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blk
             if (c.keysrc) hipLaunchKernelGGL(k3_part_l<true>, dim3(ncu * STARCH_PL_WG), dim3(LT), 0, st, c, bout);
             else hipLaunchKernelGGL(k3_part_l<false>, dim3(ncu * STARCH_PL_WG), dim3(LT), 0, st, c, bout);
             HIP_CHECK(hipGetLastError());
-#ifdef STARCH_PL_PROF
-            {
-                unsigned long long h[16];
-                HIP_CHECK(hipStreamSynchronize(st));
-                HIP_CHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_plprof), sizeof(h)));
-                static const unsigned long long z[16] = {};
-                HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_plprof), z, sizeof(z)));
-                const char* nm[9] = {"zero", "pass1", "scan", "pass2", "final+classify", "groups", "elems", "big", "kernel(all wg)"};
-                fprintf(stderr, "[plprof] level %d sdig %u:", level, c.sdig);
-                for (int q = 0; q < 9; ++q) fprintf(stderr, " %s %llu", nm[q], h[q]);
-                fprintf(stderr, "\n");
-            }
-#endif
             c.sdig = 0;                  // (deeper levels: the sub-buckets' digits are gathered)
             zero(bit(C_L0 + lsel) | bit(C_LM0 + lsel));
             lsel ^= 1u;
@@ -3570,23 +3179,14 @@ bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blk
         const uint32_t n0 = hctr[C_M0];
         const uint32_t nw = hctr[C_W], ns = hctr[C_S], ns2 = hctr[C_S2], n1 = hctr[C_M1], n2 = hctr[C_M2],
                        n3 = hctr[C_M3];
-        static const bool dbg = getenv("STARCH_BWT_DEBUG") != nullptr;
-        if (dbg)
-            fprintf(stderr, "[bwt3] rtext %u mode %u: W %u S %u S2 %u M0 %u M1 %u M2 %u M3 %u | level-2 %u lsd %u (so far)\n",
-                    c.rtext, c.mode, nw, ns, ns2, n0, n1, n2, n3, hctr[C_DBG2], hctr[C_DBGL]);
         // every launch reads its own binned copy; stream order lets them share one buffer
         // grids: a multiple of 8 (static per-XCD segments), about one resident wave of workgroups
         auto g8 = [](uint32_t x) { return dim3((x + 7) / 8 * 8); };
         // static assignment needs every workgroup resident at once: one wave of
         // workgroups, sized by the kernel's occupancy
-        auto resident = [&](const void* f, int threads = 256, const char* env = nullptr) {
+        auto resident = [&](const void* f, int threads = 256) {
             int per_cu = 0;
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, f, threads, 0));
-            // experiments: fewer workgroups per CU (never more than can be resident:
-            // the static assignment would wait on workgroups that never start)
-            const char* e = env ? getenv(env) : nullptr;
-            if (e && atoi(e) > 0 && atoi(e) < per_cu) per_cu = atoi(e);
-            if (getenv("STARCH_BWT_DEBUG")) fprintf(stderr, "[bwt3] resident %s: %d per CU\n", env ? env : "-", per_cu);
             return g8((uint32_t)ncu * (uint32_t)(per_cu > 0 ? per_cu : 1));
         };
         // M classes: k3_sort_lds (MSD digit(s) + compare, LSD fallback); S: k3_sort_grp,
@@ -3594,82 +3194,50 @@ bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blk
         // Doubling rounds (keys in K/K2) run their own instantiations.
         const uint32_t* hard_n = c.L.ctr + C_H;
         auto clear_h = [&]() { zero(bit(C_H)); };
-        auto sstat = [&](const char* name) {
-#ifdef STARCH_SORT_STATS
-            HIP_CHECK(hipMemcpyAsync(hctr, c.L.ctr, C_N * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            fprintf(stderr, "[sort] r%u m%u %-8s groups %u elems %u pathA %u rankwork %u lsdpasses %u hard %u lvl2 %u lsdg %u\n",
-                    c.rtext, c.mode, name, hctr[C_STG], hctr[C_STE], hctr[C_STA], hctr[C_STW], hctr[C_STLP], hctr[C_STH],
-                    hctr[C_DBG2], hctr[C_DBGL]);
-            HIP_CHECK(hipMemsetAsync(c.L.ctr + C_DBG2, 0, 2 * sizeof(uint32_t), st));
-            HIP_CHECK(hipMemsetAsync(c.L.ctr + C_STG, 0, 6 * sizeof(uint32_t), st));
-#else
-            (void)name;
-#endif
-        };
         auto leaf = [&](auto dbl) {
             constexpr bool D = decltype(dbl)::value;
             // M2 / M3: 8 / 16 waves of 4 rotations per lane (the 4-wave, 8 / 16
             // per lane forms held 168 / 294 VGPRs: 3 / 1 waves per SIMD)
-#ifndef STARCH_M_WIDE
-#define STARCH_M_WIDE 1
-#endif
-            constexpr int M2W = STARCH_M_WIDE ? 8 : 4, M2E = STARCH_M_WIDE ? 4 : 8;
-            constexpr int M3W = STARCH_M_WIDE ? 16 : 4, M3E = STARCH_M_WIDE ? 4 : 16;
-            static const dim3 gm3 = resident(reinterpret_cast<const void*>(&k3_sort_lds<M3W, M3E, D>), 64 * M3W, "STARCH_RES_M3");
-            static const dim3 gm2 = resident(reinterpret_cast<const void*>(&k3_sort_lds<M2W, M2E, D>), 64 * M2W, "STARCH_RES_M2");
-            static const dim3 gm1 = resident(reinterpret_cast<const void*>(&k3_sort_lds<4, 4, D>), 256, "STARCH_RES_M1");
-            static const dim3 gm0 = resident(reinterpret_cast<const void*>(&k3_sort_lds<4, 2, D>), 256, "STARCH_RES_M0");
-            static const dim3 gs = resident(reinterpret_cast<const void*>(&k3_sort_grp<1, 2, D>), 256, "STARCH_RES_S");
-            static const dim3 gs2 = resident(reinterpret_cast<const void*>(&k3_sort_grp<1, 4, D>), 256, "STARCH_RES_S2");
-            static const dim3 gw = resident(reinterpret_cast<const void*>(&k3_sort_w<D>), 256, "STARCH_RES_W");
+            constexpr int M2W = 8, M2E = 4;
+            constexpr int M3W = 16, M3E = 4;
+            static const dim3 gm3 = resident(reinterpret_cast<const void*>(&k3_sort_lds<M3W, M3E, D>), 64 * M3W);
+            static const dim3 gm2 = resident(reinterpret_cast<const void*>(&k3_sort_lds<M2W, M2E, D>), 64 * M2W);
+            static const dim3 gm1 = resident(reinterpret_cast<const void*>(&k3_sort_lds<4, 4, D>), 256);
+            static const dim3 gm0 = resident(reinterpret_cast<const void*>(&k3_sort_lds<4, 2, D>), 256);
+            static const dim3 gs = resident(reinterpret_cast<const void*>(&k3_sort_grp<1, 2, D>), 256);
+            static const dim3 gs2 = resident(reinterpret_cast<const void*>(&k3_sort_grp<1, 4, D>), 256);
+            static const dim3 gw = resident(reinterpret_cast<const void*>(&k3_sort_w<D>), 256);
             if (n3) {
                 bin(c.L.m3, n3, bout);
                 hipLaunchKernelGGL((k3_sort_lds<M3W, M3E, D>), gm3, dim3(64 * M3W), 0, st, c, bout, nullptr);
-                sstat("M3");
             }
             if (n2) {
                 bin(c.L.m2, n2, bout);
                 hipLaunchKernelGGL((k3_sort_lds<M2W, M2E, D>), gm2, dim3(64 * M2W), 0, st, c, bout, nullptr);
-                sstat("M2");
             }
             if (n0) {
                 bin(c.L.m0, n0, bout);
-#ifdef STARCH_M0_1W
-                static const dim3 gm0w = resident(reinterpret_cast<const void*>(&k3_sort_grp<1, 8, D>));
-                clear_h();
-                hipLaunchKernelGGL((k3_sort_grp<1, 8, D>), gm0w, dim3(256), 0, st, c, bout, c.L.m0);
-                hipLaunchKernelGGL((k3_sort_lds<1, 8, D>), dim3(ncu / 2), dim3(256), 0, st, c, c.L.m0, hard_n);
-#else
                 hipLaunchKernelGGL((k3_sort_lds<4, 2, D>), gm0, dim3(256), 0, st, c, bout, nullptr);
-#endif
-                sstat("M0");
             }
             if (n1) {
                 bin(c.L.m1, n1, bout);
                 hipLaunchKernelGGL((k3_sort_lds<4, 4, D>), gm1, dim3(256), 0, st, c, bout, nullptr);
-                sstat("M1");
             }
             if (ns) {
                 bin(c.L.s, ns, bout);
                 clear_h();
                 hipLaunchKernelGGL((k3_sort_grp<1, 2, D>), gs, dim3(256), 0, st, c, bout, c.L.s);
-                sstat("S");
                 hipLaunchKernelGGL((k3_sort_lds<1, 2, D>), dim3(ncu / 2), dim3(256), 0, st, c, c.L.s, hard_n);
-                sstat("S-hard");
             }
             if (ns2) {
                 bin(c.L.s2, ns2, bout);
                 clear_h();
                 hipLaunchKernelGGL((k3_sort_grp<1, 4, D>), gs2, dim3(256), 0, st, c, bout, c.L.s2);
-                sstat("S2");
                 hipLaunchKernelGGL((k3_sort_lds<1, 4, D>), dim3(ncu / 2), dim3(256), 0, st, c, c.L.s2, hard_n);
-                sstat("S2-hard");
             }
             if (nw) {
                 bin(c.L.w, nw, bout);
                 hipLaunchKernelGGL(k3_sort_w<D>, gw, dim3(256), 0, st, c, bout);
-                sstat("W");
             }
         };
         if (c.keysrc) leaf(std::true_type{});
@@ -3679,16 +3247,7 @@ bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blk
     };
 
     // ---- round 0: packed prefix keys gathered from the PSS by every sort, as
-    // the text rounds do (bwt_kmat(): materialised next to SA by the scatter) ----
-    static const bool direct = [] { const char* e = getenv("STARCH_SCATTER"); return e && !strcmp(e, "direct"); }();
-    const bool kgather = bwt_kgather() && scr.KM0 && !direct;
-    if (bwt_kmat() && scr.KM0 && !direct) {   // (the direct scatter writes SA only)
-        c.keysrc = 1;
-        c.kA = scr.KM0;
-        c.kB = scr.KM1;
-        c.lA = scr.LS0;
-        c.lB = scr.LS1;
-    }
+    // the text rounds do ----
     {
         const uint32_t maxw = (uint32_t)pss_words(scr.stride);
         hipLaunchKernelGGL(k3_pss, dim3((maxw + 255) / 256, nb), dim3(256), 0, st, c);
@@ -3707,29 +3266,13 @@ bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blk
         // about one block in flight per XCD: one 1024-thread workgroup per CU,
         // a block's MAXT tiles spread over its XCD's CUs
         const dim3 gsc((ncu + 7) / 8 * 8);
-        // (k3_scatter_lds leaves the L buckets' first partition digits in LL;
-        // STARCH_SDIG=0: k3_part_l gathers them instead)
-        static const bool sdig_off = [] { const char* e = getenv("STARCH_SDIG"); return e && !strcmp(e, "0"); }();
-        c.sdig = direct || sdig_off ? 0u : 1u;
-        if (direct && wide) hipLaunchKernelGGL(k3_scatter<PNB_WIDE>, gsc, dim3(SCT), 0, st, c);
-        else if (direct) hipLaunchKernelGGL(k3_scatter<PNB>, gsc, dim3(SCT), 0, st, c);
-        else if (wide && c.lA && !kgather) hipLaunchKernelGGL((k3_scatter_lds<PNB_WIDE, true>), gsc, dim3(SCT), 0, st, c);
-        else if (wide) hipLaunchKernelGGL((k3_scatter_lds<PNB_WIDE, false>), gsc, dim3(SCT), 0, st, c);
-        else if (c.lA && !kgather) hipLaunchKernelGGL((k3_scatter_lds<PNB, true>), gsc, dim3(SCT), 0, st, c);
-        else hipLaunchKernelGGL((k3_scatter_lds<PNB, false>), gsc, dim3(SCT), 0, st, c);
-        if (kgather) {   // keys by position after the scatter (its PSS reads are the key source: keysrc 0 here)
-            Ctx ck = c;
-            ck.keysrc = 0;
-            hipLaunchKernelGGL(k3_keys, dim3(((uint32_t)(scr.stride / 1024) + 7) / 8 * 8 / 2 + 1, nb), dim3(256), 0, st, ck);
-        }
+        c.sdig = 1;                      // (k3_scatter_lds leaves the L buckets' first partition digits in LL)
+        if (wide) hipLaunchKernelGGL(k3_scatter_lds<PNB_WIDE>, gsc, dim3(SCT), 0, st, c);
+        else hipLaunchKernelGGL(k3_scatter_lds<PNB>, gsc, dim3(SCT), 0, st, c);
         HIP_CHECK(hipGetLastError());
     }
     sort_groups();
     c.sdig = 0;
-    c.keysrc = 0;                    // text rounds read the PSS at an offset
-    c.kA = scr.K2;
-    c.kB = scr.K;
-    c.lA = c.lB = nullptr;
     // ---- text rounds: extend the tied rotations' keys from the PSS ----
     uint32_t rtext = 0;
     uint64_t prev_tied = ~0ull;
@@ -3782,30 +3325,6 @@ bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blk
     }
     hipLaunchKernelGGL(k3_finish, dim3((nb + 255) / 256), dim3(256), 0, st, c, nb, stats);
     HIP_CHECK(hipGetLastError());
-#ifdef STARCH_SORT_PROF
-    {
-        unsigned long long h[16];
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_sprof), sizeof(h)));
-        static const unsigned long long zero[16] = {};
-        HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_sprof), zero, sizeof(zero)));
-        const char* nm[8] = {"keys-wait+finish", "digit+hist+scan", "digit..place", "next-keys-issue", "ties+heads",
-                             "tail(ties..emit)", "rotate+next-vals", "total"};
-        for (int e = 0; e < 2; ++e)
-            for (int q = 0; q < 8; ++q)
-                fprintf(stderr, "[sprof] E=%d %-18s %14llu (%.1f%%)\n", e ? 4 : 2, nm[q], h[8 * e + q],
-                        100.0 * (double)h[8 * e + q] / (double)(h[8 * e + 7] ? h[8 * e + 7] : 1));
-        unsigned long long h2[16];
-        HIP_CHECK(hipMemcpyFromSymbol(h2, HIP_SYMBOL(g_sprof2), sizeof(h2)));
-        HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_sprof2), zero, sizeof(zero)));
-        const char* nm2[8] = {"finish-keys+diff", "digit count+scan", "scatter+rank", "ties+heads", "emit",
-                              "rotate+next-vals", "-", "total"};
-        for (int e = 0; e < 2; ++e)
-            for (int q = 0; q < 8; ++q)
-                fprintf(stderr, "[sprof2] %s %-18s %14llu (%.1f%%)\n", e ? "M1" : "M2/M3", nm2[q], h2[8 * e + q],
-                        100.0 * (double)h2[8 * e + q] / (double)(h2[8 * e + 7] ? h2[8 * e + 7] : 1));
-    }
-#endif
     return !done;   // prefix doubling ran: some block may be periodic (flags bit 0)
 }
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env bash
 # GPU box: one probe of bench.py (BENCH_ARGS) -- its JSON line, stderr and,
 # unless NOPROF=1, the rocprofv3 kernel-trace summary of the same command.
-# ENVS: extra environment for the bench process (e.g. STARCH_BWT_DEBUG=1).
+# ENVS: extra environment for the bench process (e.g. STARCH_WIDE=0).
 # Output: gpurun_out/probe/<TAG>.{json,err,csv}
 set -o pipefail
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
