@@ -485,6 +485,47 @@ int starch_cat_host(starch_ctx* ctx, const void* const* archives, const uint64_t
 /* Of the last successful starch_cat_host on this context. */
 int starch_cat_get_stats(starch_ctx* ctx, starch_cat_stats* out);
 
+/* ---- sort-bed: BED lines into the order every other entry point expects ------
+ * Input is BED as bytes, cut into lines at '\n'; a last line without '\n' is a
+ * line, and every output line ends in '\n'.  A line is chrom TAB start TAB stop,
+ * optionally TAB rest: chrom is one or more bytes that are neither TAB nor
+ * '\n'; start and stop are 1 to 19 ASCII digits each with a value of at most
+ * 2^63-1 (leading zeros stay in the bytes and do not count in the value).  The
+ * output (starch_output_size / _copy / _device) is the same lines, byte for
+ * byte, ordered by chrom (unsigned memcmp, a proper prefix first: the order of
+ * starch_cat_host's groups), then start, then stop, both as numbers; lines
+ * equal in all three keep their input order (starch_cat_host's rule for
+ * ties; BEDOPS sort-bed orders such lines by the rest of the line instead).
+ * Any other line -- an empty one, fewer than three fields, a non-digit or no
+ * digit in a coordinate (so also the '\r' of a CRLF BED3 file), 20 or more
+ * digits or a value above 2^63-1, a line that starts with '#' or is a `track`
+ * header -- is STARCH_ERR_DATA: starch_last_error names the number (from 1) of
+ * the first such line and what is wrong with it, and there is no output.
+ * n == 0 gives an empty output.  2^32 lines or more in one call is
+ * STARCH_ERR_ARG.  An input already in order is copied (plus a final '\n' if
+ * it lacks one) and not sorted. */
+int starch_sort_host(starch_ctx* ctx, const void* bed, uint64_t n);
+int starch_sort_device(starch_ctx* ctx, const void* d_bed, uint64_t n);   /* BED bytes in HBM */
+typedef struct {
+    uint64_t input_bytes, n_lines, n_chromosomes;
+    uint64_t already_sorted;        /* 1: the input was in order */
+    uint64_t first_unsorted_line;   /* 1-based, 0: none: the first line whose key is below its predecessor's */
+    uint32_t radix_passes;          /* key bytes that differ between lines (of 20) */
+    float ms_parse, ms_rank, ms_sort, ms_gather, ms_total;
+} starch_sort_stats;
+/* Of the last successful starch_sort_* call on this context. */
+int starch_sort_get_stats(starch_ctx* ctx, starch_sort_stats* out);
+/* The order check alone (parse, chromosome ranks, one comparison pass): no
+ * output is written and the context's output is left as it was. */
+int starch_sort_check_host(starch_ctx* ctx, const void* bed, uint64_t n, uint64_t* first_unsorted_line);
+/* starch_sort_host, then starch_encode_device of the sorted bytes while they
+ * are in HBM: the archive is read as after starch_encode_host, and the sorted
+ * BED stays readable through starch_output_*. */
+int starch_sort_encode_host(starch_ctx* ctx, const void* bed, uint64_t n, const starch_options* opt);
+/* Sizes the sort's kernels switch on: lines per radix tile, and the length
+ * (with its '\n') from which an output line is copied by a whole wave. */
+int starch_sort_constants(uint32_t* tile_lines, uint32_t* wave_copy_bytes);
+
 int starch_output_size(starch_ctx* ctx, uint64_t* n);
 int starch_output_copy(starch_ctx* ctx, void* dst, uint64_t cap);
 int starch_output_device(starch_ctx* ctx, const void** d_ptr);

@@ -17,7 +17,7 @@ import os
 
 __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_archive", "plan_units", "assign_shards",
            "archive_layout", "compress_multi", "Unit", "Segment", "Comm", "gather_host", "MAGIC", "HG38", "HG38_LEN",
-           "list_archive", "cat_plan", "cat_host"]
+           "list_archive", "cat_plan", "cat_host", "sort_constants"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STARCH_AMD_LIB") or os.path.join(_HERE, "_build", "libstarch_amd.so")
@@ -119,6 +119,14 @@ class CatStats(ctypes.Structure):
                                                "lines_merged", "bytes_copied", "bytes_decoded")]
 
 
+class SortStats(ctypes.Structure):
+    """starch_sort_stats: the last sort_bed / sort_check / compress_sorted."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("input_bytes", "n_lines", "n_chromosomes", "already_sorted",
+                                               "first_unsorted_line")] + \
+               [("radix_passes", ctypes.c_uint32)] + \
+               [(n, ctypes.c_float) for n in ("ms_parse", "ms_rank", "ms_sort", "ms_gather", "ms_total")]
+
+
 class IndexEntry(ctypes.Structure):
     """starch_index_entry: one stream of an archive's index."""
     _fields_ = [("name_off", ctypes.c_uint64), ("name_len", ctypes.c_uint64), ("offset", ctypes.c_uint64),
@@ -218,6 +226,12 @@ def load():
         "starch_cat_host": ([vp, ctypes.POINTER(ctypes.c_char_p), pu64, u64, ctypes.POINTER(Options),
                              ctypes.POINTER(vp), pu64], ctypes.c_int),
         "starch_cat_get_stats": ([vp, ctypes.POINTER(CatStats)], ctypes.c_int),
+        "starch_sort_host": ([vp, ctypes.c_char_p, u64], ctypes.c_int),
+        "starch_sort_device": ([vp, vp, u64], ctypes.c_int),
+        "starch_sort_get_stats": ([vp, ctypes.POINTER(SortStats)], ctypes.c_int),
+        "starch_sort_check_host": ([vp, ctypes.c_char_p, u64, pu64], ctypes.c_int),
+        "starch_sort_encode_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(Options)], ctypes.c_int),
+        "starch_sort_constants": ([ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
         "starch_output_size": ([vp, pu64], ctypes.c_int),
         "starch_output_copy": ([vp, vp, u64], ctypes.c_int),
         "starch_output_device": ([vp, ctypes.POINTER(vp)], ctypes.c_int),
@@ -582,6 +596,42 @@ class Starch:
         _check(self._L.starch_extract_get_stats(self._h, ctypes.byref(s)), self._h)
         return {k: getattr(s, k) for k, _ in ExtractStats._fields_}
 
+    # ---- sort-bed ----
+    def sort_bed(self, bed: bytes) -> bytes:
+        """BED lines in any order -> the same lines ordered by (chromosome
+        bytes, start, stop); lines equal in all three keep their input order.
+        A malformed line is StarchError -12 naming its number."""
+        _check(self._L.starch_sort_host(self._h, bed, len(bed)), self._h)
+        return self._output()
+
+    def sort_bed_device(self, d_ptr: int, n: int) -> int:
+        """The same for BED bytes in HBM; returns the output size (output_device_ptr())."""
+        _check(self._L.starch_sort_device(self._h, ctypes.c_void_p(d_ptr), n), self._h)
+        k = ctypes.c_uint64()
+        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
+        return k.value
+
+    def sort_check(self, bed: bytes) -> int:
+        """0 if bed is sorted, else the number (from 1) of the first line that
+        sorts before its predecessor.  Writes no output."""
+        k = ctypes.c_uint64()
+        _check(self._L.starch_sort_check_host(self._h, bed, len(bed), ctypes.byref(k)), self._h)
+        return k.value
+
+    def sort_stats(self) -> dict:
+        """Of the last sort call: input_bytes / n_lines / n_chromosomes /
+        already_sorted / first_unsorted_line / radix_passes / ms_*."""
+        s = SortStats()
+        _check(self._L.starch_sort_get_stats(self._h, ctypes.byref(s)), self._h)
+        return {k: getattr(s, k) for k, _ in SortStats._fields_}
+
+    def compress_sorted(self, bed: bytes, emit_index=True) -> bytes:
+        """sort_bed, then compress from the sorted bytes while they are in HBM:
+        the archive compress(sort_bed(bed)) gives."""
+        o = self._opts(emit_index)
+        _check(self._L.starch_sort_encode_host(self._h, bed, len(bed), ctypes.byref(o)), self._h)
+        return self.archive()
+
     def cat(self, archives) -> bytes:
         """starchcat: the archives (bytes, in order) merged into one, with this
         instance's note, block_size_100k and base_counts.  A chromosome held
@@ -596,6 +646,14 @@ class Starch:
         s = CatStats()
         _check(self._L.starch_cat_get_stats(self._h, ctypes.byref(s)), self._h)
         return {k: getattr(s, k) for k, _ in CatStats._fields_}
+
+
+def sort_constants():
+    """(lines per radix tile, bytes from which an output line is copied by a
+    whole wave) of the sort's kernels; no GPU needed."""
+    a, b = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(load().starch_sort_constants(ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
 
 
 def _cat_args(archives):

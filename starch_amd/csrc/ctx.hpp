@@ -21,6 +21,7 @@
 #include "bz2.hpp"
 #include "bz2_decode.hpp"
 #include "gz.hpp"
+#include "sort_bed.hpp"
 #include "transform.hpp"
 #include "untransform.hpp"
 
@@ -205,6 +206,12 @@ struct starch_ctx {
     bool have_xstats = false;
     starch_cat_stats cstats{};       // the last starch_cat_host
     bool have_cstats = false;
+    // sort-bed (sort_bed.hip): the sorted text has a buffer of its own, so an
+    // encode that follows reads it while it fills the other buffers
+    sb::SortWorkspace sorter;
+    DevBuf sort_out;
+    starch_sort_stats sstats{};      // the last starch_sort_* call
+    bool have_sstats = false;
     std::string err;
     // last result
     bool have = false;

@@ -3124,3 +3124,104 @@ int starch_cat_get_stats(starch_ctx* c, starch_cat_stats* out)
 }
 
 }  // extern "C"
+
+// ---- sort-bed (include/starch_amd.h; kernels in sort_bed.hip) -----------------
+namespace {
+void sort_run(starch_ctx* c, const uint8_t* d, uint64_t n, bool check_only)
+{
+    c->have_sstats = false;
+    if (!check_only) c->have_out = false;
+    sb::SortResult r;
+    c->sorter.run(d, n, c->st, check_only, c->sort_out, r);
+    starch_sort_stats& s = c->sstats;
+    s = starch_sort_stats{};
+    s.input_bytes = n;
+    s.n_lines = r.n_lines;
+    s.n_chromosomes = r.n_chromosomes;
+    s.already_sorted = r.already_sorted ? 1 : 0;
+    s.first_unsorted_line = r.first_unsorted_line;
+    s.radix_passes = r.radix_passes;
+    s.ms_parse = r.ms_parse;
+    s.ms_rank = r.ms_rank;
+    s.ms_sort = r.ms_sort;
+    s.ms_gather = r.ms_gather;
+    s.ms_total = r.ms_total;
+    c->have_sstats = true;
+    if (check_only) return;
+    c->out_dev = static_cast<const uint8_t*>(c->sort_out.p);
+    c->out_bytes = r.out_bytes;
+    c->have_out = true;
+}
+const uint8_t* sort_upload(starch_ctx* c, const void* bed, uint64_t n)
+{
+    uint8_t* d = c->input.as<uint8_t>(n + 64);
+    HostRegistration reg(bed, n, 256ull << 20);
+    reg.h2d(d, bed, n, c->st);
+    HIP_CHECK(hipStreamSynchronize(c->st));
+    return d;
+}
+}  // namespace
+
+extern "C" {
+
+int starch_sort_device(starch_ctx* c, const void* d_bed, uint64_t n)
+{
+    GUARD(c)
+    if (n && !d_bed) return STARCH_ERR_ARG;
+    sort_run(c, static_cast<const uint8_t*>(d_bed), n, false);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_sort_host(starch_ctx* c, const void* bed, uint64_t n)
+{
+    GUARD(c)
+    if (n && !bed) return STARCH_ERR_ARG;
+    sort_run(c, sort_upload(c, bed, n), n, false);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_sort_check_host(starch_ctx* c, const void* bed, uint64_t n, uint64_t* first_unsorted_line)
+{
+    GUARD(c)
+    if ((n && !bed) || !first_unsorted_line) return STARCH_ERR_ARG;
+    sort_run(c, sort_upload(c, bed, n), n, true);
+    *first_unsorted_line = c->sstats.first_unsorted_line;
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_sort_encode_host(starch_ctx* c, const void* bed, uint64_t n, const starch_options* opt)
+{
+    GUARD(c)
+    if (n && !bed) return STARCH_ERR_ARG;
+    starch_options o;
+    starch_options_init(&o);
+    if (opt) o = *opt;
+    if (o.block_size_100k < 1 || o.block_size_100k > 9 ||
+        (o.compression_method != STARCH_METHOD_BZIP2 && o.compression_method != STARCH_METHOD_GZIP)) return STARCH_ERR_ARG;
+    c->have = false;
+    sort_run(c, sort_upload(c, bed, n), n, false);
+    // the sorted text is in sort_out, which no encoder stage writes
+    encode_device(c, c->out_dev, c->out_bytes, o);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_sort_get_stats(starch_ctx* c, starch_sort_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_sstats) return STARCH_ERR_STATE;
+    *out = c->sstats;
+    return STARCH_OK;
+}
+
+int starch_sort_constants(uint32_t* tile_lines, uint32_t* wave_copy_bytes)
+{
+    if (tile_lines) *tile_lines = (uint32_t)sb::kSortTile;
+    if (wave_copy_bytes) *wave_copy_bytes = sb::kWaveCopyBytes;
+    return STARCH_OK;
+}
+
+}  // extern "C"

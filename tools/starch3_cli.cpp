@@ -12,7 +12,12 @@
 // --device N, --gpus N (shard chromosomes over devices 0..N-1 in one process),
 // --devices LIST (explicit device list, e.g. 0,1 or 0,0 for virtual shards),
 // --stats, --batch-mb N (streamed batches: 256 MiB, 32 MiB from a pipe), --slurp,
-// --distributed.
+// --distributed, --sort.
+//
+// --sort: the input may be in any order; it is read to its end (a file or a
+// pipe: a sort cannot start before the last line is in), ordered on the GPU as
+// the sort-bed command orders it and encoded from the sorted bytes in HBM
+// (starch_sort_encode_host).  One device.
 //
 // --distributed: one process per GPU (e.g. `torchrun --no-python
 // --nproc-per-node 8 starch3 --distributed in.bed > out`): RANK / WORLD_SIZE /
@@ -82,6 +87,10 @@ static void usage(FILE* f)
             "  --stats               print per-stage timings to stderr\n"
             "  --batch-mb N          streamed encode: encode once N MiB are held (default 256)\n"
             "  --slurp               read the whole input, then encode it in one call\n"
+            "  --sort                sort the input first, as the sort-bed command does (lines with equal\n"
+            "                        chromosome, start and stop keep their input order); a sort cannot\n"
+            "                        stream, so the input, piped or not, is read to its end before any\n"
+            "                        of it is encoded\n"
             "  --base-counts         per-chromosome unique / non-unique base counts in the index\n"
             "  --distributed         one process per GPU (RANK/WORLD_SIZE/LOCAL_RANK/MASTER_ADDR from the env;\n"
             "                        input must be a file); rank 0 writes the archive\n"
@@ -328,7 +337,7 @@ int main(int argc, char** argv)
     g_premain_s = since_process_start();
     std::string note, input;
     int methods = 0, gzip = 0, level = 9, emit_index = 1, compat = 0, device = 0, stats = 0, slurp = 0, bases = 0;
-    int distributed = 0;
+    int distributed = 0, sort = 0;
     uint64_t batch_mb = 0;          // 0: 256 MiB, or 32 MiB for a pipe (see below)
     std::vector<int> devices;
     static struct option longs[] = {
@@ -340,6 +349,7 @@ int main(int argc, char** argv)
         {"gpus", required_argument, nullptr, 'G'},   {"devices", required_argument, nullptr, 'E'},
         {"batch-mb", required_argument, nullptr, 'M'}, {"slurp", no_argument, nullptr, 'U'},
         {"base-counts", no_argument, nullptr, 'B'}, {"distributed", no_argument, nullptr, 'P'},
+        {"sort", no_argument, nullptr, 'T'},
         {nullptr, 0, nullptr, 0}};
     opterr = 0;
     int c, li;
@@ -360,6 +370,7 @@ int main(int argc, char** argv)
             case 'U': slurp = 1; break;
             case 'B': bases = 1; break;
             case 'P': distributed = 1; break;
+            case 'T': sort = 1; slurp = 1; break;
             case 'G': {
                 devices.clear();
                 for (int i = 0, k = atoi(optarg); i < k; ++i) devices.push_back(i);
@@ -396,6 +407,10 @@ int main(int argc, char** argv)
     }
     if (level < 1 || level > 9) {
         fprintf(stderr, "Error: --level must be 1..9\n");
+        return EINVAL;
+    }
+    if (sort && (distributed || devices.size() > 1)) {
+        fprintf(stderr, "Error: --sort runs on one device (not with --gpus, --devices or --distributed)\n");
         return EINVAL;
     }
     struct stat st;
@@ -677,7 +692,8 @@ int main(int argc, char** argv)
             if (in != stdin) fclose(in);
         }
         rc = ctxs.size() > 1 ? starch_encode_multi_host(ctxs.data(), (int)ctxs.size(), data.data(), data.size(), &opt)
-                             : starch_encode_host(ctx, data.data(), data.size(), &opt);
+                             : sort ? starch_sort_encode_host(ctx, data.data(), data.size(), &opt)
+                                    : starch_encode_host(ctx, data.data(), data.size(), &opt);
         if (rc == STARCH_OK) {
             uint64_t n = 0;
             starch_archive_size(ctx, &n);
