@@ -526,6 +526,72 @@ int starch_sort_encode_host(starch_ctx* ctx, const void* bed, uint64_t n, const 
  * (with its '\n') from which an output line is copied by a whole wave. */
 int starch_sort_constants(uint32_t* tile_lines, uint32_t* wave_copy_bytes);
 
+/* ---- bedops: merge, intersect, difference, symmdiff, complement ---------------
+ * The inputs are ninputs >= 1 sorted BED inputs, numbered from 0 in argument
+ * order.  A line is what starch_sort_host accepts, and stop > start is also
+ * required; columns after the third are ignored; a last line without '\n' is a
+ * line; an empty input is valid and covers nothing.  S_k is the set of
+ * (chrom, base) pairs covered by input k: base x is covered by a line when
+ * start <= x < stop.  The result set R is
+ *   merge        the union of all S_k;
+ *   intersect    the intersection of all S_k;
+ *   difference   S_0 minus the union of S_1 .. S_{N-1};
+ *   symmdiff     the bases that lie in exactly one S_k;
+ *   complement   per chromosome, the bases outside the union that lie between
+ *                that chromosome's smallest start and its largest stop over all
+ *                inputs (nothing is known about chromosome lengths).
+ * With one input, merge, intersect, difference and symmdiff all give that input
+ * merged.  The output (starch_output_size / _copy / _device) is BED3, chrom TAB
+ * start TAB stop '\n' in plain decimal: one line for each maximal run of
+ * consecutive bases of R on a chromosome, so abutting pieces are joined
+ * ([0,10) and [10,20) become 0 20, wherever they came from); chromosomes in
+ * starch_sort_host's order, lines within one by start.  It is itself valid
+ * input for starch_encode_*, starch_sort_check_host and this call.
+ * This is a definition by sets: it is believed to match BEDOPS' bedops for
+ * these five options, but that is unverified against a BEDOPS binary.
+ * Errors leave no output; starch_last_error names the input (from 0) and the
+ * line (from 1, counted within that input; for an archive, its decoded BED
+ * lines).  In this order: a malformed line, kinds and texts as in
+ * starch_sort_host, is STARCH_ERR_DATA (the lowest (input, line)); then the
+ * lowest (input, line) that has stop <= start, or whose key (chrom, start,
+ * stop) is below the previous line of the same input, is STARCH_ERR_DATA, and
+ * the text says which (the first line of an input is never compared with the
+ * last line of the input before it); 2^31 lines or more over all inputs is
+ * STARCH_ERR_ARG (every line gives two ends, indexed with 32 bits).
+ * ninputs == 0, an unknown op or a NULL context or array is STARCH_ERR_ARG,
+ * answered before anything touches a device.
+ * An input whose first four bytes are the archive magic ca 5c ad 1a is an
+ * archive of this library: its streams are decoded and inverse-transformed on
+ * the GPU, as in starch_unstarch_host, and the BED stays in HBM; a gzip-method
+ * archive is STARCH_ERR_ARG, as in starch_extract_host. */
+#define STARCH_SETOP_MERGE 0
+#define STARCH_SETOP_INTERSECT 1
+#define STARCH_SETOP_DIFFERENCE 2
+#define STARCH_SETOP_SYMMDIFF 3
+#define STARCH_SETOP_COMPLEMENT 4
+typedef struct {
+    const void* data;   /* BED text or an archive */
+    uint64_t len;
+} starch_setop_input;
+int starch_setop_host(starch_ctx* ctx, int op, const starch_setop_input* inputs, uint64_t ninputs);
+/* BED text only, the inputs back to back in HBM: input k is
+ * d_bed[offs[k], offs[k + 1]) (offs: ninputs + 1 host values, not decreasing). */
+int starch_setop_device(starch_ctx* ctx, int op, const void* d_bed, const uint64_t* offs, uint64_t ninputs);
+typedef struct {
+    uint64_t n_inputs, input_bytes, n_lines, n_chromosomes;
+    uint64_t runs_merged;      /* intervals left after the per-input merge, over all inputs */
+    uint64_t groups;           /* distinct (chromosome, position) among their ends */
+    uint64_t lines_out, output_bytes;
+    uint64_t archives_decoded;
+    uint32_t radix_passes;
+    /* ms_decode (upload and archive decode) and ms_total are host clock, the others GPU events */
+    float ms_decode, ms_parse, ms_merge, ms_sort, ms_sweep, ms_format, ms_total;
+} starch_setop_stats;
+/* Of the last successful starch_setop_* call on this context. */
+int starch_setop_get_stats(starch_ctx* ctx, starch_setop_stats* out);
+/* Lines per tile of the segmented max-scan (where its carry crosses). */
+int starch_setop_constants(uint32_t* scan_tile_lines);
+
 int starch_output_size(starch_ctx* ctx, uint64_t* n);
 int starch_output_copy(starch_ctx* ctx, void* dst, uint64_t cap);
 int starch_output_device(starch_ctx* ctx, const void** d_ptr);

@@ -17,7 +17,7 @@ import os
 
 __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_archive", "plan_units", "assign_shards",
            "archive_layout", "compress_multi", "Unit", "Segment", "Comm", "gather_host", "MAGIC", "HG38", "HG38_LEN",
-           "list_archive", "cat_plan", "cat_host", "sort_constants"]
+           "list_archive", "cat_plan", "cat_host", "sort_constants", "setop_constants", "SETOPS"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STARCH_AMD_LIB") or os.path.join(_HERE, "_build", "libstarch_amd.so")
@@ -117,6 +117,23 @@ class CatRun(ctypes.Structure):
 class CatStats(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint64) for n in ("streams_in", "streams_copied", "groups_merged", "runs_decoded",
                                                "lines_merged", "bytes_copied", "bytes_decoded")]
+
+
+SETOPS = {"merge": 0, "intersect": 1, "difference": 2, "symmdiff": 3, "complement": 4}   # STARCH_SETOP_*
+
+
+class SetopInput(ctypes.Structure):
+    """starch_setop_input: BED text or an archive."""
+    _fields_ = [("data", ctypes.c_char_p), ("len", ctypes.c_uint64)]
+
+
+class SetopStats(ctypes.Structure):
+    """starch_setop_stats: the last setop()."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_inputs", "input_bytes", "n_lines", "n_chromosomes", "runs_merged",
+                                               "groups", "lines_out", "output_bytes", "archives_decoded")] + \
+               [("radix_passes", ctypes.c_uint32)] + \
+               [(n, ctypes.c_float) for n in ("ms_decode", "ms_parse", "ms_merge", "ms_sort", "ms_sweep", "ms_format",
+                                              "ms_total")]
 
 
 class SortStats(ctypes.Structure):
@@ -232,6 +249,10 @@ def load():
         "starch_sort_check_host": ([vp, ctypes.c_char_p, u64, pu64], ctypes.c_int),
         "starch_sort_encode_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(Options)], ctypes.c_int),
         "starch_sort_constants": ([ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+        "starch_setop_host": ([vp, ctypes.c_int, ctypes.POINTER(SetopInput), u64], ctypes.c_int),
+        "starch_setop_device": ([vp, ctypes.c_int, vp, pu64, u64], ctypes.c_int),
+        "starch_setop_get_stats": ([vp, ctypes.POINTER(SetopStats)], ctypes.c_int),
+        "starch_setop_constants": ([ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
         "starch_output_size": ([vp, pu64], ctypes.c_int),
         "starch_output_copy": ([vp, vp, u64], ctypes.c_int),
         "starch_output_device": ([vp, ctypes.POINTER(vp)], ctypes.c_int),
@@ -632,6 +653,47 @@ class Starch:
         _check(self._L.starch_sort_encode_host(self._h, bed, len(bed), ctypes.byref(o)), self._h)
         return self.archive()
 
+    # ---- bedops set operations ----
+    def setop(self, op: str, inputs) -> bytes:
+        """bedops --merge / --intersect / --difference / --symmdiff /
+        --complement over sorted inputs (a list of bytes: BED text, or an
+        archive, recognised by its magic) -> BED3, one line per maximal run of
+        result bases.  The set definitions are in include/starch_amd.h.  A
+        malformed or unsorted line is StarchError -12 naming input and line."""
+        if op not in SETOPS:
+            raise ValueError("setop: op must be one of %s" % ", ".join(SETOPS))
+        inputs = [bytes(b) for b in inputs]
+        arr = (SetopInput * max(1, len(inputs)))()
+        for k, b in enumerate(inputs):
+            arr[k].data = b
+            arr[k].len = len(b)
+        _check(self._L.starch_setop_host(self._h, SETOPS[op], arr, len(inputs)), self._h)
+        return self._output()
+
+    def setop_device(self, op: str, d_ptr: int, offs) -> int:
+        """The same for BED text in HBM, input k at d_ptr + [offs[k], offs[k+1]);
+        returns the output size (output_device_ptr())."""
+        offs = [int(o) for o in offs]
+        a = (ctypes.c_uint64 * len(offs))(*offs)
+        _check(self._L.starch_setop_device(self._h, SETOPS[op], ctypes.c_void_p(d_ptr), a, len(offs) - 1), self._h)
+        k = ctypes.c_uint64()
+        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
+        return k.value
+
+    def merge(self, *inputs) -> bytes: return self.setop("merge", inputs)
+    def intersect(self, *inputs) -> bytes: return self.setop("intersect", inputs)
+    def difference(self, *inputs) -> bytes: return self.setop("difference", inputs)
+    def symmdiff(self, *inputs) -> bytes: return self.setop("symmdiff", inputs)
+    def complement(self, *inputs) -> bytes: return self.setop("complement", inputs)
+
+    def setop_stats(self) -> dict:
+        """Of the last setop(): n_inputs / input_bytes / n_lines / n_chromosomes /
+        runs_merged / groups / lines_out / output_bytes / archives_decoded /
+        radix_passes / ms_*."""
+        s = SetopStats()
+        _check(self._L.starch_setop_get_stats(self._h, ctypes.byref(s)), self._h)
+        return {k: getattr(s, k) for k, _ in SetopStats._fields_}
+
     def cat(self, archives) -> bytes:
         """starchcat: the archives (bytes, in order) merged into one, with this
         instance's note, block_size_100k and base_counts.  A chromosome held
@@ -654,6 +716,13 @@ def sort_constants():
     a, b = ctypes.c_uint32(), ctypes.c_uint32()
     _check(load().starch_sort_constants(ctypes.byref(a), ctypes.byref(b)))
     return a.value, b.value
+
+
+def setop_constants():
+    """Lines per tile of the set operations' segmented max-scan; no GPU needed."""
+    a = ctypes.c_uint32()
+    _check(load().starch_setop_constants(ctypes.byref(a)))
+    return a.value
 
 
 def _cat_args(archives):

@@ -22,6 +22,7 @@
 #include "bz2_decode.hpp"
 #include "gz.hpp"
 #include "sort_bed.hpp"
+#include "bed_setops.hpp"
 #include "transform.hpp"
 #include "untransform.hpp"
 
@@ -212,6 +213,11 @@ struct starch_ctx {
     DevBuf sort_out;
     starch_sort_stats sstats{};      // the last starch_sort_* call
     bool have_sstats = false;
+    // bedops set operations (bed_setops.hip): the inputs back to back, and the result
+    so::SetopWorkspace setop;
+    DevBuf setop_in, setop_out;
+    starch_setop_stats ostats{};     // the last starch_setop_* call
+    bool have_ostats = false;
     std::string err;
     // last result
     bool have = false;

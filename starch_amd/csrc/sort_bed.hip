@@ -51,25 +51,6 @@ enum : uint32_t {
     B_STOP_DIGIT, B_STOP_RANGE, B_LONG
 };
 
-const char* bad_text(uint32_t k)
-{
-    switch (k) {
-        case B_EMPTY: return "empty line";
-        case B_HASH: return "'#' header line";
-        case B_TRACK: return "'track' header line";
-        case B_NOCHROM: return "empty chromosome field";
-        case B_FIELDS: return "fewer than three tab-separated fields";
-        case B_START_EMPTY: return "empty start coordinate";
-        case B_START_DIGIT: return "non-digit in the start coordinate";
-        case B_START_RANGE: return "start coordinate has 20 or more digits or is above 2^63-1";
-        case B_STOP_EMPTY: return "empty stop coordinate";
-        case B_STOP_DIGIT: return "non-digit in the stop coordinate";
-        case B_STOP_RANGE: return "stop coordinate has 20 or more digits or is above 2^63-1";
-        case B_LONG: return "line of 2^32 bytes or more";
-        default: return "malformed line";
-    }
-}
-
 struct Ent {            // one distinct chromosome name
     uint64_t off;       // its bytes in the input (the representative line's)
     uint32_t len, slot;
@@ -499,25 +480,38 @@ inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return (unsigne
 
 }  // namespace
 
+const char* bad_text(uint32_t k)
+{
+    switch (k) {
+        case B_EMPTY: return "empty line";
+        case B_HASH: return "'#' header line";
+        case B_TRACK: return "'track' header line";
+        case B_NOCHROM: return "empty chromosome field";
+        case B_FIELDS: return "fewer than three tab-separated fields";
+        case B_START_EMPTY: return "empty start coordinate";
+        case B_START_DIGIT: return "non-digit in the start coordinate";
+        case B_START_RANGE: return "start coordinate has 20 or more digits or is above 2^63-1";
+        case B_STOP_EMPTY: return "empty stop coordinate";
+        case B_STOP_DIGIT: return "non-digit in the stop coordinate";
+        case B_STOP_RANGE: return "stop coordinate has 20 or more digits or is above 2^63-1";
+        case B_LONG: return "line of 2^32 bytes or more";
+        default: return "malformed line";
+    }
+}
+
+
 SortWorkspace::~SortWorkspace()
 {
     for (auto& e : ev)
         if (e) (void)hipEventDestroy(e);
 }
 
-void SortWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, bool check_only, DevBuf& out, SortResult& res)
+uint64_t SortWorkspace::stage_parse(const uint8_t* d_bed, uint64_t n, hipStream_t st, uint64_t* bad)
 {
-    res = SortResult{};
-    if (n == 0) return;
-    for (auto& e : ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(STARCH_ERR_DEVICE, "hipEventCreate"); }
     uint64_t* scal = b_scal.as<uint64_t>(S_COUNT);
     unsigned long long* uscal = reinterpret_cast<unsigned long long*>(scal);
     HIP_CHECK(hipMemsetAsync(scal, 0, 16 * sizeof(uint64_t), st));
     HIP_CHECK(hipMemsetAsync(scal + 16, 0xff, 16 * sizeof(uint64_t), st));
-    HIP_CHECK(hipEventRecord(ev[0], st));
-
-    // 1. line index and parse
     const uint64_t ntile = ceil_div(n, kTileBytes);
     uint32_t* tile_cnt = b_tile_cnt.as<uint32_t>(ntile + 1);
     uint64_t* tile_off = b_tile_off.as<uint64_t>(ntile + 1);
@@ -531,26 +525,31 @@ void SortWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, bool c
     const bool open_end = last != '\n';
     const uint64_t L = nl + (open_end ? 1 : 0);
     if (L > 0xffffffffull) throw StarchError(STARCH_ERR_ARG, "sort-bed: more than 2^32-1 lines in one call");
-    res.n_lines = L;
-    uint64_t* line_end = b_line_end.as<uint64_t>(L + 1);
-    if (nl) hipLaunchKernelGGL(k_sb_index_nl, dim3((unsigned)ntile), dim3(kThreads), 0, st, d_bed, n, tile_off, line_end);
-    if (open_end) hipLaunchKernelGGL(k_sb_set_u64, dim3(1), dim3(1), 0, st, line_end + nl, n + 1);
-    uint64_t* start = b_start.as<uint64_t>(L);
-    uint64_t* stop = b_stop.as<uint64_t>(L);
-    uint32_t* chr_len = b_chr_len.as<uint32_t>(L);
-    const unsigned lblocks = blocks_for(L, kThreads);
-    hipLaunchKernelGGL(k_sb_parse, dim3(lblocks), dim3(kThreads), 0, st, d_bed, line_end, L, start, stop, chr_len,
-                       uscal + S_BAD);
+    ln = Lines{};
+    ln.L = L;
+    ln.open_end = open_end;
+    ln.line_end = b_line_end.as<uint64_t>(L + 1);
+    if (nl) hipLaunchKernelGGL(k_sb_index_nl, dim3((unsigned)ntile), dim3(kThreads), 0, st, d_bed, n, tile_off, ln.line_end);
+    if (open_end) hipLaunchKernelGGL(k_sb_set_u64, dim3(1), dim3(1), 0, st, ln.line_end + nl, n + 1);
+    ln.start = b_start.as<uint64_t>(L);
+    ln.stop = b_stop.as<uint64_t>(L);
+    ln.chr_len = b_chr_len.as<uint32_t>(L);
+    hipLaunchKernelGGL(k_sb_parse, dim3(blocks_for(L, kThreads)), dim3(kThreads), 0, st, d_bed, ln.line_end, L, ln.start,
+                       ln.stop, ln.chr_len, uscal + S_BAD);
     HIP_CHECK(hipGetLastError());
-    uint64_t bad = 0;
-    HIP_CHECK(hipMemcpyAsync(&bad, scal + S_BAD, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipEventRecord(ev[1], st));
+    HIP_CHECK(hipMemcpyAsync(bad, scal + S_BAD, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    if (bad != ~0ull)
-        throw StarchError(STARCH_ERR_DATA, "sort-bed: line " + std::to_string((bad >> 8) + 1) + ": " +
-                                               bad_text((uint32_t)(bad & 255)));
+    return L;
+}
 
-    // 2. chromosome ranks
+void SortWorkspace::stage_rank(const uint8_t* d_bed, hipStream_t st)
+{
+    const uint64_t L = ln.L;
+    uint64_t* scal = b_scal.as<uint64_t>(S_COUNT);
+    unsigned long long* uscal = reinterpret_cast<unsigned long long*>(scal);
+    const uint64_t* line_end = ln.line_end;
+    const uint32_t* chr_len = ln.chr_len;
+    const unsigned lblocks = blocks_for(L, kThreads);
     uint64_t* hash = b_hash.as<uint64_t>(L);
     uint32_t* rank = b_rank.as<uint32_t>(L);
     uint64_t cap_max = 1ull << 16;
@@ -582,7 +581,7 @@ void SortWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, bool c
         if (h[0] == 0) break;
         ++seed;                                 // two names under one hash: hash again
     }
-    res.n_chromosomes = names;
+    n_chromosomes = names;
     {
         Ent* ent = b_ent.as<Ent>(names);
         hipLaunchKernelGGL(k_sb_collect, dim3(blocks_for(cap, kThreads)), dim3(kThreads), 0, st, keys, rep, cap, line_end,
@@ -608,7 +607,13 @@ void SortWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, bool c
             const int c = memcmp(hn.data() + dst[a], hn.data() + dst[b], std::min(la, lb));
             return c ? c < 0 : la < lb;        // (distinct names never tie)
         });
-        for (uint64_t k = 0; k < names; ++k) rank_of[order[k]] = (uint32_t)k;
+        chrom_off.resize(names);
+        chrom_len.resize(names);
+        for (uint64_t k = 0; k < names; ++k) {
+            rank_of[order[k]] = (uint32_t)k;
+            chrom_off[k] = he[order[k]].off;
+            chrom_len[k] = he[order[k]].len;
+        }
         uint32_t* d_rank_of = b_slot_rank.as<uint32_t>(names);
         HIP_CHECK(hipMemcpyAsync(d_rank_of, rank_of.data(), names * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(k_sb_slot_ranks, dim3(blocks_for(names, kThreads)), dim3(kThreads), 0, st, ent, d_rank_of, names,
@@ -617,20 +622,97 @@ void SortWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, bool c
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(st));   // the host vectors above were copy sources
     }
-    HIP_CHECK(hipEventRecord(ev[2], st));
+    ln.rank = rank;
+}
 
-    // 3. order check
-    const unsigned cblocks = (unsigned)std::min<uint64_t>(lblocks, 2048);
+KeyBits SortWorkspace::stage_check(const uint32_t* rank, const uint64_t* start, const uint64_t* stop, uint64_t L,
+                                   hipStream_t st)
+{
+    uint64_t* scal = b_scal.as<uint64_t>(S_COUNT);
+    unsigned long long* uscal = reinterpret_cast<unsigned long long*>(scal);
+    HIP_CHECK(hipMemsetAsync(scal + S_OR_RANK, 0, 3 * sizeof(uint64_t), st));
+    HIP_CHECK(hipMemsetAsync(scal + S_DESC, 0xff, 4 * sizeof(uint64_t), st));
+    const unsigned cblocks = (unsigned)std::min<uint64_t>(blocks_for(L, kThreads), 2048);
     hipLaunchKernelGGL(k_sb_check, dim3(cblocks), dim3(kThreads), 0, st, rank, start, stop, L, uscal);
     uint64_t hs[S_COUNT];
     HIP_CHECK(hipMemcpyAsync(hs, scal, sizeof(hs), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
-    res.already_sorted = hs[S_DESC] == ~0ull;
-    res.first_unsorted_line = res.already_sorted ? 0 : hs[S_DESC] + 1;
+    KeyBits kb;
+    kb.or_rank = hs[S_OR_RANK];   kb.and_rank = hs[S_AND_RANK];
+    kb.or_start = hs[S_OR_START]; kb.and_start = hs[S_AND_START];
+    kb.or_stop = hs[S_OR_STOP];   kb.and_stop = hs[S_AND_STOP];
+    kb.desc = hs[S_DESC];
+    return kb;
+}
+
+const uint32_t* SortWorkspace::stage_radix(const uint32_t* rank, const uint64_t* start, const uint64_t* stop, uint64_t L,
+                                           const KeyBits& kb, hipStream_t st, uint32_t* passes_out)
+{
+    // one pass per key byte that is not the same in every line, least significant first
+    struct Pass { const uint64_t* k64; const uint32_t* k32; uint32_t shift; };
+    std::vector<Pass> passes;
+    if (stop)
+        for (uint32_t b = 0; b < 8; ++b)
+            if (((kb.or_stop ^ kb.and_stop) >> (8 * b)) & 255) passes.push_back(Pass{stop, nullptr, 8 * b});
+    for (uint32_t b = 0; b < 8; ++b)
+        if (((kb.or_start ^ kb.and_start) >> (8 * b)) & 255) passes.push_back(Pass{start, nullptr, 8 * b});
+    for (uint32_t b = 0; b < 4; ++b)
+        if (((kb.or_rank ^ kb.and_rank) >> (8 * b)) & 255) passes.push_back(Pass{nullptr, rank, 8 * b});
+    *passes_out = (uint32_t)passes.size();
+    if (passes.empty()) return nullptr;
+    const uint64_t ntiles = ceil_div(L, kSortTile);
+    uint32_t* idx[2] = {b_idx[0].as<uint32_t>(L), b_idx[1].as<uint32_t>(L)};
+    uint8_t* dig = b_digit.as<uint8_t>(L);
+    uint32_t* hist = b_hist.as<uint32_t>(256 * ntiles);
+    uint64_t* hist_off = b_hist_off.as<uint64_t>(256 * ntiles);
+    int cur = 0;
+    bool first = true;
+    for (const Pass& p : passes) {
+        const uint32_t* src = first ? nullptr : idx[cur];
+        hipLaunchKernelGGL(k_sb_hist, dim3((unsigned)ntiles), dim3(kSortThreads), 0, st, src, p.k64, p.k32, p.shift, L,
+                           ntiles, dig, hist);
+        scan::excl_sum_u32_to_u64(hist, hist_off, 256 * ntiles, (uint64_t*)nullptr, b_tmp, st);
+        hipLaunchKernelGGL(k_sb_scatter, dim3((unsigned)ntiles), dim3(kSortThreads), 0, st, src, dig, hist_off, L, ntiles,
+                           idx[cur ^ 1]);
+        cur ^= 1;
+        first = false;
+    }
+    HIP_CHECK(hipGetLastError());
+    return idx[cur];
+}
+
+void SortWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, bool check_only, DevBuf& out, SortResult& res)
+{
+    res = SortResult{};
+    if (n == 0) return;
+    for (auto& e : ev)
+        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(STARCH_ERR_DEVICE, "hipEventCreate"); }
+    HIP_CHECK(hipEventRecord(ev[0], st));
+
+    // 1. line index and parse
+    uint64_t bad = 0;
+    const uint64_t L = stage_parse(d_bed, n, st, &bad);
+    res.n_lines = L;
+    HIP_CHECK(hipEventRecord(ev[1], st));
+    if (bad != ~0ull)
+        throw StarchError(STARCH_ERR_DATA, "sort-bed: line " + std::to_string((bad >> 8) + 1) + ": " +
+                                               bad_text((uint32_t)(bad & 255)));
+
+    // 2. chromosome ranks
+    stage_rank(d_bed, st);
+    res.n_chromosomes = n_chromosomes;
+    HIP_CHECK(hipEventRecord(ev[2], st));
+
+    // 3. order check
+    const KeyBits kb = stage_check(ln.rank, ln.start, ln.stop, L, st);
+    res.already_sorted = kb.desc == ~0ull;
+    res.first_unsorted_line = res.already_sorted ? 0 : kb.desc + 1;
     if (check_only) {
         HIP_CHECK(hipEventRecord(ev[3], st));
         HIP_CHECK(hipEventRecord(ev[4], st));
     } else {
+        const bool open_end = ln.open_end;
+        unsigned long long* uscal = reinterpret_cast<unsigned long long*>(b_scal.as<uint64_t>(S_COUNT));
         res.out_bytes = n + (open_end ? 1 : 0);
         uint8_t* o = out.as<uint8_t>(res.out_bytes + 64);
         if (res.already_sorted) {
@@ -638,48 +720,29 @@ void SortWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, bool c
             HIP_CHECK(hipMemcpyAsync(o, d_bed, n, hipMemcpyDeviceToDevice, st));
             if (open_end) HIP_CHECK(hipMemsetAsync(o + n, '\n', 1, st));
         } else {
-            // 4. one pass per key byte that is not the same in every line, least significant first
-            struct Pass { const uint64_t* k64; const uint32_t* k32; uint32_t shift; };
-            std::vector<Pass> passes;
-            for (uint32_t b = 0; b < 8; ++b)
-                if (((hs[S_OR_STOP] ^ hs[S_AND_STOP]) >> (8 * b)) & 255) passes.push_back(Pass{stop, nullptr, 8 * b});
-            for (uint32_t b = 0; b < 8; ++b)
-                if (((hs[S_OR_START] ^ hs[S_AND_START]) >> (8 * b)) & 255) passes.push_back(Pass{start, nullptr, 8 * b});
-            for (uint32_t b = 0; b < 4; ++b)
-                if (((hs[S_OR_RANK] ^ hs[S_AND_RANK]) >> (8 * b)) & 255) passes.push_back(Pass{nullptr, rank, 8 * b});
-            res.radix_passes = (uint32_t)passes.size();
-            const uint64_t ntiles = ceil_div(L, kSortTile);
-            uint32_t* idx[2] = {b_idx[0].as<uint32_t>(L), b_idx[1].as<uint32_t>(L)};
-            uint8_t* dig = b_digit.as<uint8_t>(L);
-            uint32_t* hist = b_hist.as<uint32_t>(256 * ntiles);
-            uint64_t* hist_off = b_hist_off.as<uint64_t>(256 * ntiles);
-            int cur = 0;
-            bool first = true;
-            for (const Pass& p : passes) {
-                const uint32_t* src = first ? nullptr : idx[cur];
-                hipLaunchKernelGGL(k_sb_hist, dim3((unsigned)ntiles), dim3(kSortThreads), 0, st, src, p.k64, p.k32, p.shift,
-                                   L, ntiles, dig, hist);
-                scan::excl_sum_u32_to_u64(hist, hist_off, 256 * ntiles, (uint64_t*)nullptr, b_tmp, st);
-                hipLaunchKernelGGL(k_sb_scatter, dim3((unsigned)ntiles), dim3(kSortThreads), 0, st, src, dig, hist_off, L,
-                                   ntiles, idx[cur ^ 1]);
-                cur ^= 1;
-                first = false;
-            }
-            if (first) {   // (an unsorted input has a varying byte; kept for safety)
-                hipLaunchKernelGGL(k_sb_iota, dim3(lblocks), dim3(kThreads), 0, st, idx[0], L);
-                cur = 0;
+            // 4. radix passes
+            const unsigned lblocks = blocks_for(L, kThreads);
+            const uint32_t* order = stage_radix(ln.rank, ln.start, ln.stop, L, kb, st, &res.radix_passes);
+            uint32_t* spare = b_idx[0].as<uint32_t>(L);
+            if (!order) {   // (an unsorted input has a varying byte; kept for safety)
+                hipLaunchKernelGGL(k_sb_iota, dim3(lblocks), dim3(kThreads), 0, st, spare, L);
+                order = spare;
+                spare = b_idx[1].as<uint32_t>(L);
+            } else if (order == spare) {
+                spare = b_idx[1].as<uint32_t>(L);
             }
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipEventRecord(ev[3], st));
             // 5. gather
+            const uint64_t* line_end = ln.line_end;
             uint32_t* len = b_len.as<uint32_t>(L);
             uint64_t* out_off = b_out_off.as<uint64_t>(L);
-            hipLaunchKernelGGL(k_sb_len, dim3(lblocks), dim3(kThreads), 0, st, idx[cur], line_end, L, len);
+            hipLaunchKernelGGL(k_sb_len, dim3(lblocks), dim3(kThreads), 0, st, order, line_end, L, len);
             scan::excl_sum_u32_to_u64(len, out_off, L, (uint64_t*)nullptr, b_tmp, st);
-            hipLaunchKernelGGL(k_sb_copy, dim3(lblocks), dim3(kThreads), 0, st, d_bed, line_end, idx[cur], len, out_off, L, o,
-                               idx[cur ^ 1], uscal);
+            hipLaunchKernelGGL(k_sb_copy, dim3(lblocks), dim3(kThreads), 0, st, d_bed, line_end, order, len, out_off, L, o,
+                               spare, uscal);
             hipLaunchKernelGGL(k_sb_copy_long, dim3((unsigned)std::min<uint64_t>(lblocks, 1024)), dim3(kThreads), 0, st,
-                               d_bed, line_end, idx[cur], len, out_off, o, idx[cur ^ 1], uscal);
+                               d_bed, line_end, order, len, out_off, o, spare, uscal);
             HIP_CHECK(hipGetLastError());
         }
         HIP_CHECK(hipEventRecord(ev[4], st));

@@ -1,6 +1,7 @@
 // starch_amd/csrc/sort_bed.hpp -- host interface of the BED sort (sort_bed.hip).
 #pragma once
 #include <string>
+#include <vector>
 
 #include "common.hpp"
 
@@ -19,6 +20,16 @@ struct SortResult {
     float ms_parse = 0, ms_rank = 0, ms_sort = 0, ms_gather = 0, ms_total = 0;
 };
 
+// OR and AND of every key word over the lines (a byte whose OR equals its AND
+// is the same in every line), and the first line whose key is below its
+// predecessor's (~0: none)
+struct KeyBits {
+    uint64_t or_rank = 0, and_rank = 0, or_start = 0, and_start = 0, or_stop = 0, and_stop = 0, desc = ~0ull;
+};
+
+// what is wrong with a malformed line: the low byte of stage_parse's *bad
+const char* bad_text(uint32_t kind);
+
 struct SortWorkspace {
     DevBuf b_tile_cnt, b_tile_off, b_scal, b_tmp, b_line_end, b_start, b_stop, b_chr_len, b_hash, b_rank, b_keys, b_rep,
         b_ent, b_names, b_name_dst, b_slot_rank, b_idx[2], b_digit, b_hist, b_hist_off, b_len, b_out_off;
@@ -28,6 +39,31 @@ struct SortWorkspace {
     // (STARCH_ERR_DATA naming the first malformed line, STARCH_ERR_ARG for 2^32
     // lines or more).
     void run(const uint8_t* d_bed, uint64_t n, hipStream_t st, bool check_only, DevBuf& out, SortResult& res);
+
+    // The stages of run(), for callers that put their own work between them
+    // (bed_setops.hip).  Per-line arrays of the last stage_parse, in HBM:
+    struct Lines {
+        uint64_t L = 0;
+        bool open_end = false;                          // the last line had no '\n'
+        uint64_t *line_end = nullptr, *start = nullptr, *stop = nullptr;
+        uint32_t *chr_len = nullptr, *rank = nullptr;   // rank: after stage_rank
+    } ln;
+    uint64_t n_chromosomes = 0;                // after stage_rank
+    std::vector<uint64_t> chrom_off;           // by rank: the name's bytes in d_bed (its representative line's)
+    std::vector<uint32_t> chrom_len;
+    // 1. line ends and parse of d_bed[0, n), n > 0.  Returns the number of
+    // lines; *bad is ~0, or (line << 8) | kind of the first malformed line.
+    uint64_t stage_parse(const uint8_t* d_bed, uint64_t n, hipStream_t st, uint64_t* bad);
+    // 2. chromosome ranks of the parsed lines (none of them malformed)
+    void stage_rank(const uint8_t* d_bed, hipStream_t st);
+    // 3. key bits and first descent of any L keys (stop may equal start's array)
+    KeyBits stage_check(const uint32_t* rank, const uint64_t* start, const uint64_t* stop, uint64_t L, hipStream_t st);
+    // 4. stable radix order of L < 2^32 keys (rank, start, stop), skipping the
+    // bytes kb says are constant; stop == nullptr: (rank, start) alone.  Returns
+    // the permutation (position -> key index), or nullptr when no byte varies
+    // and the order is the input's.
+    const uint32_t* stage_radix(const uint32_t* rank, const uint64_t* start, const uint64_t* stop, uint64_t L,
+                                const KeyBits& kb, hipStream_t st, uint32_t* passes);
     ~SortWorkspace();
 };
 

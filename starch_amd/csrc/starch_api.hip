@@ -2523,6 +2523,34 @@ std::vector<std::pair<std::string, ChrQuery>> normalise_regions(const starch_reg
     return q;
 }
 
+// The whole archive a[0, n) decoded and inverse-transformed into c->ut_out;
+// returns the BED bytes.  refuse_gzip: the caller's name for the error that a
+// gzip-method archive gets (nullptr: the decoder decides).
+uint64_t unstarch_to_ut_out(starch_ctx* c, const uint8_t* a, uint64_t n, const char* refuse_gzip)
+{
+    uint64_t index_off = 0;
+    ArchiveInfo info;
+    const std::vector<IndexEntry> idx = read_index(a, n, &index_off, &info);
+    if (refuse_gzip && info.format == "gzip")
+        throw StarchError(STARCH_ERR_ARG,
+                          std::string(refuse_gzip) + ": gzip archives are not decoded (compressionFormat \"gzip\")");
+    // the streams region [4, index_off) is the concatenated bzip2 streams, in index order
+    const uint64_t m = index_off - 4;
+    uint8_t* d = c->dec_in.as<uint8_t>(m + 256);
+    if (m) HIP_CHECK(hipMemcpyAsync(d, a + 4, m, hipMemcpyHostToDevice, c->st));
+    HIP_CHECK(hipMemsetAsync(d + m, 0, 256, c->st));
+    const uint64_t tbytes = c->dec.decode(d, m, a + 4, c->st, c->dec_out, c->dstreams);
+    if (c->dstreams.size() != idx.size()) throw StarchError(STARCH_ERR_DATA, "archive: index and streams disagree");
+    std::vector<ut::Untransform::Seg> segs;
+    for (size_t k = 0; k < idx.size(); ++k) {
+        const bz::DecStream& s = c->dstreams[k];
+        if (s.in_beg + 4 != idx[k].offset || s.in_end - s.in_beg != idx[k].size)
+            throw StarchError(STARCH_ERR_DATA, "archive: stream " + std::to_string(k) + " is not where the index says");
+        segs.push_back(ut::Untransform::Seg{s.out_off, s.out_len, idx[k].chr});
+    }
+    return c->untf.run(c->tf, static_cast<const uint8_t*>(c->dec_out.p), tbytes, segs, c->st, c->ut_out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2598,24 +2626,7 @@ int starch_unstarch_host(starch_ctx* c, const void* archive, uint64_t n)
     GUARD(c)
     if (!archive) return STARCH_ERR_ARG;
     c->have_out = false;
-    const uint8_t* a = static_cast<const uint8_t*>(archive);
-    uint64_t index_off = 0;
-    const std::vector<IndexEntry> idx = read_index(a, n, &index_off);
-    // the streams region [4, index_off) is the concatenated bzip2 streams, in index order
-    const uint64_t m = index_off - 4;
-    uint8_t* d = c->dec_in.as<uint8_t>(m + 256);
-    if (m) HIP_CHECK(hipMemcpyAsync(d, a + 4, m, hipMemcpyHostToDevice, c->st));
-    HIP_CHECK(hipMemsetAsync(d + m, 0, 256, c->st));
-    const uint64_t tbytes = c->dec.decode(d, m, a + 4, c->st, c->dec_out, c->dstreams);
-    if (c->dstreams.size() != idx.size()) throw StarchError(STARCH_ERR_DATA, "archive: index and streams disagree");
-    std::vector<ut::Untransform::Seg> segs;
-    for (size_t k = 0; k < idx.size(); ++k) {
-        const bz::DecStream& s = c->dstreams[k];
-        if (s.in_beg + 4 != idx[k].offset || s.in_end - s.in_beg != idx[k].size)
-            throw StarchError(STARCH_ERR_DATA, "archive: stream " + std::to_string(k) + " is not where the index says");
-        segs.push_back(ut::Untransform::Seg{s.out_off, s.out_len, idx[k].chr});
-    }
-    c->out_bytes = c->untf.run(c->tf, static_cast<const uint8_t*>(c->dec_out.p), tbytes, segs, c->st, c->ut_out);
+    c->out_bytes = unstarch_to_ut_out(c, static_cast<const uint8_t*>(archive), n, nullptr);
     c->out_dev = static_cast<const uint8_t*>(c->ut_out.p);
     c->have_out = true;
     return STARCH_OK;
@@ -3221,6 +3232,160 @@ int starch_sort_constants(uint32_t* tile_lines, uint32_t* wave_copy_bytes)
 {
     if (tile_lines) *tile_lines = (uint32_t)sb::kSortTile;
     if (wave_copy_bytes) *wave_copy_bytes = sb::kWaveCopyBytes;
+    return STARCH_OK;
+}
+
+}  // extern "C"
+
+// ---- bedops set operations (include/starch_amd.h; kernels in bed_setops.hip) ----
+namespace {
+// c->setop_in with room for `want` bytes, its first `used` bytes kept
+uint8_t* setop_reserve(starch_ctx* c, uint64_t used, uint64_t want)
+{
+    DevBuf& b = c->setop_in;
+    if (b.p && want <= b.cap) return static_cast<uint8_t*>(b.p);
+    DevBuf nb;
+    (void)nb.get(std::max<uint64_t>(want, 2 * (uint64_t)b.cap));
+    if (used) {
+        HIP_CHECK(hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, c->st));
+        HIP_CHECK(hipStreamSynchronize(c->st));
+    }
+    std::swap(b.p, nb.p);
+    std::swap(b.cap, nb.cap);
+    return static_cast<uint8_t*>(b.p);
+}
+
+void setop_run(starch_ctx* c, int op, uint64_t len, const std::vector<uint64_t>& in_end, uint64_t archives, double ms_decode,
+               const std::chrono::steady_clock::time_point& t0)
+{
+    so::SetopResult r;
+    c->setop.run(c->sorter, op, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, c->st, c->setop_out, r);
+    starch_setop_stats& s = c->ostats;
+    s = starch_setop_stats{};
+    s.n_inputs = in_end.size();
+    s.input_bytes = len;
+    s.n_lines = r.n_lines;
+    s.n_chromosomes = r.n_chromosomes;
+    s.runs_merged = r.runs_merged;
+    s.groups = r.groups;
+    s.lines_out = r.lines_out;
+    s.output_bytes = r.out_bytes;
+    s.archives_decoded = archives;
+    s.radix_passes = r.radix_passes;
+    s.ms_decode = (float)ms_decode;
+    s.ms_parse = r.ms_parse;
+    s.ms_merge = r.ms_merge;
+    s.ms_sort = r.ms_sort;
+    s.ms_sweep = r.ms_sweep;
+    s.ms_format = r.ms_format;
+    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->have_ostats = true;
+    c->out_dev = static_cast<const uint8_t*>(c->setop_out.p);
+    c->out_bytes = r.out_bytes;
+    c->have_out = true;
+}
+
+bool setop_args_ok(int op, const void* inputs, uint64_t ninputs)
+{
+    return op >= STARCH_SETOP_MERGE && op <= STARCH_SETOP_COMPLEMENT && inputs && ninputs;
+}
+}  // namespace
+
+extern "C" {
+
+int starch_setop_host(starch_ctx* c, int op, const starch_setop_input* inputs, uint64_t ninputs)
+{
+    if (!c || !setop_args_ok(op, inputs, ninputs)) return STARCH_ERR_ARG;
+    for (uint64_t k = 0; k < ninputs; ++k)
+        if (inputs[k].len && !inputs[k].data) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_ostats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    uint64_t want = 64;
+    for (uint64_t k = 0; k < ninputs; ++k) want += inputs[k].len + 1;
+    uint8_t* d = setop_reserve(c, 0, want);
+    uint64_t len = 0, archives = 0;
+    std::vector<uint64_t> in_end;
+    for (uint64_t k = 0; k < ninputs; ++k) {
+        const uint8_t* a = static_cast<const uint8_t*>(inputs[k].data);
+        const uint64_t n = inputs[k].len;
+        uint64_t m = n;
+        uint8_t last = '\n';
+        if (n >= 4 && memcmp(a, archive::kMagic, 4) == 0) {
+            ++archives;
+            m = unstarch_to_ut_out(c, a, n, "bedops");
+            want += m;
+            d = setop_reserve(c, len, want);
+            if (m) {
+                HIP_CHECK(hipMemcpyAsync(d + len, c->ut_out.p, m, hipMemcpyDeviceToDevice, c->st));
+                HIP_CHECK(hipMemcpyAsync(&last, static_cast<const uint8_t*>(c->ut_out.p) + (m - 1), 1, hipMemcpyDeviceToHost,
+                                         c->st));
+                HIP_CHECK(hipStreamSynchronize(c->st));
+            }
+        } else if (n) {
+            HIP_CHECK(hipMemcpyAsync(d + len, a, n, hipMemcpyHostToDevice, c->st));
+            last = a[n - 1];
+        }
+        len += m;
+        if (m && last != '\n') {
+            HIP_CHECK(hipMemsetAsync(d + len, '\n', 1, c->st));
+            ++len;
+        }
+        in_end.push_back(len);
+    }
+    HIP_CHECK(hipStreamSynchronize(c->st));
+    const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    setop_run(c, op, len, in_end, archives, ms_decode, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_setop_device(starch_ctx* c, int op, const void* d_bed, const uint64_t* offs, uint64_t ninputs)
+{
+    if (!c || !setop_args_ok(op, offs, ninputs)) return STARCH_ERR_ARG;
+    for (uint64_t k = 0; k < ninputs; ++k)
+        if (offs[k + 1] < offs[k]) return STARCH_ERR_ARG;
+    if (offs[ninputs] > offs[0] && !d_bed) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_ostats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint8_t* src = static_cast<const uint8_t*>(d_bed);
+    uint8_t* d = setop_reserve(c, 0, offs[ninputs] - offs[0] + ninputs + 64);
+    std::vector<uint8_t> last(ninputs, (uint8_t)'\n');
+    for (uint64_t k = 0; k < ninputs; ++k)
+        if (offs[k + 1] > offs[k])
+            HIP_CHECK(hipMemcpyAsync(&last[k], src + offs[k + 1] - 1, 1, hipMemcpyDeviceToHost, c->st));
+    HIP_CHECK(hipStreamSynchronize(c->st));
+    uint64_t len = 0;
+    std::vector<uint64_t> in_end;
+    for (uint64_t k = 0; k < ninputs; ++k) {
+        const uint64_t m = offs[k + 1] - offs[k];
+        if (m) HIP_CHECK(hipMemcpyAsync(d + len, src + offs[k], m, hipMemcpyDeviceToDevice, c->st));
+        len += m;
+        if (m && last[k] != '\n') {
+            HIP_CHECK(hipMemsetAsync(d + len, '\n', 1, c->st));
+            ++len;
+        }
+        in_end.push_back(len);
+    }
+    setop_run(c, op, len, in_end, 0, 0.0, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_setop_get_stats(starch_ctx* c, starch_setop_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_ostats) return STARCH_ERR_STATE;
+    *out = c->ostats;
+    return STARCH_OK;
+}
+
+int starch_setop_constants(uint32_t* scan_tile_lines)
+{
+    if (scan_tile_lines) *scan_tile_lines = (uint32_t)so::kScanTile;
     return STARCH_OK;
 }
 
