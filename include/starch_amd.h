@@ -592,6 +592,82 @@ int starch_setop_get_stats(starch_ctx* ctx, starch_setop_stats* out);
 /* Lines per tile of the segmented max-scan (where its carry crosses). */
 int starch_setop_constants(uint32_t* scan_tile_lines);
 
+/* ---- bedmap: count and bases of map elements over reference intervals ----------
+ * Two sorted BED inputs: the reference is input 0, the map input 1; with no map
+ * the reference is mapped onto itself.  A line is what starch_setop_host
+ * accepts: stop > start is required, and each input must be in
+ * starch_sort_host's order; a last line without '\n' is a line; an empty input
+ * is valid.  Either input may be a bzip2-method archive, recognised by its
+ * magic and decoded on the GPU (a gzip-method archive is STARCH_ERR_ARG).
+ * For a reference line (c, s, e) and range r the window is [s', e') =
+ * [max(0, s - r), e + r) on c (e + r stops at 2^64-1).  A map line (c, a, b)
+ * overlaps it when a < e' and b > s': BEDOPS' default of 1 bp of overlap.  The
+ * columns:
+ *   ECHO           the reference line's bytes, every column, without its '\n';
+ *   COUNT          the number of overlapping map lines;
+ *   BASES          the sum over the overlapping map lines of
+ *                  min(b, e') - max(a, s');
+ *   BASES_UNIQ     the number of bases of the window that at least one map line
+ *                  covers;
+ *   INDICATOR      1 if COUNT > 0, else 0;
+ *   ECHO_REF_SIZE  e - s (without the range).
+ * The output (starch_output_size / _copy / _device) is one line per reference
+ * line, in reference order: the chosen columns (1 to 8 of them) in the order
+ * given, joined by delim (1 to 8 bytes; bedmap's default is "|"), then '\n'.
+ * Numbers are plain decimal.  With skip_unmapped, lines whose COUNT is 0 are
+ * left out.  A reference line on a chromosome the map lacks gets zeros; map
+ * lines on chromosomes the reference lacks are ignored.
+ * All arithmetic is unsigned 64-bit, modulo 2^64 (the sums of map coordinates
+ * that BASES is taken from wrap freely): the results are exact whenever the
+ * true value fits in 64 bits, so coordinates up to 2^63-1 work.
+ * This is believed to match BEDOPS' bedmap for --echo, --count, --bases,
+ * --bases-uniq, --indicator, --echo-ref-size, --range, --delim and
+ * --skip-unmapped, but that is unverified against a BEDOPS binary.
+ * Errors leave no output and have the kinds, order and naming of
+ * starch_setop_host: input number from 0, line number from 1; first the lowest
+ * malformed (input, line), then the lowest with stop <= start or below its
+ * predecessor, both STARCH_ERR_DATA.  2^32 lines or more over reference and map
+ * (the reference twice when it is its own map) is STARCH_ERR_ARG.  A repeated
+ * column, no columns or more than 8, an unknown code, an empty or over-long
+ * delimiter and a NULL context, reference or options are STARCH_ERR_ARG,
+ * answered before anything touches a device. */
+#define STARCH_MAP_ECHO 0
+#define STARCH_MAP_COUNT 1
+#define STARCH_MAP_BASES 2
+#define STARCH_MAP_BASES_UNIQ 3
+#define STARCH_MAP_INDICATOR 4
+#define STARCH_MAP_ECHO_REF_SIZE 5
+typedef struct {
+    uint32_t ncols;          /* 1 to 8 */
+    uint8_t cols[8];         /* STARCH_MAP_*, none twice */
+    uint64_t range;
+    uint32_t skip_unmapped;
+    uint32_t delim_len;      /* 1 to 8 */
+    char delim[8];
+} starch_map_options;
+/* map_or_null == NULL: the reference is its own map. */
+int starch_map_host(starch_ctx* ctx, const starch_setop_input* ref, const starch_setop_input* map_or_null,
+                    const starch_map_options* opt);
+/* BED text only, back to back in HBM: the reference is d_bed[offs[0], offs[1]),
+ * the map d_bed[offs[1], offs[2]); ninputs is 1 (no map) or 2. */
+int starch_map_device(starch_ctx* ctx, const void* d_bed, const uint64_t* offs, uint64_t ninputs,
+                      const starch_map_options* opt);
+typedef struct {
+    uint64_t n_ref, n_map;     /* lines; n_map == n_ref when there is no map */
+    uint64_t n_chromosomes;    /* over both inputs */
+    uint64_t map_runs_merged;  /* disjoint runs of the map (0 unless BASES_UNIQ is asked for) */
+    uint64_t stops_sorted;     /* 1: a map line is nested in another, so the stops were sorted */
+    uint64_t lines_out, output_bytes;
+    /* ms_decode (upload and archive decode) and ms_total are host clock, the others GPU events */
+    float ms_decode, ms_parse, ms_build, ms_query, ms_format, ms_total;
+} starch_map_stats;
+/* Of the last successful starch_map_* call on this context. */
+int starch_map_get_stats(starch_ctx* ctx, starch_map_stats* out);
+/* Sizes the kernels switch on: reference lines per query workgroup (a window
+ * into the map arrays is found once per workgroup and chromosome), and the
+ * largest window, in elements, that is staged in LDS (0: there is no such path). */
+int starch_map_constants(uint32_t* tile_refs, uint32_t* lds_window);
+
 int starch_output_size(starch_ctx* ctx, uint64_t* n);
 int starch_output_copy(starch_ctx* ctx, void* dst, uint64_t cap);
 int starch_output_device(starch_ctx* ctx, const void** d_ptr);

@@ -17,7 +17,8 @@ import os
 
 __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_archive", "plan_units", "assign_shards",
            "archive_layout", "compress_multi", "Unit", "Segment", "Comm", "gather_host", "MAGIC", "HG38", "HG38_LEN",
-           "list_archive", "cat_plan", "cat_host", "sort_constants", "setop_constants", "SETOPS"]
+           "list_archive", "cat_plan", "cat_host", "sort_constants", "setop_constants", "SETOPS",
+           "map_constants", "MAPCOLS"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STARCH_AMD_LIB") or os.path.join(_HERE, "_build", "libstarch_amd.so")
@@ -134,6 +135,22 @@ class SetopStats(ctypes.Structure):
                [("radix_passes", ctypes.c_uint32)] + \
                [(n, ctypes.c_float) for n in ("ms_decode", "ms_parse", "ms_merge", "ms_sort", "ms_sweep", "ms_format",
                                               "ms_total")]
+
+
+MAPCOLS = {"echo": 0, "count": 1, "bases": 2, "bases_uniq": 3, "indicator": 4, "echo_ref_size": 5}   # STARCH_MAP_*
+
+
+class MapOptions(ctypes.Structure):
+    """starch_map_options: the columns, range, skip_unmapped and delimiter of bedmap()."""
+    _fields_ = [("ncols", ctypes.c_uint32), ("cols", ctypes.c_uint8 * 8), ("range", ctypes.c_uint64),
+                ("skip_unmapped", ctypes.c_uint32), ("delim_len", ctypes.c_uint32), ("delim", ctypes.c_char * 8)]
+
+
+class MapStats(ctypes.Structure):
+    """starch_map_stats: the last bedmap()."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_ref", "n_map", "n_chromosomes", "map_runs_merged", "stops_sorted",
+                                               "lines_out", "output_bytes")] + \
+               [(n, ctypes.c_float) for n in ("ms_decode", "ms_parse", "ms_build", "ms_query", "ms_format", "ms_total")]
 
 
 class SortStats(ctypes.Structure):
@@ -253,6 +270,11 @@ def load():
         "starch_setop_device": ([vp, ctypes.c_int, vp, pu64, u64], ctypes.c_int),
         "starch_setop_get_stats": ([vp, ctypes.POINTER(SetopStats)], ctypes.c_int),
         "starch_setop_constants": ([ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+        "starch_map_host": ([vp, ctypes.POINTER(SetopInput), ctypes.POINTER(SetopInput), ctypes.POINTER(MapOptions)],
+                            ctypes.c_int),
+        "starch_map_device": ([vp, vp, pu64, u64, ctypes.POINTER(MapOptions)], ctypes.c_int),
+        "starch_map_get_stats": ([vp, ctypes.POINTER(MapStats)], ctypes.c_int),
+        "starch_map_constants": ([ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
         "starch_output_size": ([vp, pu64], ctypes.c_int),
         "starch_output_copy": ([vp, vp, u64], ctypes.c_int),
         "starch_output_device": ([vp, ctypes.POINTER(vp)], ctypes.c_int),
@@ -694,6 +716,41 @@ class Starch:
         _check(self._L.starch_setop_get_stats(self._h, ctypes.byref(s)), self._h)
         return {k: getattr(s, k) for k, _ in SetopStats._fields_}
 
+    # ---- bedmap ----
+    def bedmap(self, ref, map=None, cols=("echo", "count"), range=0, skip_unmapped=False, delim=b"|") -> bytes:
+        """bedmap: one line per line of the sorted reference ``ref`` with the
+        columns ``cols`` (names of MAPCOLS, in this order, none twice) joined
+        by ``delim``: the reference line, and the count, bases, distinct bases
+        and indicator of the lines of the sorted ``map`` (None: ``ref``
+        itself) that overlap it after padding it by ``range`` bases.  Either
+        input is BED text or an archive.  The definitions are in
+        include/starch_amd.h.  A malformed or unsorted line is StarchError -12
+        naming input (ref 0, map 1) and line; a bad argument is -2."""
+        o = _map_options(cols, range, skip_unmapped, delim)
+        r = SetopInput(bytes(ref), len(ref))
+        m = None if map is None else ctypes.byref(SetopInput(bytes(map), len(map)))
+        _check(self._L.starch_map_host(self._h, ctypes.byref(r), m, ctypes.byref(o)), self._h)
+        return self._output()
+
+    def bedmap_device(self, d_ptr: int, offs, cols=("echo", "count"), range=0, skip_unmapped=False, delim=b"|") -> int:
+        """The same for BED text in HBM: the reference at d_ptr + [offs[0],
+        offs[1]), the map (if offs has a third entry) at d_ptr + [offs[1],
+        offs[2]); returns the output size (output_device_ptr())."""
+        o = _map_options(cols, range, skip_unmapped, delim)
+        offs = [int(x) for x in offs]
+        a = (ctypes.c_uint64 * len(offs))(*offs)
+        _check(self._L.starch_map_device(self._h, ctypes.c_void_p(d_ptr), a, len(offs) - 1, ctypes.byref(o)), self._h)
+        k = ctypes.c_uint64()
+        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
+        return k.value
+
+    def map_stats(self) -> dict:
+        """Of the last bedmap(): n_ref / n_map / n_chromosomes / map_runs_merged /
+        stops_sorted / lines_out / output_bytes / ms_*."""
+        s = MapStats()
+        _check(self._L.starch_map_get_stats(self._h, ctypes.byref(s)), self._h)
+        return {k: getattr(s, k) for k, _ in MapStats._fields_}
+
     def cat(self, archives) -> bytes:
         """starchcat: the archives (bytes, in order) merged into one, with this
         instance's note, block_size_100k and base_counts.  A chromosome held
@@ -723,6 +780,33 @@ def setop_constants():
     a = ctypes.c_uint32()
     _check(load().starch_setop_constants(ctypes.byref(a)))
     return a.value
+
+
+def map_constants():
+    """(reference lines per query workgroup, largest map window in elements
+    that is staged in LDS, 0 when there is no such path) of bedmap's query
+    kernel; no GPU needed."""
+    a, b = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(load().starch_map_constants(ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def _map_options(cols, range_, skip_unmapped, delim):
+    """starch_map_options; unknown names are ValueError, everything else is left to the library."""
+    cols = list(cols)
+    for c in cols:
+        if c not in MAPCOLS:
+            raise ValueError("bedmap: a column must be one of %s" % ", ".join(MAPCOLS))
+    delim = bytes(delim)
+    o = MapOptions()
+    o.ncols = len(cols)
+    for k, c in enumerate(cols[:8]):
+        o.cols[k] = MAPCOLS[c]
+    o.range = int(range_)
+    o.skip_unmapped = 1 if skip_unmapped else 0
+    o.delim_len = len(delim)
+    ctypes.memmove(ctypes.addressof(o) + MapOptions.delim.offset, delim, min(len(delim), 8))
+    return o
 
 
 def _cat_args(archives):

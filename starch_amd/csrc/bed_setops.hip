@@ -31,6 +31,7 @@
 
 #include "../../include/starch_amd.h"
 #include "bed_setops.hpp"
+#include "seg_max.hpp"
 
 namespace so {
 namespace {
@@ -96,47 +97,6 @@ k_so_check(const uint32_t* __restrict__ rank, const uint64_t* __restrict__ start
 }
 
 // ---- 3. segmented max-scan and the runs' ends -------------------------------------
-struct MF {          // the maximum since the last head (f: the range holds a head)
-    uint64_t m;
-    uint32_t f;
-};
-__device__ __forceinline__ MF comb(MF a, MF b) { return MF{b.f ? b.m : (a.m > b.m ? a.m : b.m), a.f | b.f}; }
-
-__device__ __forceinline__ MF wave_incl_mf(MF v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        MF o;
-        o.m = __shfl_up(v.m, d, 64);
-        o.f = __shfl_up(v.f, d, 64);
-        if (lane >= d) v = comb(o, v);
-    }
-    return v;
-}
-
-// exclusive scan over the block (all threads call it); sh_m, sh_f: blockDim.x / 64 entries
-__device__ __forceinline__ MF block_excl_mf(MF v, uint64_t* sh_m, uint32_t* sh_f, MF* total)
-{
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const MF inc = wave_incl_mf(v);
-    MF exc;
-    exc.m = __shfl_up(inc.m, 1, 64);
-    exc.f = __shfl_up(inc.f, 1, 64);
-    if (lane == 0) exc = MF{0, 0};
-    if (lane == 63) { sh_m[wid] = inc.m; sh_f[wid] = inc.f; }
-    __syncthreads();
-    MF pre{0, 0};
-    for (int w = 0; w < wid; ++w) pre = comb(pre, MF{sh_m[w], sh_f[w]});
-    if (total) {
-        MF tot = pre;
-        for (int w = wid; w < nw; ++w) tot = comb(tot, MF{sh_m[w], sh_f[w]});
-        *total = tot;
-    }
-    __syncthreads();
-    return comb(pre, exc);
-}
-
 __global__ void __launch_bounds__(kScanThreads)
 k_so_reduce(const uint64_t* __restrict__ stop, const uint8_t* __restrict__ head, uint64_t L, uint64_t* __restrict__ part_m,
             uint32_t* __restrict__ part_f)
@@ -364,6 +324,75 @@ SetopWorkspace::~SetopWorkspace()
         if (e) (void)hipEventDestroy(e);
 }
 
+uint64_t SetopWorkspace::stage_lines(sb::SortWorkspace& sorter, const char* tool, const uint8_t* d_cat, uint64_t n,
+                                     const std::vector<uint64_t>& in_end, hipStream_t st, std::vector<uint64_t>& first)
+{
+    const uint64_t N = in_end.size();
+    const std::string name(tool);
+    uint64_t* scal = b_scal.as<uint64_t>(S_COUNT);
+    unsigned long long* uscal = reinterpret_cast<unsigned long long*>(scal);
+    HIP_CHECK(hipMemsetAsync(scal, 0, S_COUNT * sizeof(uint64_t), st));
+    HIP_CHECK(hipMemsetAsync(scal + S_BAD, 0xff, sizeof(uint64_t), st));
+
+    // 1. framing, parse, first lines, ranks
+    uint64_t bad = 0;
+    const uint64_t L = sorter.stage_parse(d_cat, n, st, &bad);
+    const uint64_t* line_end = sorter.ln.line_end;
+    uint64_t* d_in_end = b_in_end.as<uint64_t>(N);
+    uint64_t* d_first = b_first.as<uint64_t>(N + 1);
+    HIP_CHECK(hipMemcpyAsync(d_in_end, in_end.data(), N * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_so_first_line, dim3(blocks_for(N, kThreads)), dim3(kThreads), 0, st, line_end, L, d_in_end, N,
+                       d_first);
+    HIP_CHECK(hipGetLastError());
+    first.assign(N + 1, 0);
+    HIP_CHECK(hipMemcpyAsync(first.data(), d_first, (N + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    // "input K, line M" of line i of the whole buffer
+    auto where = [&](uint64_t i) {
+        const uint64_t k = (uint64_t)(std::upper_bound(first.begin() + 1, first.end(), i) - (first.begin() + 1));
+        return name + ": input " + std::to_string(k) + ", line " + std::to_string(i - first[k] + 1) + ": ";
+    };
+    if (bad != ~0ull) throw StarchError(STARCH_ERR_DATA, where(bad >> 8) + sb::bad_text((uint32_t)(bad & 255)));
+    sorter.stage_rank(d_cat, st);
+
+    // 2. order check, segment heads
+    head = b_head.as<uint8_t>(L);
+    HIP_CHECK(hipMemsetAsync(head, 0, L, st));
+    hipLaunchKernelGGL(k_so_mark, dim3(blocks_for(N, kThreads)), dim3(kThreads), 0, st, d_first, N, L, head);
+    hipLaunchKernelGGL(k_so_check, dim3(blocks_for(L, kThreads)), dim3(kThreads), 0, st, sorter.ln.rank, sorter.ln.start,
+                       sorter.ln.stop, L, head, uscal + S_BAD);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(&bad, scal + S_BAD, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (bad != ~0ull)
+        throw StarchError(STARCH_ERR_DATA,
+                          where(bad >> 1) + ((bad & 1) ? "the line sorts below the line before it; sort the input with sort-bed"
+                                                       : "stop is not above start; " + name + " needs stop > start in every line of "
+                                                         "an input sorted with sort-bed"));
+    return L;
+}
+
+uint64_t SetopWorkspace::stage_merge(const uint64_t* start, const uint64_t* stop, const uint8_t* hd, uint64_t L, hipStream_t st)
+{
+    uint64_t* scal = b_scal.as<uint64_t>(S_COUNT);
+    const uint64_t nb = ceil_div(L, kScanTile);
+    uint64_t* part_m = b_part_m.as<uint64_t>(nb);
+    uint32_t* part_f = b_part_f.as<uint32_t>(nb);
+    incl = b_incl.as<uint64_t>(L);
+    open = b_open.as<uint32_t>(L);
+    pos = b_pos.as<uint64_t>(L);
+    hipLaunchKernelGGL(k_so_reduce, dim3((unsigned)nb), dim3(kScanThreads), 0, st, stop, hd, L, part_m, part_f);
+    hipLaunchKernelGGL(k_so_parts, dim3(1), dim3(1024), 0, st, part_m, part_f, nb);
+    hipLaunchKernelGGL(k_so_down, dim3((unsigned)nb), dim3(kScanThreads), 0, st, start, stop, hd, L, part_m, part_f, incl,
+                       open);
+    HIP_CHECK(hipGetLastError());
+    scan::excl_sum_u32_to_u64(open, pos, L, scal + S_RUNS, b_tmp, st);
+    uint64_t R = 0;
+    HIP_CHECK(hipMemcpyAsync(&R, scal + S_RUNS, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return R;
+}
+
 void SetopWorkspace::run(sb::SortWorkspace& sorter, int op, const uint8_t* d_cat, uint64_t n,
                          const std::vector<uint64_t>& in_end, hipStream_t st, DevBuf& out, SetopResult& res)
 {
@@ -378,71 +407,23 @@ void SetopWorkspace::run(sb::SortWorkspace& sorter, int op, const uint8_t* d_cat
         HIP_CHECK(hipStreamSynchronize(st));
         return;
     }
-    uint64_t* scal = b_scal.as<uint64_t>(S_COUNT);
-    unsigned long long* uscal = reinterpret_cast<unsigned long long*>(scal);
-    HIP_CHECK(hipMemsetAsync(scal, 0, S_COUNT * sizeof(uint64_t), st));
-    HIP_CHECK(hipMemsetAsync(scal + S_BAD, 0xff, sizeof(uint64_t), st));
 
-    // 1. framing, parse, first lines, ranks
-    uint64_t bad = 0;
-    const uint64_t L = sorter.stage_parse(d_cat, n, st, &bad);
+    // 1, 2. parse, ranks, order check, segment heads
+    std::vector<uint64_t> first;
+    const uint64_t L = stage_lines(sorter, "bedops", d_cat, n, in_end, st, first);
     res.n_lines = L;
-    const uint64_t* line_end = sorter.ln.line_end;
+    res.n_chromosomes = sorter.n_chromosomes;
+    uint64_t* scal = b_scal.as<uint64_t>(S_COUNT);
     const uint64_t* start = sorter.ln.start;
     const uint64_t* stop = sorter.ln.stop;
-    uint64_t* d_in_end = b_in_end.as<uint64_t>(N);
-    uint64_t* d_first = b_first.as<uint64_t>(N + 1);
-    HIP_CHECK(hipMemcpyAsync(d_in_end, in_end.data(), N * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_so_first_line, dim3(blocks_for(N, kThreads)), dim3(kThreads), 0, st, line_end, L, d_in_end, N,
-                       d_first);
-    HIP_CHECK(hipGetLastError());
-    std::vector<uint64_t> first(N + 1);
-    HIP_CHECK(hipMemcpyAsync(first.data(), d_first, (N + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    // "input K, line M" of line i of the whole buffer
-    auto where = [&](uint64_t i) {
-        const uint64_t k = (uint64_t)(std::upper_bound(first.begin() + 1, first.end(), i) - (first.begin() + 1));
-        return "bedops: input " + std::to_string(k) + ", line " + std::to_string(i - first[k] + 1) + ": ";
-    };
-    if (bad != ~0ull) throw StarchError(STARCH_ERR_DATA, where(bad >> 8) + sb::bad_text((uint32_t)(bad & 255)));
-    sorter.stage_rank(d_cat, st);
-    res.n_chromosomes = sorter.n_chromosomes;
     const uint32_t* rank = sorter.ln.rank;
     const unsigned lblocks = blocks_for(L, kThreads);
-
-    // 2. order check, segment heads
-    uint8_t* head = b_head.as<uint8_t>(L);
-    HIP_CHECK(hipMemsetAsync(head, 0, L, st));
-    hipLaunchKernelGGL(k_so_mark, dim3(blocks_for(N, kThreads)), dim3(kThreads), 0, st, d_first, N, L, head);
-    hipLaunchKernelGGL(k_so_check, dim3(lblocks), dim3(kThreads), 0, st, rank, start, stop, L, head, uscal + S_BAD);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(&bad, scal + S_BAD, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (bad != ~0ull)
-        throw StarchError(STARCH_ERR_DATA,
-                          where(bad >> 1) + ((bad & 1) ? "the line sorts below the line before it; sort the input with sort-bed"
-                                                       : "stop is not above start; bedops needs stop > start in every line of "
-                                                         "an input sorted with sort-bed"));
     if (L >= (1ull << 31))
         throw StarchError(STARCH_ERR_ARG, "bedops: 2^31 lines or more over all inputs (the interval ends are indexed with 32 bits)");
     HIP_CHECK(hipEventRecord(ev[1], st));
 
     // 3. per-input merge
-    const uint64_t nb = ceil_div(L, kScanTile);
-    uint64_t* part_m = b_part_m.as<uint64_t>(nb);
-    uint32_t* part_f = b_part_f.as<uint32_t>(nb);
-    uint64_t* incl = b_incl.as<uint64_t>(L);
-    uint32_t* open = b_open.as<uint32_t>(L);
-    uint64_t* pos = b_pos.as<uint64_t>(L);
-    hipLaunchKernelGGL(k_so_reduce, dim3((unsigned)nb), dim3(kScanThreads), 0, st, stop, head, L, part_m, part_f);
-    hipLaunchKernelGGL(k_so_parts, dim3(1), dim3(1024), 0, st, part_m, part_f, nb);
-    hipLaunchKernelGGL(k_so_down, dim3((unsigned)nb), dim3(kScanThreads), 0, st, start, stop, head, L, part_m, part_f, incl,
-                       open);
-    HIP_CHECK(hipGetLastError());
-    scan::excl_sum_u32_to_u64(open, pos, L, scal + S_RUNS, b_tmp, st);
-    uint64_t R = 0;
-    HIP_CHECK(hipMemcpyAsync(&R, scal + S_RUNS, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    const uint64_t R = stage_merge(start, stop, head, L, st);
     if (R == 0 || R > L) throw StarchError(STARCH_ERR_INTERNAL, "bedops: the run count is out of range");
     res.runs_merged = R;
     const uint64_t E = 2 * R;   // below 2^32

@@ -30,6 +30,22 @@ struct SetopWorkspace {
     // radix order.  Throws StarchError as include/starch_amd.h describes.
     void run(sb::SortWorkspace& sorter, int op, const uint8_t* d_cat, uint64_t n, const std::vector<uint64_t>& in_end,
              hipStream_t st, DevBuf& out, SetopResult& res);
+
+    // The first stages of run(), for bed_map.hip.
+    // 1, 2. framing, parse and ranks of d_cat[0, n), n > 0, through sorter (whose
+    // ln then holds the per-line arrays), the first line of every input
+    // (first: in_end.size() + 1 entries), stop > start and the per-input order;
+    // errors are thrown with `tool` in front.  Returns the number of lines and
+    // leaves head: bit 0 at the first line of every (input, chromosome) segment.
+    uint64_t stage_lines(sb::SortWorkspace& sorter, const char* tool, const uint8_t* d_cat, uint64_t n,
+                         const std::vector<uint64_t>& in_end, hipStream_t st, std::vector<uint64_t>& first);
+    // 3. the segments of L > 0 checked lines merged with themselves: incl (the
+    // largest stop from the segment's head to the line), open (1: the line opens
+    // a merged run) and pos (open's exclusive sum).  Returns the number of runs.
+    uint64_t stage_merge(const uint64_t* start, const uint64_t* stop, const uint8_t* hd, uint64_t L, hipStream_t st);
+    uint8_t* head = nullptr;
+    uint64_t *incl = nullptr, *pos = nullptr;
+    uint32_t* open = nullptr;
     ~SetopWorkspace();
 };
 

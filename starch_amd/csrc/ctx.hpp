@@ -23,6 +23,7 @@
 #include "gz.hpp"
 #include "sort_bed.hpp"
 #include "bed_setops.hpp"
+#include "bed_map.hpp"
 #include "transform.hpp"
 #include "untransform.hpp"
 
@@ -218,6 +219,10 @@ struct starch_ctx {
     DevBuf setop_in, setop_out;
     starch_setop_stats ostats{};     // the last starch_setop_* call
     bool have_ostats = false;
+    // bedmap (bed_map.hip): reads setop_in, writes setop_out
+    bm::MapWorkspace mapper;
+    starch_map_stats mstats{};       // the last starch_map_* call
+    bool have_mstats = false;
     std::string err;
     // last result
     bool have = false;

@@ -3285,28 +3285,15 @@ void setop_run(starch_ctx* c, int op, uint64_t len, const std::vector<uint64_t>&
     c->have_out = true;
 }
 
-bool setop_args_ok(int op, const void* inputs, uint64_t ninputs)
+// The inputs (BED text or archives, in host memory) back to back in c->setop_in,
+// each non-empty one ending in '\n'.  Returns the bytes; in_end: where each ends.
+uint64_t setop_load_host(starch_ctx* c, const starch_setop_input* inputs, uint64_t ninputs, const char* tool,
+                         std::vector<uint64_t>& in_end, uint64_t* archives_out)
 {
-    return op >= STARCH_SETOP_MERGE && op <= STARCH_SETOP_COMPLEMENT && inputs && ninputs;
-}
-}  // namespace
-
-extern "C" {
-
-int starch_setop_host(starch_ctx* c, int op, const starch_setop_input* inputs, uint64_t ninputs)
-{
-    if (!c || !setop_args_ok(op, inputs, ninputs)) return STARCH_ERR_ARG;
-    for (uint64_t k = 0; k < ninputs; ++k)
-        if (inputs[k].len && !inputs[k].data) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have_out = false;
-    c->have_ostats = false;
-    const auto t0 = std::chrono::steady_clock::now();
     uint64_t want = 64;
     for (uint64_t k = 0; k < ninputs; ++k) want += inputs[k].len + 1;
     uint8_t* d = setop_reserve(c, 0, want);
     uint64_t len = 0, archives = 0;
-    std::vector<uint64_t> in_end;
     for (uint64_t k = 0; k < ninputs; ++k) {
         const uint8_t* a = static_cast<const uint8_t*>(inputs[k].data);
         const uint64_t n = inputs[k].len;
@@ -3314,7 +3301,7 @@ int starch_setop_host(starch_ctx* c, int op, const starch_setop_input* inputs, u
         uint8_t last = '\n';
         if (n >= 4 && memcmp(a, archive::kMagic, 4) == 0) {
             ++archives;
-            m = unstarch_to_ut_out(c, a, n, "bedops");
+            m = unstarch_to_ut_out(c, a, n, tool);
             want += m;
             d = setop_reserve(c, len, want);
             if (m) {
@@ -3335,6 +3322,55 @@ int starch_setop_host(starch_ctx* c, int op, const starch_setop_input* inputs, u
         in_end.push_back(len);
     }
     HIP_CHECK(hipStreamSynchronize(c->st));
+    if (archives_out) *archives_out = archives;
+    return len;
+}
+
+// The same for BED text in HBM: input k is d_bed[offs[k], offs[k + 1]).
+uint64_t setop_load_device(starch_ctx* c, const void* d_bed, const uint64_t* offs, uint64_t ninputs,
+                           std::vector<uint64_t>& in_end)
+{
+    const uint8_t* src = static_cast<const uint8_t*>(d_bed);
+    uint8_t* d = setop_reserve(c, 0, offs[ninputs] - offs[0] + ninputs + 64);
+    std::vector<uint8_t> last(ninputs, (uint8_t)'\n');
+    for (uint64_t k = 0; k < ninputs; ++k)
+        if (offs[k + 1] > offs[k])
+            HIP_CHECK(hipMemcpyAsync(&last[k], src + offs[k + 1] - 1, 1, hipMemcpyDeviceToHost, c->st));
+    HIP_CHECK(hipStreamSynchronize(c->st));
+    uint64_t len = 0;
+    for (uint64_t k = 0; k < ninputs; ++k) {
+        const uint64_t m = offs[k + 1] - offs[k];
+        if (m) HIP_CHECK(hipMemcpyAsync(d + len, src + offs[k], m, hipMemcpyDeviceToDevice, c->st));
+        len += m;
+        if (m && last[k] != '\n') {
+            HIP_CHECK(hipMemsetAsync(d + len, '\n', 1, c->st));
+            ++len;
+        }
+        in_end.push_back(len);
+    }
+    return len;
+}
+
+bool setop_args_ok(int op, const void* inputs, uint64_t ninputs)
+{
+    return op >= STARCH_SETOP_MERGE && op <= STARCH_SETOP_COMPLEMENT && inputs && ninputs;
+}
+}  // namespace
+
+extern "C" {
+
+int starch_setop_host(starch_ctx* c, int op, const starch_setop_input* inputs, uint64_t ninputs)
+{
+    if (!c || !setop_args_ok(op, inputs, ninputs)) return STARCH_ERR_ARG;
+    for (uint64_t k = 0; k < ninputs; ++k)
+        if (inputs[k].len && !inputs[k].data) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_ostats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> in_end;
+    uint64_t archives = 0;
+    const uint64_t len = setop_load_host(c, inputs, ninputs, "bedops", in_end, &archives);
     const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     setop_run(c, op, len, in_end, archives, ms_decode, t0);
     return STARCH_OK;
@@ -3351,25 +3387,8 @@ int starch_setop_device(starch_ctx* c, int op, const void* d_bed, const uint64_t
     c->have_out = false;
     c->have_ostats = false;
     const auto t0 = std::chrono::steady_clock::now();
-    const uint8_t* src = static_cast<const uint8_t*>(d_bed);
-    uint8_t* d = setop_reserve(c, 0, offs[ninputs] - offs[0] + ninputs + 64);
-    std::vector<uint8_t> last(ninputs, (uint8_t)'\n');
-    for (uint64_t k = 0; k < ninputs; ++k)
-        if (offs[k + 1] > offs[k])
-            HIP_CHECK(hipMemcpyAsync(&last[k], src + offs[k + 1] - 1, 1, hipMemcpyDeviceToHost, c->st));
-    HIP_CHECK(hipStreamSynchronize(c->st));
-    uint64_t len = 0;
     std::vector<uint64_t> in_end;
-    for (uint64_t k = 0; k < ninputs; ++k) {
-        const uint64_t m = offs[k + 1] - offs[k];
-        if (m) HIP_CHECK(hipMemcpyAsync(d + len, src + offs[k], m, hipMemcpyDeviceToDevice, c->st));
-        len += m;
-        if (m && last[k] != '\n') {
-            HIP_CHECK(hipMemsetAsync(d + len, '\n', 1, c->st));
-            ++len;
-        }
-        in_end.push_back(len);
-    }
+    const uint64_t len = setop_load_device(c, d_bed, offs, ninputs, in_end);
     setop_run(c, op, len, in_end, 0, 0.0, t0);
     return STARCH_OK;
     END_GUARD(c)
@@ -3386,6 +3405,108 @@ int starch_setop_get_stats(starch_ctx* c, starch_setop_stats* out)
 int starch_setop_constants(uint32_t* scan_tile_lines)
 {
     if (scan_tile_lines) *scan_tile_lines = (uint32_t)so::kScanTile;
+    return STARCH_OK;
+}
+
+}  // extern "C"
+
+// ---- bedmap (include/starch_amd.h; kernels in bed_map.hip) -------------------------
+namespace {
+bool map_options_ok(const starch_map_options* o, bm::MapOptions* out)
+{
+    if (!o || o->ncols < 1 || o->ncols > 8 || o->delim_len < 1 || o->delim_len > 8) return false;
+    uint32_t seen = 0;
+    for (uint32_t k = 0; k < o->ncols; ++k) {
+        if (o->cols[k] > STARCH_MAP_ECHO_REF_SIZE || ((seen >> o->cols[k]) & 1)) return false;
+        seen |= 1u << o->cols[k];
+        out->cols[k] = o->cols[k];
+    }
+    out->ncols = o->ncols;
+    out->range = o->range;
+    out->skip_unmapped = o->skip_unmapped ? 1 : 0;
+    out->delim_len = o->delim_len;
+    memcpy(out->delim, o->delim, o->delim_len);
+    return true;
+}
+
+void map_run(starch_ctx* c, const bm::MapOptions& opt, uint64_t len, const std::vector<uint64_t>& in_end, double ms_decode,
+             const std::chrono::steady_clock::time_point& t0)
+{
+    bm::MapResult r;
+    c->mapper.run(c->sorter, c->setop, opt, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, c->st, c->setop_out, r);
+    starch_map_stats& s = c->mstats;
+    s = starch_map_stats{};
+    s.n_ref = r.n_ref;
+    s.n_map = r.n_map;
+    s.n_chromosomes = r.n_chromosomes;
+    s.map_runs_merged = r.map_runs_merged;
+    s.stops_sorted = r.stops_sorted;
+    s.lines_out = r.lines_out;
+    s.output_bytes = r.out_bytes;
+    s.ms_decode = (float)ms_decode;
+    s.ms_parse = r.ms_parse;
+    s.ms_build = r.ms_build;
+    s.ms_query = r.ms_query;
+    s.ms_format = r.ms_format;
+    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->have_mstats = true;
+    c->out_dev = static_cast<const uint8_t*>(c->setop_out.p);
+    c->out_bytes = r.out_bytes;
+    c->have_out = true;
+}
+}  // namespace
+
+extern "C" {
+
+int starch_map_host(starch_ctx* c, const starch_setop_input* ref, const starch_setop_input* map, const starch_map_options* opt)
+{
+    bm::MapOptions mo;
+    if (!c || !ref || !map_options_ok(opt, &mo)) return STARCH_ERR_ARG;
+    if ((ref->len && !ref->data) || (map && map->len && !map->data)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_mstats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<starch_setop_input> inputs{*ref};
+    if (map) inputs.push_back(*map);
+    std::vector<uint64_t> in_end;
+    const uint64_t len = setop_load_host(c, inputs.data(), inputs.size(), "bedmap", in_end, nullptr);
+    const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    map_run(c, mo, len, in_end, ms_decode, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_map_device(starch_ctx* c, const void* d_bed, const uint64_t* offs, uint64_t ninputs, const starch_map_options* opt)
+{
+    bm::MapOptions mo;
+    if (!c || !offs || ninputs < 1 || ninputs > 2 || !map_options_ok(opt, &mo)) return STARCH_ERR_ARG;
+    for (uint64_t k = 0; k < ninputs; ++k)
+        if (offs[k + 1] < offs[k]) return STARCH_ERR_ARG;
+    if (offs[ninputs] > offs[0] && !d_bed) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_mstats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> in_end;
+    const uint64_t len = setop_load_device(c, d_bed, offs, ninputs, in_end);
+    map_run(c, mo, len, in_end, 0.0, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_map_get_stats(starch_ctx* c, starch_map_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_mstats) return STARCH_ERR_STATE;
+    *out = c->mstats;
+    return STARCH_OK;
+}
+
+int starch_map_constants(uint32_t* tile_refs, uint32_t* lds_window)
+{
+    if (tile_refs) *tile_refs = (uint32_t)bm::kTileRefs;
+    if (lds_window) *lds_window = bm::kLdsWindow;
     return STARCH_OK;
 }
 
