@@ -592,6 +592,77 @@ int starch_setop_get_stats(starch_ctx* ctx, starch_setop_stats* out);
 /* Lines per tile of the segmented max-scan (where its carry crosses). */
 int starch_setop_constants(uint32_t* scan_tile_lines);
 
+/* ---- bedops: element-of, not-element-of, partition, chop, everything ------------
+ * starch_bedops_host / _device take every operation of the bedops command: ops 0
+ * to 4 behave exactly as through starch_setop_*, and five more are defined here.
+ * Inputs, line validity, errors and their order, archive inputs and the limit of
+ * 2^31 lines are those of starch_setop_host: stop > start, each input in
+ * starch_sort_host's order, error texts that name the input from 0 and the line
+ * from 1.  A last line without '\n' is a line, and wherever it is echoed it gets
+ * a '\n'.  These are definitions by sets: they are believed to match BEDOPS'
+ * bedops for --everything, --element-of, --not-element-of, --partition and
+ * --chop, but that is unverified against a BEDOPS binary.
+ *   everything   Every line of every input, all of its columns, ordered by
+ *                (chromosome bytewise, start, stop) as numbers; ties by (input
+ *                number, line number).  For valid inputs this is what
+ *                starch_sort_host gives for the inputs one after the other.
+ *   element-of, not-element-of
+ *                They take a threshold and at least two inputs (fewer is
+ *                STARCH_ERR_ARG before a device is touched).  U is the set of
+ *                maximal runs of the union of inputs 1 .. N-1; abutting runs are
+ *                joined, as merge joins them.  For a line (c, s, e) of input 0, ov
+ *                is the largest min(b, e) - max(a, s) over the runs [a, b) of U on
+ *                c, 0 if none overlaps: deliberately the largest overlap with one
+ *                run, not the total over several.  With a threshold in bases t
+ *                (t >= 1) the line is selected when ov >= t; with a threshold in
+ *                percent p (1 .. 100) when ov * 100 >= p * (e - s), exact for every
+ *                64-bit length.  element-of writes the selected lines of input 0,
+ *                whole, in input order; not-element-of writes the others.  The
+ *                commands' default threshold is 100%.
+ *   partition    All lines of all inputs together, not merged.  Per chromosome, P
+ *                is the sorted set of distinct starts and stops; for consecutive
+ *                p, q of P, BED3 `c p q` is written when at least one line covers
+ *                [p, q).  Pieces are never joined, and a piece is written once
+ *                however many lines cover it.
+ *   chop         A width w >= 1, a stagger g >= 1 and an exclude flag.  U is the
+ *                merge of all inputs.  For a run [a, b) of U and k = 0, 1, ...
+ *                while a + k*g < b, the piece [a + k*g, min(a + k*g + w, b)) is
+ *                written as BED3, in k order; with the flag, pieces shorter than w
+ *                are left out.  Nothing wraps for coordinates up to 2^63-1.  A
+ *                result of 2^32 pieces or more, or of 2^40 bytes or more, is
+ *                refused: STARCH_ERR_ARG, "result too large", answered from the
+ *                scanned counts before the pieces (or, for the bytes, the
+ *                output) are allocated.
+ * partition and chop write BED3 as the first five ops do, in starch_sort_host's
+ * order.  A threshold of 0 bases or a percent outside 1 .. 100, chop == 0, an
+ * unknown op, ninputs == 0 and a NULL pointer are STARCH_ERR_ARG, answered
+ * before anything touches a device. */
+#define STARCH_SETOP_ELEMENT_OF 5
+#define STARCH_SETOP_NOT_ELEMENT_OF 6
+#define STARCH_SETOP_PARTITION 7
+#define STARCH_SETOP_CHOP 8
+#define STARCH_SETOP_EVERYTHING 9
+typedef struct {
+    int32_t op;                      /* STARCH_SETOP_*, 0 to 9 */
+    uint64_t threshold;              /* element-of, not-element-of */
+    uint32_t threshold_is_percent;   /* threshold counts percent, not bases */
+    uint64_t chop;                   /* chop: the width w */
+    uint64_t stagger;                /* chop: g; 0 means equal to chop */
+    uint32_t exclude_short;          /* chop: leave out pieces shorter than w */
+} starch_bedops_options;             /* 48 bytes, every field naturally aligned */
+/* Fields that the op does not use are not looked at. */
+int starch_bedops_host(starch_ctx* ctx, const starch_bedops_options* opt, const starch_setop_input* inputs, uint64_t ninputs);
+int starch_bedops_device(starch_ctx* ctx, const starch_bedops_options* opt, const void* d_bed, const uint64_t* offs,
+                         uint64_t ninputs);
+/* starch_setop_get_stats reports the last call through starch_setop_* or
+ * starch_bedops_*: the fields that have a meaning for the op (runs_merged: the
+ * runs of U for element-of, not-element-of and chop; groups: partition, chop)
+ * and the rest 0. */
+/* Sizes the new kernels switch on: runs per tile of element-of's range maximum,
+ * and pieces per workgroup of chop's expansion (also the largest window of runs
+ * it stages in LDS). */
+int starch_bedops_constants(uint32_t* rmq_tile, uint32_t* expand_tile);
+
 /* ---- bedmap: count and bases of map elements over reference intervals ----------
  * Two sorted BED inputs: the reference is input 0, the map input 1; with no map
  * the reference is mapped onto itself.  A line is what starch_setop_host

@@ -18,7 +18,7 @@ import os
 __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_archive", "plan_units", "assign_shards",
            "archive_layout", "compress_multi", "Unit", "Segment", "Comm", "gather_host", "MAGIC", "HG38", "HG38_LEN",
            "list_archive", "cat_plan", "cat_host", "sort_constants", "setop_constants", "SETOPS",
-           "map_constants", "MAPCOLS"]
+           "map_constants", "MAPCOLS", "BEDOPS_OPS", "bedops_constants"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STARCH_AMD_LIB") or os.path.join(_HERE, "_build", "libstarch_amd.so")
@@ -121,6 +121,14 @@ class CatStats(ctypes.Structure):
 
 
 SETOPS = {"merge": 0, "intersect": 1, "difference": 2, "symmdiff": 3, "complement": 4}   # STARCH_SETOP_*
+# every op of starch_bedops_host (STARCH_SETOP_*, 0 to 9)
+BEDOPS_OPS = dict(SETOPS, element_of=5, not_element_of=6, partition=7, chop=8, everything=9)
+
+
+class BedopsOptions(ctypes.Structure):
+    """starch_bedops_options."""
+    _fields_ = [("op", ctypes.c_int32), ("threshold", ctypes.c_uint64), ("threshold_is_percent", ctypes.c_uint32),
+                ("chop", ctypes.c_uint64), ("stagger", ctypes.c_uint64), ("exclude_short", ctypes.c_uint32)]
 
 
 class SetopInput(ctypes.Structure):
@@ -270,6 +278,9 @@ def load():
         "starch_setop_device": ([vp, ctypes.c_int, vp, pu64, u64], ctypes.c_int),
         "starch_setop_get_stats": ([vp, ctypes.POINTER(SetopStats)], ctypes.c_int),
         "starch_setop_constants": ([ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+        "starch_bedops_host": ([vp, ctypes.POINTER(BedopsOptions), ctypes.POINTER(SetopInput), u64], ctypes.c_int),
+        "starch_bedops_device": ([vp, ctypes.POINTER(BedopsOptions), vp, pu64, u64], ctypes.c_int),
+        "starch_bedops_constants": ([ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
         "starch_map_host": ([vp, ctypes.POINTER(SetopInput), ctypes.POINTER(SetopInput), ctypes.POINTER(MapOptions)],
                             ctypes.c_int),
         "starch_map_device": ([vp, vp, pu64, u64, ctypes.POINTER(MapOptions)], ctypes.c_int),
@@ -708,8 +719,53 @@ class Starch:
     def symmdiff(self, *inputs) -> bytes: return self.setop("symmdiff", inputs)
     def complement(self, *inputs) -> bytes: return self.setop("complement", inputs)
 
+    def bedops(self, op: str, inputs, threshold="100%", chop=1, stagger=None, exclude_short=False) -> bytes:
+        """Any operation of the bedops command (a name of BEDOPS_OPS) over
+        sorted inputs (a list of bytes: BED text or archives).  The five of
+        setop() give BED3; "element_of" / "not_element_of" give the whole
+        lines of inputs[0] whose largest overlap with one merged run of the
+        other inputs reaches (or misses) ``threshold``, bases as an int or
+        "7", percent as "50%"; "partition" gives the disjoint pieces between
+        consecutive starts and stops that a line covers; "chop" cuts the
+        merged regions into pieces of ``chop`` bases every ``stagger`` (None:
+        ``chop``) bases, without the shorter ones if ``exclude_short``;
+        "everything" gives every line of every input in sort-bed's order.
+        The definitions are in include/starch_amd.h."""
+        o = _bedops_options(op, threshold, chop, stagger, exclude_short)
+        inputs = [bytes(b) for b in inputs]
+        arr = (SetopInput * max(1, len(inputs)))()
+        for k, b in enumerate(inputs):
+            arr[k].data = b
+            arr[k].len = len(b)
+        _check(self._L.starch_bedops_host(self._h, ctypes.byref(o), arr, len(inputs)), self._h)
+        return self._output()
+
+    def bedops_device(self, op: str, d_ptr: int, offs, threshold="100%", chop=1, stagger=None, exclude_short=False) -> int:
+        """The same for BED text in HBM, input k at d_ptr + [offs[k], offs[k+1]);
+        returns the output size (output_device_ptr())."""
+        o = _bedops_options(op, threshold, chop, stagger, exclude_short)
+        offs = [int(x) for x in offs]
+        a = (ctypes.c_uint64 * len(offs))(*offs)
+        _check(self._L.starch_bedops_device(self._h, ctypes.byref(o), ctypes.c_void_p(d_ptr), a, len(offs) - 1), self._h)
+        k = ctypes.c_uint64()
+        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
+        return k.value
+
+    def element_of(self, ref, *others, threshold="100%") -> bytes:
+        return self.bedops("element_of", (ref,) + others, threshold=threshold)
+
+    def not_element_of(self, ref, *others, threshold="100%") -> bytes:
+        return self.bedops("not_element_of", (ref,) + others, threshold=threshold)
+
+    def partition(self, *inputs) -> bytes: return self.bedops("partition", inputs)
+
+    def chop(self, *inputs, width=1, stagger=None, exclude_short=False) -> bytes:
+        return self.bedops("chop", inputs, chop=width, stagger=stagger, exclude_short=exclude_short)
+
+    def everything(self, *inputs) -> bytes: return self.bedops("everything", inputs)
+
     def setop_stats(self) -> dict:
-        """Of the last setop(): n_inputs / input_bytes / n_lines / n_chromosomes /
+        """Of the last setop() or bedops(): n_inputs / input_bytes / n_lines / n_chromosomes /
         runs_merged / groups / lines_out / output_bytes / archives_decoded /
         radix_passes / ms_*."""
         s = SetopStats()
@@ -780,6 +836,36 @@ def setop_constants():
     a = ctypes.c_uint32()
     _check(load().starch_setop_constants(ctypes.byref(a)))
     return a.value
+
+
+def bedops_constants():
+    """(runs per tile of element-of's range maximum, pieces per workgroup of
+    chop's expansion); no GPU needed."""
+    a, b = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(load().starch_bedops_constants(ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def _bedops_options(op, threshold, chop, stagger, exclude_short):
+    """starch_bedops_options; an unknown op or a threshold that is no number is
+    ValueError, every range is left to the library."""
+    if op not in BEDOPS_OPS:
+        raise ValueError("bedops: op must be one of %s" % ", ".join(BEDOPS_OPS))
+    o = BedopsOptions()
+    o.op = BEDOPS_OPS[op]
+    t = threshold.decode("ascii") if isinstance(threshold, (bytes, bytearray)) else threshold
+    if isinstance(t, str):
+        pct = t.endswith("%")
+        digits = t[:-1] if pct else t
+        if not (digits.isascii() and digits.isdigit()):
+            raise ValueError("bedops: threshold is a number of bases or a percentage such as '50%'")
+        o.threshold, o.threshold_is_percent = int(digits), int(pct)
+    else:
+        o.threshold, o.threshold_is_percent = int(t), 0
+    o.chop = int(chop)
+    o.stagger = 0 if stagger is None else int(stagger)
+    o.exclude_short = 1 if exclude_short else 0
+    return o
 
 
 def map_constants():

@@ -42,7 +42,7 @@ static_assert(kSortThreads == 256, "k_sb_hist and k_sb_scatter give one thread t
 
 // device scalars (u64 each); [0, 16) start as 0, [16, 32) as all ones
 enum : int {
-    S_NL = 0, S_NAMES, S_OVERFLOW, S_COLLISION, S_ENT, S_LONG, S_OR_RANK, S_OR_START, S_OR_STOP,
+    S_NL = 0, S_NAMES, S_OVERFLOW, S_COLLISION, S_ENT, S_LONG, S_OR_RANK, S_OR_START, S_OR_STOP, S_GATHERED,
     S_BAD = 16, S_DESC, S_AND_RANK, S_AND_START, S_AND_STOP, S_COUNT = 32
 };
 
@@ -681,6 +681,38 @@ const uint32_t* SortWorkspace::stage_radix(const uint32_t* rank, const uint64_t*
     return idx[cur];
 }
 
+uint64_t SortWorkspace::stage_gather(const uint8_t* d_bed, const uint32_t* order, uint64_t K, uint64_t bytes,
+                                     uint32_t* long_list, hipStream_t st, DevBuf& out)
+{
+    if (K == 0) {
+        (void)out.as<uint8_t>(64);
+        return 0;
+    }
+    uint64_t* scal = b_scal.as<uint64_t>(S_COUNT);
+    unsigned long long* uscal = reinterpret_cast<unsigned long long*>(scal);
+    const unsigned kblocks = blocks_for(K, kThreads);
+    const uint64_t* line_end = ln.line_end;
+    uint32_t* len = b_len.as<uint32_t>(K);
+    uint64_t* out_off = b_out_off.as<uint64_t>(K);
+    if (!long_list) long_list = b_long.as<uint32_t>(K);
+    HIP_CHECK(hipMemsetAsync(scal + S_LONG, 0, sizeof(uint64_t), st));
+    hipLaunchKernelGGL(k_sb_len, dim3(kblocks), dim3(kThreads), 0, st, order, line_end, K, len);
+    if (bytes == ~0ull) {
+        scan::excl_sum_u32_to_u64(len, out_off, K, scal + S_GATHERED, b_tmp, st);
+        HIP_CHECK(hipMemcpyAsync(&bytes, scal + S_GATHERED, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    } else {
+        scan::excl_sum_u32_to_u64(len, out_off, K, (uint64_t*)nullptr, b_tmp, st);
+    }
+    uint8_t* o = out.as<uint8_t>(bytes + 64);
+    hipLaunchKernelGGL(k_sb_copy, dim3(kblocks), dim3(kThreads), 0, st, d_bed, line_end, order, len, out_off, K, o, long_list,
+                       uscal);
+    hipLaunchKernelGGL(k_sb_copy_long, dim3((unsigned)std::min<uint64_t>(kblocks, 1024)), dim3(kThreads), 0, st, d_bed,
+                       line_end, order, len, out_off, o, long_list, uscal);
+    HIP_CHECK(hipGetLastError());
+    return bytes;
+}
+
 void SortWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, bool check_only, DevBuf& out, SortResult& res)
 {
     res = SortResult{};
@@ -734,16 +766,7 @@ void SortWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, bool c
             HIP_CHECK(hipGetLastError());
             HIP_CHECK(hipEventRecord(ev[3], st));
             // 5. gather
-            const uint64_t* line_end = ln.line_end;
-            uint32_t* len = b_len.as<uint32_t>(L);
-            uint64_t* out_off = b_out_off.as<uint64_t>(L);
-            hipLaunchKernelGGL(k_sb_len, dim3(lblocks), dim3(kThreads), 0, st, order, line_end, L, len);
-            scan::excl_sum_u32_to_u64(len, out_off, L, (uint64_t*)nullptr, b_tmp, st);
-            hipLaunchKernelGGL(k_sb_copy, dim3(lblocks), dim3(kThreads), 0, st, d_bed, line_end, order, len, out_off, L, o,
-                               spare, uscal);
-            hipLaunchKernelGGL(k_sb_copy_long, dim3((unsigned)std::min<uint64_t>(lblocks, 1024)), dim3(kThreads), 0, st,
-                               d_bed, line_end, order, len, out_off, o, spare, uscal);
-            HIP_CHECK(hipGetLastError());
+            (void)stage_gather(d_bed, order, L, res.out_bytes, spare, st, out);
         }
         HIP_CHECK(hipEventRecord(ev[4], st));
     }

@@ -64,6 +64,14 @@ struct SortWorkspace {
     // and the order is the input's.
     const uint32_t* stage_radix(const uint32_t* rank, const uint64_t* start, const uint64_t* stop, uint64_t L,
                                 const KeyBits& kb, hipStream_t st, uint32_t* passes);
+    // 5. the K parsed lines order[0, K) (line indices of the last stage_parse),
+    // whole and each ending in '\n', one after the other into out.  bytes: their
+    // total when the caller knows it, ~0: it is read back from the scan of their
+    // lengths.  long_list: K entries of scratch that are not order's (nullptr:
+    // the workspace's own).  Returns the total.
+    uint64_t stage_gather(const uint8_t* d_bed, const uint32_t* order, uint64_t K, uint64_t bytes, uint32_t* long_list,
+                          hipStream_t st, DevBuf& out);
+    DevBuf b_long;
     ~SortWorkspace();
 };
 

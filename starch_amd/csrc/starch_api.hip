@@ -3255,11 +3255,11 @@ uint8_t* setop_reserve(starch_ctx* c, uint64_t used, uint64_t want)
     return static_cast<uint8_t*>(b.p);
 }
 
-void setop_run(starch_ctx* c, int op, uint64_t len, const std::vector<uint64_t>& in_end, uint64_t archives, double ms_decode,
-               const std::chrono::steady_clock::time_point& t0)
+void setop_run(starch_ctx* c, const so::BedopsOptions& opt, uint64_t len, const std::vector<uint64_t>& in_end, uint64_t archives,
+               double ms_decode, const std::chrono::steady_clock::time_point& t0)
 {
     so::SetopResult r;
-    c->setop.run(c->sorter, op, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, c->st, c->setop_out, r);
+    c->setop.run_bedops(c->sorter, opt, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, c->st, c->setop_out, r);
     starch_setop_stats& s = c->ostats;
     s = starch_setop_stats{};
     s.n_inputs = in_end.size();
@@ -3355,13 +3355,36 @@ bool setop_args_ok(int op, const void* inputs, uint64_t ninputs)
 {
     return op >= STARCH_SETOP_MERGE && op <= STARCH_SETOP_COMPLEMENT && inputs && ninputs;
 }
-}  // namespace
 
-extern "C" {
-
-int starch_setop_host(starch_ctx* c, int op, const starch_setop_input* inputs, uint64_t ninputs)
+// starch_bedops_options checked into out; nothing here touches a device
+bool bedops_options_ok(const starch_bedops_options* o, uint64_t ninputs, so::BedopsOptions* out)
 {
-    if (!c || !setop_args_ok(op, inputs, ninputs)) return STARCH_ERR_ARG;
+    if (!o || o->op < STARCH_SETOP_MERGE || o->op > STARCH_SETOP_EVERYTHING || !ninputs) return false;
+    *out = so::BedopsOptions{};
+    out->op = o->op;
+    if (o->op == STARCH_SETOP_ELEMENT_OF || o->op == STARCH_SETOP_NOT_ELEMENT_OF) {
+        if (ninputs < 2 || o->threshold == 0 || (o->threshold_is_percent && o->threshold > 100)) return false;
+        out->threshold = o->threshold;
+        out->percent = o->threshold_is_percent != 0;
+    }
+    if (o->op == STARCH_SETOP_CHOP) {
+        if (o->chop == 0) return false;
+        out->chop = o->chop;
+        out->stagger = o->stagger ? o->stagger : o->chop;
+        out->exclude_short = o->exclude_short != 0;
+    }
+    return true;
+}
+
+so::BedopsOptions plain_op(int op)
+{
+    so::BedopsOptions o;
+    o.op = op;
+    return o;
+}
+
+int bedops_host(starch_ctx* c, const so::BedopsOptions& opt, const starch_setop_input* inputs, uint64_t ninputs)
+{
     for (uint64_t k = 0; k < ninputs; ++k)
         if (inputs[k].len && !inputs[k].data) return STARCH_ERR_ARG;
     GUARD(c)
@@ -3372,14 +3395,13 @@ int starch_setop_host(starch_ctx* c, int op, const starch_setop_input* inputs, u
     uint64_t archives = 0;
     const uint64_t len = setop_load_host(c, inputs, ninputs, "bedops", in_end, &archives);
     const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    setop_run(c, op, len, in_end, archives, ms_decode, t0);
+    setop_run(c, opt, len, in_end, archives, ms_decode, t0);
     return STARCH_OK;
     END_GUARD(c)
 }
 
-int starch_setop_device(starch_ctx* c, int op, const void* d_bed, const uint64_t* offs, uint64_t ninputs)
+int bedops_device(starch_ctx* c, const so::BedopsOptions& opt, const void* d_bed, const uint64_t* offs, uint64_t ninputs)
 {
-    if (!c || !setop_args_ok(op, offs, ninputs)) return STARCH_ERR_ARG;
     for (uint64_t k = 0; k < ninputs; ++k)
         if (offs[k + 1] < offs[k]) return STARCH_ERR_ARG;
     if (offs[ninputs] > offs[0] && !d_bed) return STARCH_ERR_ARG;
@@ -3389,9 +3411,46 @@ int starch_setop_device(starch_ctx* c, int op, const void* d_bed, const uint64_t
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<uint64_t> in_end;
     const uint64_t len = setop_load_device(c, d_bed, offs, ninputs, in_end);
-    setop_run(c, op, len, in_end, 0, 0.0, t0);
+    setop_run(c, opt, len, in_end, 0, 0.0, t0);
     return STARCH_OK;
     END_GUARD(c)
+}
+}  // namespace
+
+extern "C" {
+
+int starch_bedops_host(starch_ctx* c, const starch_bedops_options* o, const starch_setop_input* inputs, uint64_t ninputs)
+{
+    so::BedopsOptions opt;
+    if (!c || !inputs || !bedops_options_ok(o, ninputs, &opt)) return STARCH_ERR_ARG;
+    return bedops_host(c, opt, inputs, ninputs);
+}
+
+int starch_bedops_device(starch_ctx* c, const starch_bedops_options* o, const void* d_bed, const uint64_t* offs,
+                         uint64_t ninputs)
+{
+    so::BedopsOptions opt;
+    if (!c || !offs || !bedops_options_ok(o, ninputs, &opt)) return STARCH_ERR_ARG;
+    return bedops_device(c, opt, d_bed, offs, ninputs);
+}
+
+int starch_bedops_constants(uint32_t* rmq_tile, uint32_t* expand_tile)
+{
+    if (rmq_tile) *rmq_tile = so::kRmqTile;
+    if (expand_tile) *expand_tile = (uint32_t)so::kExpandTile;
+    return STARCH_OK;
+}
+
+int starch_setop_host(starch_ctx* c, int op, const starch_setop_input* inputs, uint64_t ninputs)
+{
+    if (!c || !setop_args_ok(op, inputs, ninputs)) return STARCH_ERR_ARG;
+    return bedops_host(c, plain_op(op), inputs, ninputs);
+}
+
+int starch_setop_device(starch_ctx* c, int op, const void* d_bed, const uint64_t* offs, uint64_t ninputs)
+{
+    if (!c || !setop_args_ok(op, offs, ninputs)) return STARCH_ERR_ARG;
+    return bedops_device(c, plain_op(op), d_bed, offs, ninputs);
 }
 
 int starch_setop_get_stats(starch_ctx* c, starch_setop_stats* out)
