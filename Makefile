@@ -8,9 +8,10 @@ HIPSRC := $(wildcard $(CSRC)/*.hip)
 CPPSRC := $(wildcard $(CSRC)/*.cpp)
 OBJS := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIPSRC)) $(patsubst $(CSRC)/%.cpp,$(BUILD)/%.o,$(CPPSRC))
 HDRS := $(wildcard $(CSRC)/*.hpp) include/starch_amd.h include/starch_bzlib.h
+CLIS := starch3 unstarch starchcat sort-bed bedops bedmap
 FLAGS := -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable --offload-arch=$(ARCH) $(EXTRA)
 
-all: $(BUILD)/libstarch_amd.so $(BUILD)/starch3 $(BUILD)/unstarch $(BUILD)/starchcat $(BUILD)/sort-bed $(BUILD)/bedops $(BUILD)/bedmap $(BUILD)/starch3_hpp_example oracle
+all: $(BUILD)/libstarch_amd.so $(CLIS:%=$(BUILD)/%) $(BUILD)/starch3_hpp_example oracle
 
 $(BUILD)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(BUILD)
@@ -23,23 +24,10 @@ $(BUILD)/%.o: $(CSRC)/%.cpp $(HDRS)
 $(BUILD)/libstarch_amd.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) -lpthread
 
-$(BUILD)/starch3: tools/starch3_cli.cpp $(BUILD)/libstarch_amd.so include/starch_amd.h
-	$(HIPCC) -O2 -std=c++17 -o $@ tools/starch3_cli.cpp -L$(BUILD) -lstarch_amd -Wl,-rpath,'$$ORIGIN'
-
-$(BUILD)/unstarch: tools/unstarch_cli.cpp $(BUILD)/libstarch_amd.so include/starch_amd.h
-	$(HIPCC) -O2 -std=c++17 -o $@ tools/unstarch_cli.cpp -L$(BUILD) -lstarch_amd -Wl,-rpath,'$$ORIGIN'
-
-$(BUILD)/starchcat: tools/starchcat_cli.cpp $(BUILD)/libstarch_amd.so include/starch_amd.h
-	$(HIPCC) -O2 -std=c++17 -o $@ tools/starchcat_cli.cpp -L$(BUILD) -lstarch_amd -Wl,-rpath,'$$ORIGIN'
-
-$(BUILD)/sort-bed: tools/sortbed_cli.cpp $(BUILD)/libstarch_amd.so include/starch_amd.h
-	$(HIPCC) -O2 -std=c++17 -o $@ tools/sortbed_cli.cpp -L$(BUILD) -lstarch_amd -Wl,-rpath,'$$ORIGIN'
-
-$(BUILD)/bedops: tools/bedops_cli.cpp $(BUILD)/libstarch_amd.so include/starch_amd.h
-	$(HIPCC) -O2 -std=c++17 -o $@ tools/bedops_cli.cpp -L$(BUILD) -lstarch_amd -Wl,-rpath,'$$ORIGIN'
-
-$(BUILD)/bedmap: tools/bedmap_cli.cpp $(BUILD)/libstarch_amd.so include/starch_amd.h
-	$(HIPCC) -O2 -std=c++17 -o $@ tools/bedmap_cli.cpp -L$(BUILD) -lstarch_amd -Wl,-rpath,'$$ORIGIN'
+# a command's source is its name without the hyphen
+.SECONDEXPANSION:
+$(CLIS:%=$(BUILD)/%): $(BUILD)/%: tools/$$(subst -,,$$*)_cli.cpp tools/cli_common.hpp $(BUILD)/libstarch_amd.so include/starch_amd.h
+	$(HIPCC) -O2 -std=c++17 -o $@ $< -L$(BUILD) -lstarch_amd -Wl,-rpath,'$$ORIGIN'
 
 $(BUILD)/starch3_hpp_example: tools/starch3_hpp_example.cpp $(BUILD)/libstarch_amd.so include/starch3_amd.hpp include/starch_amd.h
 	g++ -O2 -std=c++11 -Wall -o $@ tools/starch3_hpp_example.cpp -L$(BUILD) -lstarch_amd -Wl,-rpath,'$$ORIGIN'

@@ -1,0 +1,442 @@
+// starch_amd/csrc/api_bed.hip -- the C ABI of sort-bed, bedops and bedmap.
+#include <string.h>
+
+#include <algorithm>
+#include <chrono>
+#include <vector>
+
+#include "api_int.hpp"
+
+using namespace api;
+
+namespace {
+// input k of a device call is d_bed[offs[k], offs[k + 1])
+bool offs_ok(const void* d_bed, const uint64_t* offs, uint64_t ninputs)
+{
+    for (uint64_t k = 0; k < ninputs; ++k)
+        if (offs[k + 1] < offs[k]) return false;
+    return offs[ninputs] <= offs[0] || d_bed;
+}
+}  // namespace
+
+// ---- sort-bed (include/starch_amd.h; kernels in sort_bed.hip) -----------------
+namespace {
+void sort_run(starch_ctx* c, const uint8_t* d, uint64_t n, bool check_only)
+{
+    c->have_sstats = false;
+    if (!check_only) c->have_out = false;
+    sb::SortResult r;
+    c->sorter.run(d, n, c->st, check_only, c->sort_out, r);
+    starch_sort_stats& s = c->sstats;
+    s = starch_sort_stats{};
+    s.input_bytes = n;
+    s.n_lines = r.n_lines;
+    s.n_chromosomes = r.n_chromosomes;
+    s.already_sorted = r.already_sorted ? 1 : 0;
+    s.first_unsorted_line = r.first_unsorted_line;
+    s.radix_passes = r.radix_passes;
+    s.ms_parse = r.ms_parse;
+    s.ms_rank = r.ms_rank;
+    s.ms_sort = r.ms_sort;
+    s.ms_gather = r.ms_gather;
+    s.ms_total = r.ms_total;
+    c->have_sstats = true;
+    if (check_only) return;
+    publish(c, c->sort_out, r.out_bytes);
+}
+const uint8_t* sort_upload(starch_ctx* c, const void* bed, uint64_t n)
+{
+    uint8_t* d = c->input.as<uint8_t>(n + 64);
+    HostRegistration reg(bed, n, 256ull << 20);
+    reg.h2d(d, bed, n, c->st);
+    HIP_CHECK(hipStreamSynchronize(c->st));
+    return d;
+}
+}  // namespace
+
+extern "C" {
+
+int starch_sort_device(starch_ctx* c, const void* d_bed, uint64_t n)
+{
+    GUARD(c)
+    if (n && !d_bed) return STARCH_ERR_ARG;
+    sort_run(c, static_cast<const uint8_t*>(d_bed), n, false);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_sort_host(starch_ctx* c, const void* bed, uint64_t n)
+{
+    GUARD(c)
+    if (n && !bed) return STARCH_ERR_ARG;
+    sort_run(c, sort_upload(c, bed, n), n, false);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_sort_check_host(starch_ctx* c, const void* bed, uint64_t n, uint64_t* first_unsorted_line)
+{
+    GUARD(c)
+    if ((n && !bed) || !first_unsorted_line) return STARCH_ERR_ARG;
+    sort_run(c, sort_upload(c, bed, n), n, true);
+    *first_unsorted_line = c->sstats.first_unsorted_line;
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_sort_encode_host(starch_ctx* c, const void* bed, uint64_t n, const starch_options* opt)
+{
+    GUARD(c)
+    if (n && !bed) return STARCH_ERR_ARG;
+    const starch_options o = options_of(opt);
+    if (!options_ok(o)) return STARCH_ERR_ARG;
+    c->have = false;
+    sort_run(c, sort_upload(c, bed, n), n, false);
+    // the sorted text is in sort_out, which no encoder stage writes
+    encode_device(c, c->out_dev, c->out_bytes, o);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_sort_get_stats(starch_ctx* c, starch_sort_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_sstats) return STARCH_ERR_STATE;
+    *out = c->sstats;
+    return STARCH_OK;
+}
+
+int starch_sort_constants(uint32_t* tile_lines, uint32_t* wave_copy_bytes)
+{
+    if (tile_lines) *tile_lines = (uint32_t)sb::kSortTile;
+    if (wave_copy_bytes) *wave_copy_bytes = sb::kWaveCopyBytes;
+    return STARCH_OK;
+}
+
+}  // extern "C"
+
+// ---- bedops set operations (include/starch_amd.h; kernels in bed_setops.hip) ----
+namespace {
+// c->setop_in with room for `want` bytes, its first `used` bytes kept
+uint8_t* setop_reserve(starch_ctx* c, uint64_t used, uint64_t want)
+{
+    DevBuf& b = c->setop_in;
+    if (b.p && want <= b.cap) return static_cast<uint8_t*>(b.p);
+    DevBuf nb;
+    (void)nb.get(std::max<uint64_t>(want, 2 * (uint64_t)b.cap));
+    if (used) {
+        HIP_CHECK(hipMemcpyAsync(nb.p, b.p, used, hipMemcpyDeviceToDevice, c->st));
+        HIP_CHECK(hipStreamSynchronize(c->st));
+    }
+    std::swap(b.p, nb.p);
+    std::swap(b.cap, nb.cap);
+    return static_cast<uint8_t*>(b.p);
+}
+
+void setop_run(starch_ctx* c, const so::BedopsOptions& opt, uint64_t len, const std::vector<uint64_t>& in_end, uint64_t archives,
+               double ms_decode, const std::chrono::steady_clock::time_point& t0)
+{
+    so::SetopResult r;
+    c->setop.run_bedops(c->sorter, opt, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, c->st, c->setop_out, r);
+    starch_setop_stats& s = c->ostats;
+    s = starch_setop_stats{};
+    s.n_inputs = in_end.size();
+    s.input_bytes = len;
+    s.n_lines = r.n_lines;
+    s.n_chromosomes = r.n_chromosomes;
+    s.runs_merged = r.runs_merged;
+    s.groups = r.groups;
+    s.lines_out = r.lines_out;
+    s.output_bytes = r.out_bytes;
+    s.archives_decoded = archives;
+    s.radix_passes = r.radix_passes;
+    s.ms_decode = (float)ms_decode;
+    s.ms_parse = r.ms_parse;
+    s.ms_merge = r.ms_merge;
+    s.ms_sort = r.ms_sort;
+    s.ms_sweep = r.ms_sweep;
+    s.ms_format = r.ms_format;
+    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->have_ostats = true;
+    publish(c, c->setop_out, r.out_bytes);
+}
+
+// The inputs (BED text or archives, in host memory) back to back in c->setop_in,
+// each non-empty one ending in '\n'.  Returns the bytes; in_end: where each ends.
+uint64_t setop_load_host(starch_ctx* c, const starch_setop_input* inputs, uint64_t ninputs, const char* tool,
+                         std::vector<uint64_t>& in_end, uint64_t* archives_out)
+{
+    uint64_t want = 64;
+    for (uint64_t k = 0; k < ninputs; ++k) want += inputs[k].len + 1;
+    uint8_t* d = setop_reserve(c, 0, want);
+    uint64_t len = 0, archives = 0;
+    for (uint64_t k = 0; k < ninputs; ++k) {
+        const uint8_t* a = static_cast<const uint8_t*>(inputs[k].data);
+        const uint64_t n = inputs[k].len;
+        uint64_t m = n;
+        uint8_t last = '\n';
+        if (n >= 4 && memcmp(a, archive::kMagic, 4) == 0) {
+            ++archives;
+            m = unstarch_to_ut_out(c, a, n, tool);
+            want += m;
+            d = setop_reserve(c, len, want);
+            if (m) {
+                HIP_CHECK(hipMemcpyAsync(d + len, c->ut_out.p, m, hipMemcpyDeviceToDevice, c->st));
+                HIP_CHECK(hipMemcpyAsync(&last, static_cast<const uint8_t*>(c->ut_out.p) + (m - 1), 1, hipMemcpyDeviceToHost,
+                                         c->st));
+                HIP_CHECK(hipStreamSynchronize(c->st));
+            }
+        } else if (n) {
+            HIP_CHECK(hipMemcpyAsync(d + len, a, n, hipMemcpyHostToDevice, c->st));
+            last = a[n - 1];
+        }
+        len += m;
+        if (m && last != '\n') {
+            HIP_CHECK(hipMemsetAsync(d + len, '\n', 1, c->st));
+            ++len;
+        }
+        in_end.push_back(len);
+    }
+    HIP_CHECK(hipStreamSynchronize(c->st));
+    if (archives_out) *archives_out = archives;
+    return len;
+}
+
+// The same for BED text in HBM: input k is d_bed[offs[k], offs[k + 1]).
+uint64_t setop_load_device(starch_ctx* c, const void* d_bed, const uint64_t* offs, uint64_t ninputs,
+                           std::vector<uint64_t>& in_end)
+{
+    const uint8_t* src = static_cast<const uint8_t*>(d_bed);
+    uint8_t* d = setop_reserve(c, 0, offs[ninputs] - offs[0] + ninputs + 64);
+    std::vector<uint8_t> last(ninputs, (uint8_t)'\n');
+    for (uint64_t k = 0; k < ninputs; ++k)
+        if (offs[k + 1] > offs[k])
+            HIP_CHECK(hipMemcpyAsync(&last[k], src + offs[k + 1] - 1, 1, hipMemcpyDeviceToHost, c->st));
+    HIP_CHECK(hipStreamSynchronize(c->st));
+    uint64_t len = 0;
+    for (uint64_t k = 0; k < ninputs; ++k) {
+        const uint64_t m = offs[k + 1] - offs[k];
+        if (m) HIP_CHECK(hipMemcpyAsync(d + len, src + offs[k], m, hipMemcpyDeviceToDevice, c->st));
+        len += m;
+        if (m && last[k] != '\n') {
+            HIP_CHECK(hipMemsetAsync(d + len, '\n', 1, c->st));
+            ++len;
+        }
+        in_end.push_back(len);
+    }
+    return len;
+}
+
+bool setop_args_ok(int op, const void* inputs, uint64_t ninputs)
+{
+    return op >= STARCH_SETOP_MERGE && op <= STARCH_SETOP_COMPLEMENT && inputs && ninputs;
+}
+
+// starch_bedops_options checked into out; nothing here touches a device
+bool bedops_options_ok(const starch_bedops_options* o, uint64_t ninputs, so::BedopsOptions* out)
+{
+    if (!o || o->op < STARCH_SETOP_MERGE || o->op > STARCH_SETOP_EVERYTHING || !ninputs) return false;
+    *out = so::BedopsOptions{};
+    out->op = o->op;
+    if (o->op == STARCH_SETOP_ELEMENT_OF || o->op == STARCH_SETOP_NOT_ELEMENT_OF) {
+        if (ninputs < 2 || o->threshold == 0 || (o->threshold_is_percent && o->threshold > 100)) return false;
+        out->threshold = o->threshold;
+        out->percent = o->threshold_is_percent != 0;
+    }
+    if (o->op == STARCH_SETOP_CHOP) {
+        if (o->chop == 0) return false;
+        out->chop = o->chop;
+        out->stagger = o->stagger ? o->stagger : o->chop;
+        out->exclude_short = o->exclude_short != 0;
+    }
+    return true;
+}
+
+so::BedopsOptions plain_op(int op)
+{
+    so::BedopsOptions o;
+    o.op = op;
+    return o;
+}
+
+int bedops_host(starch_ctx* c, const so::BedopsOptions& opt, const starch_setop_input* inputs, uint64_t ninputs)
+{
+    for (uint64_t k = 0; k < ninputs; ++k)
+        if (inputs[k].len && !inputs[k].data) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_ostats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> in_end;
+    uint64_t archives = 0;
+    const uint64_t len = setop_load_host(c, inputs, ninputs, "bedops", in_end, &archives);
+    const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    setop_run(c, opt, len, in_end, archives, ms_decode, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int bedops_device(starch_ctx* c, const so::BedopsOptions& opt, const void* d_bed, const uint64_t* offs, uint64_t ninputs)
+{
+    if (!offs_ok(d_bed, offs, ninputs)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_ostats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> in_end;
+    const uint64_t len = setop_load_device(c, d_bed, offs, ninputs, in_end);
+    setop_run(c, opt, len, in_end, 0, 0.0, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+}  // namespace
+
+extern "C" {
+
+int starch_bedops_host(starch_ctx* c, const starch_bedops_options* o, const starch_setop_input* inputs, uint64_t ninputs)
+{
+    so::BedopsOptions opt;
+    if (!c || !inputs || !bedops_options_ok(o, ninputs, &opt)) return STARCH_ERR_ARG;
+    return bedops_host(c, opt, inputs, ninputs);
+}
+
+int starch_bedops_device(starch_ctx* c, const starch_bedops_options* o, const void* d_bed, const uint64_t* offs,
+                         uint64_t ninputs)
+{
+    so::BedopsOptions opt;
+    if (!c || !offs || !bedops_options_ok(o, ninputs, &opt)) return STARCH_ERR_ARG;
+    return bedops_device(c, opt, d_bed, offs, ninputs);
+}
+
+int starch_bedops_constants(uint32_t* rmq_tile, uint32_t* expand_tile)
+{
+    if (rmq_tile) *rmq_tile = so::kRmqTile;
+    if (expand_tile) *expand_tile = (uint32_t)so::kExpandTile;
+    return STARCH_OK;
+}
+
+int starch_setop_host(starch_ctx* c, int op, const starch_setop_input* inputs, uint64_t ninputs)
+{
+    if (!c || !setop_args_ok(op, inputs, ninputs)) return STARCH_ERR_ARG;
+    return bedops_host(c, plain_op(op), inputs, ninputs);
+}
+
+int starch_setop_device(starch_ctx* c, int op, const void* d_bed, const uint64_t* offs, uint64_t ninputs)
+{
+    if (!c || !setop_args_ok(op, offs, ninputs)) return STARCH_ERR_ARG;
+    return bedops_device(c, plain_op(op), d_bed, offs, ninputs);
+}
+
+int starch_setop_get_stats(starch_ctx* c, starch_setop_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_ostats) return STARCH_ERR_STATE;
+    *out = c->ostats;
+    return STARCH_OK;
+}
+
+int starch_setop_constants(uint32_t* scan_tile_lines)
+{
+    if (scan_tile_lines) *scan_tile_lines = (uint32_t)so::kScanTile;
+    return STARCH_OK;
+}
+
+}  // extern "C"
+
+// ---- bedmap (include/starch_amd.h; kernels in bed_map.hip) -------------------------
+namespace {
+bool map_options_ok(const starch_map_options* o, bm::MapOptions* out)
+{
+    if (!o || o->ncols < 1 || o->ncols > 8 || o->delim_len < 1 || o->delim_len > 8) return false;
+    uint32_t seen = 0;
+    for (uint32_t k = 0; k < o->ncols; ++k) {
+        if (o->cols[k] > STARCH_MAP_ECHO_REF_SIZE || ((seen >> o->cols[k]) & 1)) return false;
+        seen |= 1u << o->cols[k];
+        out->cols[k] = o->cols[k];
+    }
+    out->ncols = o->ncols;
+    out->range = o->range;
+    out->skip_unmapped = o->skip_unmapped ? 1 : 0;
+    out->delim_len = o->delim_len;
+    memcpy(out->delim, o->delim, o->delim_len);
+    return true;
+}
+
+void map_run(starch_ctx* c, const bm::MapOptions& opt, uint64_t len, const std::vector<uint64_t>& in_end, double ms_decode,
+             const std::chrono::steady_clock::time_point& t0)
+{
+    bm::MapResult r;
+    c->mapper.run(c->sorter, c->setop, opt, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, c->st, c->setop_out, r);
+    starch_map_stats& s = c->mstats;
+    s = starch_map_stats{};
+    s.n_ref = r.n_ref;
+    s.n_map = r.n_map;
+    s.n_chromosomes = r.n_chromosomes;
+    s.map_runs_merged = r.map_runs_merged;
+    s.stops_sorted = r.stops_sorted;
+    s.lines_out = r.lines_out;
+    s.output_bytes = r.out_bytes;
+    s.ms_decode = (float)ms_decode;
+    s.ms_parse = r.ms_parse;
+    s.ms_build = r.ms_build;
+    s.ms_query = r.ms_query;
+    s.ms_format = r.ms_format;
+    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->have_mstats = true;
+    publish(c, c->setop_out, r.out_bytes);
+}
+}  // namespace
+
+extern "C" {
+
+int starch_map_host(starch_ctx* c, const starch_setop_input* ref, const starch_setop_input* map, const starch_map_options* opt)
+{
+    bm::MapOptions mo;
+    if (!c || !ref || !map_options_ok(opt, &mo)) return STARCH_ERR_ARG;
+    if ((ref->len && !ref->data) || (map && map->len && !map->data)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_mstats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<starch_setop_input> inputs{*ref};
+    if (map) inputs.push_back(*map);
+    std::vector<uint64_t> in_end;
+    const uint64_t len = setop_load_host(c, inputs.data(), inputs.size(), "bedmap", in_end, nullptr);
+    const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    map_run(c, mo, len, in_end, ms_decode, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_map_device(starch_ctx* c, const void* d_bed, const uint64_t* offs, uint64_t ninputs, const starch_map_options* opt)
+{
+    bm::MapOptions mo;
+    if (!c || !offs || ninputs < 1 || ninputs > 2 || !map_options_ok(opt, &mo)) return STARCH_ERR_ARG;
+    if (!offs_ok(d_bed, offs, ninputs)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_mstats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> in_end;
+    const uint64_t len = setop_load_device(c, d_bed, offs, ninputs, in_end);
+    map_run(c, mo, len, in_end, 0.0, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_map_get_stats(starch_ctx* c, starch_map_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_mstats) return STARCH_ERR_STATE;
+    *out = c->mstats;
+    return STARCH_OK;
+}
+
+int starch_map_constants(uint32_t* tile_refs, uint32_t* lds_window)
+{
+    if (tile_refs) *tile_refs = (uint32_t)bm::kTileRefs;
+    if (lds_window) *lds_window = bm::kLdsWindow;
+    return STARCH_OK;
+}
+
+}  // extern "C"

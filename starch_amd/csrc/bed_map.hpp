@@ -12,7 +12,7 @@ namespace bm {
 constexpr int kTileRefs = 256;          // reference lines per query workgroup (one thread each)
 constexpr uint32_t kLdsWindow = 1024;   // largest window into the map starts, and into the stops, staged in LDS
 
-struct MapOptions {                     // checked by the caller (starch_api.hip)
+struct MapOptions {                     // checked by the caller (api_bed.hip)
     uint32_t ncols = 0;
     uint8_t cols[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // STARCH_MAP_*
     uint64_t range = 0;

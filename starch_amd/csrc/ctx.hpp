@@ -1,5 +1,5 @@
 // starch_amd/csrc/ctx.hpp -- the context behind the C ABI's opaque
-// starch_ctx (include/starch_amd.h), shared by starch_api.hip (encode,
+// starch_ctx (include/starch_amd.h), shared by the api_*.hip files (encode,
 // stream, decode entry points) and gather.hip (the multi-rank archive gather).
 #pragma once
 #include <stdint.h>

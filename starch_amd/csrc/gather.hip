@@ -38,7 +38,7 @@
 
 #include <rccl/rccl.h>
 
-#include "ctx.hpp"
+#include "api_int.hpp"
 #include "shard.hpp"
 
 struct starch_comm {
@@ -450,12 +450,6 @@ void tcp_bootstrap(int rank, int world, const char* host, int port, ncclUniqueId
     }
 }
 
-struct DevGuard {
-    int prev = -1;
-    explicit DevGuard(int d) { (void)hipGetDevice(&prev); (void)hipSetDevice(d); }
-    ~DevGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
 thread_local std::string g_comm_err;
 
 int comm_fail(const std::exception& e, int code)
@@ -488,7 +482,7 @@ int starch_comm_create(int device, int rank, int world, const void* id, starch_c
     if (!out || !id || world < 1 || rank < 0 || rank >= world) return STARCH_ERR_ARG;
     *out = nullptr;
     try {
-        DevGuard g(device);
+        api::Ctx g(device);
         ncclUniqueId u;
         memcpy(&u, id, sizeof(u));
         starch_comm* m = new starch_comm();
@@ -539,7 +533,7 @@ void starch_comm_destroy(starch_comm* m)
 {
     if (!m) return;
     {
-        DevGuard g(m->device);
+        api::Ctx g(m->device);
         if (m->comm) (void)rccl().CommDestroy(m->comm);
         m->s0.release();
         m->s1.release();
@@ -557,7 +551,7 @@ int starch_gather_archive(starch_ctx* c, starch_comm* m, const starch_options* o
     starch_options_init(&o);
     if (opt) o = *opt;
     try {
-        DevGuard g(c->device);
+        api::Ctx g(c->device);
         RcclTransport t(m, c);
         Gathered r;
         gather(t, c->segs, c->names, static_cast<const uint8_t*>(c->part.p), o, r);

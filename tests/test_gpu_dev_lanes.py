@@ -1,4 +1,4 @@
-"""Encoder lanes of the device path (starch_api.hip lane_cuts / encode_units):
+"""Encoder lanes of the device path (api_encode.hip lane_cuts / encode_units):
 after one transform, the segments split into contiguous runs encoded by
 separate encoders on their own streams and host threads, then emitted in
 order.  The archive must be byte-identical whatever the lane count, and the

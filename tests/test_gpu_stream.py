@@ -312,7 +312,7 @@ def test_stream_inside_chromosome_hold_knob():
 def test_stream_large_open_pieces_wait_for_their_copy():
     """Batches cut inside one large chromosome (the piece path, with a context
     line) must not be read by the encoder before their H2D copy on the copy
-    stream has landed (starch_api.hip stream_encode waits on the batch's copy
+    stream has landed (api_stream.hip stream_encode waits on the batch's copy
     event before both paths).  chr1 of cfg2 (~190 MB) in 48 MiB pieces and
     64 MiB batches: every batch is an open piece whose copy is tens of MB."""
     import starch_amd

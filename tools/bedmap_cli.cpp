@@ -19,7 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "../include/starch_amd.h"
+#include "cli_common.hpp"
 
 static const char* kName = "bedmap";
 static const char* kVersion = "0.1 (mi355x)";
@@ -67,20 +67,6 @@ static int bad_usage(const char* why, const char* what)
     fprintf(stderr, "Error: %s%s%s\n", why, what ? ": " : "", what ? what : "");
     usage(stderr);
     return kUsageError;
-}
-
-static bool read_all(int fd, std::vector<char>* out)
-{
-    const size_t kPiece = 16u << 20;
-    for (;;) {
-        const size_t at = out->size();
-        out->resize(at + kPiece);
-        const ssize_t r = read(fd, out->data() + at, kPiece);
-        if (r < 0 && errno == EINTR) { out->resize(at); continue; }
-        if (r < 0) { out->resize(at); return false; }
-        out->resize(at + (size_t)r);
-        if (r == 0) return true;
-    }
 }
 
 static bool parse_u64(const char* s, uint64_t* v)
@@ -157,7 +143,7 @@ int main(int argc, char** argv)
             }
             case O_DEVICE: device = atoi(optarg); break;
             case O_HELP: usage(stdout); return 0;
-            case O_VERSION: printf("%s\n  version: %s\n", kName, kVersion); return 0;
+            case O_VERSION: cli::print_version(kName, kVersion); return 0;
             default: return bad_usage("unsupported or unknown option", argv[optind - 1]);
         }
     }
@@ -171,50 +157,12 @@ int main(int argc, char** argv)
     if (paths.empty() || paths.size() > 2) return bad_usage("one reference and at most one map are needed", nullptr);
     if (paths.size() == 2 && paths[0] == "-" && paths[1] == "-") return bad_usage("stdin (-) may be named once", nullptr);
 
-    std::vector<std::vector<char>> data(paths.size());
-    for (size_t k = 0; k < paths.size(); ++k) {
-        const std::string& p = paths[k];
-        const int fd = p == "-" ? STDIN_FILENO : open(p.c_str(), O_RDONLY);
-        if (fd < 0) {
-            fprintf(stderr, "Error: Input file does not exist (%s)\n", p.c_str());
-            return ENODATA;
-        }
-        const bool ok = read_all(fd, &data[k]);
-        if (fd != STDIN_FILENO) close(fd);
-        if (!ok) {
-            fprintf(stderr, "Error: reading %s failed (%s)\n", p.c_str(), strerror(errno));
-            return EIO;
-        }
-    }
+    std::vector<std::vector<char>> data;
+    if (const int e = cli::load_inputs(paths, &data)) return e;
     starch_setop_input in[2];
     for (size_t k = 0; k < paths.size(); ++k) in[k] = starch_setop_input{data[k].data(), (uint64_t)data[k].size()};
 
     starch_ctx* ctx = nullptr;
-    int rc = starch_create(device, &ctx);
-    if (rc != STARCH_OK) {
-        fprintf(stderr, "Error: no GPU context (%s)\n", starch_strerror(rc));
-        return EINVAL;
-    }
-    rc = starch_map_host(ctx, &in[0], paths.size() == 2 ? &in[1] : nullptr, &opt);
-    uint64_t bytes = 0;
-    std::vector<char> out;
-    if (rc == STARCH_OK) rc = starch_output_size(ctx, &bytes);
-    if (rc == STARCH_OK && bytes) {
-        out.resize(bytes);
-        rc = starch_output_copy(ctx, out.data(), bytes);
-    }
-    if (rc != STARCH_OK) {
-        fprintf(stderr, "Error: %s (%s)\n", starch_last_error(ctx), starch_strerror(rc));
-        starch_destroy(ctx);
-        return rc == STARCH_ERR_MEM ? ENOMEM : EINVAL;
-    }
-    for (uint64_t w = 0; w < bytes;) {
-        const size_t k = fwrite(out.data() + w, 1, bytes - w, stdout);
-        if (k == 0) break;
-        w += k;
-    }
-    const bool ok = fflush(stdout) == 0 && !ferror(stdout);
-    if (!ok) fprintf(stderr, "Error: writing the output failed (%s)\n", strerror(errno ? errno : EIO));
-    starch_destroy(ctx);
-    return ok ? 0 : EIO;
+    if (const int e = cli::open_ctx(device, &ctx)) return e;
+    return cli::finish_output(ctx, starch_map_host(ctx, &in[0], paths.size() == 2 ? &in[1] : nullptr, &opt), "Error: %s (%s)\n");
 }

@@ -18,7 +18,7 @@
 #include <string>
 #include <vector>
 
-#include "../include/starch_amd.h"
+#include "cli_common.hpp"
 
 static const char* kName = "bedops";
 static const char* kVersion = "0.2 (mi355x)";
@@ -82,20 +82,6 @@ static void usage(FILE* f)
             "  A long option may be cut short while only one name begins that way, and its value\n"
             "  may be attached with = (--chop=100, --element-of=50%%).\n",
             kName, kVersion);
-}
-
-static bool read_all(int fd, std::vector<char>* out)
-{
-    const size_t kPiece = 16u << 20;
-    for (;;) {
-        const size_t at = out->size();
-        out->resize(at + kPiece);
-        const ssize_t r = read(fd, out->data() + at, kPiece);
-        if (r < 0 && errno == EINTR) { out->resize(at); continue; }
-        if (r < 0) { out->resize(at); return false; }
-        out->resize(at + (size_t)r);
-        if (r == 0) return true;
-    }
 }
 
 // [0-9]+ (pct == nullptr) or [0-9]+%? in full, and the number fits 64 bits
@@ -211,7 +197,7 @@ int main(int argc, char** argv)
             else if (name == "chop") chop(&i);
             else if (name == "everything") set_op(STARCH_SETOP_EVERYTHING);
             else if (name == "help") { usage(stdout); return 0; }
-            else if (name == "version") { printf("%s\n  version: %s\n", kName, kVersion); return 0; }
+            else if (name == "version") { cli::print_version(kName, kVersion); return 0; }
             else bad = true;
             attached_value = nullptr;
             continue;
@@ -238,7 +224,7 @@ int main(int argc, char** argv)
                     if (is_last) i = at;
                     break;
                 case 'h': usage(stdout); return 0;
-                case 'v': printf("%s\n  version: %s\n", kName, kVersion); return 0;
+                case 'v': cli::print_version(kName, kVersion); return 0;
                 default: bad = true;
             }
         }
@@ -258,50 +244,12 @@ int main(int argc, char** argv)
         return EXIT_FAILURE;
     }
 
-    std::vector<std::vector<char>> data(paths.size());
-    for (size_t k = 0; k < paths.size(); ++k) {
-        const std::string& p = paths[k];
-        const int fd = p == "-" ? STDIN_FILENO : open(p.c_str(), O_RDONLY);
-        if (fd < 0) {
-            fprintf(stderr, "Error: Input file does not exist (%s)\n", p.c_str());
-            return ENODATA;
-        }
-        const bool ok = read_all(fd, &data[k]);
-        if (fd != STDIN_FILENO) close(fd);
-        if (!ok) {
-            fprintf(stderr, "Error: reading %s failed (%s)\n", p.c_str(), strerror(errno));
-            return EIO;
-        }
-    }
+    std::vector<std::vector<char>> data;
+    if (const int e = cli::load_inputs(paths, &data)) return e;
     std::vector<starch_setop_input> in(paths.size());
     for (size_t k = 0; k < paths.size(); ++k) in[k] = starch_setop_input{data[k].data(), (uint64_t)data[k].size()};
 
     starch_ctx* ctx = nullptr;
-    int rc = starch_create(device, &ctx);
-    if (rc != STARCH_OK) {
-        fprintf(stderr, "Error: no GPU context (%s)\n", starch_strerror(rc));
-        return EINVAL;
-    }
-    rc = starch_bedops_host(ctx, &opt, in.data(), in.size());
-    uint64_t bytes = 0;
-    std::vector<char> out;
-    if (rc == STARCH_OK) rc = starch_output_size(ctx, &bytes);
-    if (rc == STARCH_OK && bytes) {
-        out.resize(bytes);
-        rc = starch_output_copy(ctx, out.data(), bytes);
-    }
-    if (rc != STARCH_OK) {
-        fprintf(stderr, "Error: %s (%s)\n", starch_last_error(ctx), starch_strerror(rc));
-        starch_destroy(ctx);
-        return rc == STARCH_ERR_MEM ? ENOMEM : EINVAL;
-    }
-    for (uint64_t w = 0; w < bytes;) {
-        const size_t k = fwrite(out.data() + w, 1, bytes - w, stdout);
-        if (k == 0) break;
-        w += k;
-    }
-    const bool ok = fflush(stdout) == 0 && !ferror(stdout);
-    if (!ok) fprintf(stderr, "Error: writing the output failed (%s)\n", strerror(errno ? errno : EIO));
-    starch_destroy(ctx);
-    return ok ? 0 : EIO;
+    if (const int e = cli::open_ctx(device, &ctx)) return e;
+    return cli::finish_output(ctx, starch_bedops_host(ctx, &opt, in.data(), in.size()), "Error: %s (%s)\n");
 }

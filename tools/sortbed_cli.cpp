@@ -22,7 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "../include/starch_amd.h"
+#include "cli_common.hpp"
 
 static const char* kName = "sort-bed";
 static const char* kVersion = "0.1 (mi355x)";
@@ -50,20 +50,6 @@ static void usage(FILE* f)
             kName, kVersion);
 }
 
-static bool read_all(int fd, std::vector<char>* out)
-{
-    const size_t kPiece = 16u << 20;
-    for (;;) {
-        const size_t at = out->size();
-        out->resize(at + kPiece);
-        const ssize_t r = read(fd, out->data() + at, kPiece);
-        if (r < 0 && errno == EINTR) { out->resize(at); continue; }
-        if (r < 0) { out->resize(at); return false; }
-        out->resize(at + (size_t)r);
-        if (r == 0) return true;
-    }
-}
-
 int main(int argc, char** argv)
 {
     int check = 0, device = 0;
@@ -79,7 +65,7 @@ int main(int argc, char** argv)
             case 'c': check = 1; break;
             case 'D': device = atoi(optarg); break;
             case 'h': usage(stdout); return 0;
-            case 'v': printf("%s\n  version: %s\n", kName, kVersion); return 0;
+            case 'v': cli::print_version(kName, kVersion); return 0;
             default: usage(stderr); return EXIT_FAILURE;
         }
     }
@@ -102,7 +88,7 @@ int main(int argc, char** argv)
     const void* bed = nullptr;
     uint64_t n = 0;
     void* map = MAP_FAILED;
-    std::vector<char> data;
+    std::vector<std::vector<char>> data(1);   // the input read, when it is not mapped
     if (inputs.size() == 1 && inputs[0] != "-") {
         const int fd = open(inputs[0].c_str(), O_RDONLY);
         if (fd < 0 || fstat(fd, &st) != 0) {
@@ -114,44 +100,24 @@ int main(int argc, char** argv)
             map = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
             if (map != MAP_FAILED) bed = map;
         }
-        if (map == MAP_FAILED) {   // not a regular file (or an empty one): read it
-            if (!read_all(fd, &data)) {
-                fprintf(stderr, "Error: reading %s failed (%s)\n", inputs[0].c_str(), strerror(errno));
-                return EIO;
-            }
-            bed = data.data();
-            n = data.size();
+        if (map == MAP_FAILED && !cli::read_all(fd, &data[0])) {   // not a regular file (or an empty one): read it
+            fprintf(stderr, "Error: reading %s failed (%s)\n", inputs[0].c_str(), strerror(errno));
+            return EIO;
         }
         close(fd);
-    } else {
-        for (const std::string& p : inputs) {
-            const int fd = p == "-" ? STDIN_FILENO : open(p.c_str(), O_RDONLY);
-            if (fd < 0) {
-                fprintf(stderr, "Error: Input file does not exist (%s)\n", p.c_str());
-                return ENODATA;
-            }
-            const size_t before = data.size();
-            const bool ok = read_all(fd, &data);
-            if (fd != STDIN_FILENO) close(fd);
-            if (!ok) {
-                fprintf(stderr, "Error: reading %s failed (%s)\n", p.c_str(), strerror(errno));
-                return EIO;
-            }
-            if (data.size() > before && data.back() != '\n') data.push_back('\n');
-        }
-        bed = data.data();
-        n = data.size();
+    } else if (const int e = cli::load_inputs(inputs, &data, true)) {
+        return e;
+    }
+    if (map == MAP_FAILED) {
+        bed = data[0].data();
+        n = data[0].size();
     }
 
     starch_ctx* ctx = nullptr;
-    int rc = starch_create(device, &ctx);
-    if (rc != STARCH_OK) {
-        fprintf(stderr, "Error: no GPU context (%s)\n", starch_strerror(rc));
-        return EINVAL;
-    }
+    if (const int e = cli::open_ctx(device, &ctx)) return e;
     if (check) {
         uint64_t line = 0;
-        rc = starch_sort_check_host(ctx, bed, n, &line);
+        const int rc = starch_sort_check_host(ctx, bed, n, &line);
         if (rc != STARCH_OK) {
             fprintf(stderr, "Error: %s (%s)\n", starch_last_error(ctx), starch_strerror(rc));
             starch_destroy(ctx);
@@ -162,27 +128,5 @@ int main(int argc, char** argv)
         starch_destroy(ctx);
         return line ? 1 : 0;
     }
-    rc = starch_sort_host(ctx, bed, n);
-    uint64_t bytes = 0;
-    std::vector<char> out;
-    if (rc == STARCH_OK) rc = starch_output_size(ctx, &bytes);
-    if (rc == STARCH_OK && bytes) {
-        out.resize(bytes);
-        rc = starch_output_copy(ctx, out.data(), bytes);
-    }
-    if (rc != STARCH_OK) {
-        fprintf(stderr, "Error: %s (%s)\n", starch_last_error(ctx), starch_strerror(rc));
-        starch_destroy(ctx);
-        return rc == STARCH_ERR_MEM ? ENOMEM : EINVAL;
-    }
-    for (uint64_t w = 0; w < bytes;) {
-        const size_t k = fwrite(out.data() + w, 1, bytes - w, stdout);
-        if (k == 0) break;
-        w += k;
-    }
-    const bool ok = fflush(stdout) == 0 && !ferror(stdout);
-    if (!ok) fprintf(stderr, "Error: writing the output failed (%s)\n", strerror(errno ? errno : EIO));
-    starch_destroy(ctx);
-    if (map != MAP_FAILED) munmap(map, n);
-    return ok ? 0 : EIO;
+    return cli::finish_output(ctx, starch_sort_host(ctx, bed, n), "Error: %s (%s)\n");
 }

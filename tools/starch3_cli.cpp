@@ -63,7 +63,7 @@
 #include <thread>
 #include <vector>
 
-#include "../include/starch_amd.h"
+#include "cli_common.hpp"
 
 static const char* kName = "starch3";
 static const char* kVersion = "0.1 (mi355x)";
@@ -226,16 +226,6 @@ struct PipeReader {
     }
 };
 
-static bool stdout_ok()
-{
-    if (fflush(stdout) != 0 || ferror(stdout)) {
-        fprintf(stderr, "Error: writing the archive failed (%s)\n", strerror(errno ? errno : EIO));
-        fflush(stderr);
-        return false;
-    }
-    return true;
-}
-
 static void print_stats(starch_ctx* ctx, std::chrono::steady_clock::time_point t0, uint64_t input_bytes)
 {
     const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -359,7 +349,7 @@ int main(int argc, char** argv)
             case 'b': ++methods; gzip = 0; break;
             case 'g': ++methods; gzip = 1; break;
             case 'h': usage(stdout); return 0;
-            case 'v': printf("%s\n  version: %s\n", kName, kVersion); return 0;
+            case 'v': cli::print_version(kName, kVersion); return 0;
             case '?': usage(stdout); return 0;
             case 'L': level = atoi(optarg); break;
             case 'I': emit_index = 0; break;
@@ -560,7 +550,7 @@ int main(int argc, char** argv)
                 fprintf(stderr, "Error: encode failed (%s: %s)\n", starch_strerror(rc), starch_last_error(ctx));
                 return rc == STARCH_ERR_MEM ? ENOMEM : EINVAL;
             }
-            if (!stdout_ok()) _exit(EIO);
+            if (!cli::stdout_ok("archive")) _exit(EIO);
             if (stats) {
                 starch_stats s;
                 starch_get_stats(ctx, &s);
@@ -707,7 +697,7 @@ int main(int argc, char** argv)
         for (auto* c : ctxs) starch_destroy(c);
         return rc == STARCH_ERR_MEM ? ENOMEM : EINVAL;
     }
-    if (!stdout_ok()) {
+    if (!cli::stdout_ok("archive")) {
         if (getenv("STARCH_CLI_TEARDOWN")) for (auto* c : ctxs) starch_destroy(c);
         _exit(EIO);
     }

@@ -22,7 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "../include/starch_amd.h"
+#include "cli_common.hpp"
 
 static const char* kName = "starchcat";
 static const char* kVersion = "0.1 (mi355x)";
@@ -47,16 +47,6 @@ static void usage(FILE* f)
             kName, kVersion);
 }
 
-static bool stdout_ok()
-{
-    if (fflush(stdout) != 0 || ferror(stdout)) {
-        fprintf(stderr, "Error: writing the archive failed (%s)\n", strerror(errno ? errno : EIO));
-        fflush(stderr);
-        return false;
-    }
-    return true;
-}
-
 int main(int argc, char** argv)
 {
     const char* note = nullptr;
@@ -79,7 +69,7 @@ int main(int argc, char** argv)
             case 'D': device = atoi(optarg); break;
             case 'S': stats = 1; break;
             case 'h': usage(stdout); return 0;
-            case 'v': printf("%s\n  version: %s\n", kName, kVersion); return 0;
+            case 'v': cli::print_version(kName, kVersion); return 0;
             default: usage(stderr); return EXIT_FAILURE;
         }
     }
@@ -145,17 +135,12 @@ int main(int argc, char** argv)
             }
             fputc('\n', stdout);
         }
-        return stdout_ok() ? 0 : EIO;
+        return cli::stdout_ok("archive") ? 0 : EIO;
     }
 
     starch_ctx* ctx = nullptr;
-    if (any_merge) {
-        rc = starch_create(device, &ctx);
-        if (rc != STARCH_OK) {
-            fprintf(stderr, "Error: no GPU context (%s)\n", starch_strerror(rc));
-            return EINVAL;
-        }
-    }
+    if (any_merge)
+        if (const int e = cli::open_ctx(device, &ctx)) return e;
     void* out = nullptr;
     uint64_t bytes = 0;
     rc = starch_cat_host(ctx, maps.data(), lens.data(), maps.size(), &opt, &out, &bytes);
@@ -166,7 +151,7 @@ int main(int argc, char** argv)
     }
     if (bytes) fwrite(out, 1, bytes, stdout);
     starch_free(out);
-    const bool ok = stdout_ok();
+    const bool ok = cli::stdout_ok("archive");
     if (ok && stats) {
         starch_cat_stats s;
         if (ctx && starch_cat_get_stats(ctx, &s) == STARCH_OK)

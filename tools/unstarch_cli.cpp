@@ -22,7 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "../include/starch_amd.h"
+#include "cli_common.hpp"
 
 static const char* kName = "unstarch";
 static const char* kVersion = "0.1 (mi355x)";
@@ -45,16 +45,6 @@ static void usage(FILE* f)
             "  --device N                GPU to decode on (default 0)\n"
             "  --help, --version\n",
             kName, kVersion);
-}
-
-static bool stdout_ok()
-{
-    if (fflush(stdout) != 0 || ferror(stdout)) {
-        fprintf(stderr, "Error: writing the output failed (%s)\n", strerror(errno ? errno : EIO));
-        fflush(stderr);
-        return false;
-    }
-    return true;
 }
 
 struct Query {
@@ -157,7 +147,7 @@ int main(int argc, char** argv)
             case 'u': mode = M_BASES_UNIQ; break;
             case 'D': device = atoi(optarg); break;
             case 'h': usage(stdout); return 0;
-            case 'v': printf("%s\n  version: %s\n", kName, kVersion); return 0;
+            case 'v': cli::print_version(kName, kVersion); return 0;
             default: usage(stderr); return EXIT_FAILURE;
         }
     }
@@ -242,33 +232,14 @@ int main(int argc, char** argv)
             }
             printf("%lld\n", sum);
         }
-        return stdout_ok() ? 0 : EIO;
+        return cli::stdout_ok("output") ? 0 : EIO;
     }
 
     starch_ctx* ctx = nullptr;
-    int rc = starch_create(device, &ctx);
-    if (rc != STARCH_OK) {
-        fprintf(stderr, "Error: no GPU context (%s)\n", starch_strerror(rc));
-        return EINVAL;
-    }
+    if (const int e = cli::open_ctx(device, &ctx)) return e;
     std::vector<starch_region> regions;
     for (const Query& q : queries)
         regions.push_back(starch_region{q.chr.data(), q.chr.size(), q.start, q.stop, q.whole ? 1 : 0});
-    rc = starch_extract_host(ctx, map, n, regions.data(), regions.size());
-    uint64_t bytes = 0;
-    std::vector<char> out;
-    if (rc == STARCH_OK) rc = starch_output_size(ctx, &bytes);
-    if (rc == STARCH_OK && bytes) {
-        out.resize(bytes);
-        rc = starch_output_copy(ctx, out.data(), bytes);
-    }
-    if (rc != STARCH_OK) {
-        fprintf(stderr, "Error: extraction failed (%s: %s)\n", starch_strerror(rc), starch_last_error(ctx));
-        starch_destroy(ctx);
-        return rc == STARCH_ERR_MEM ? ENOMEM : EINVAL;
-    }
-    if (bytes) fwrite(out.data(), 1, bytes, stdout);
-    const bool ok = stdout_ok();
-    starch_destroy(ctx);
-    return ok ? 0 : EIO;
+    return cli::finish_output(ctx, starch_extract_host(ctx, map, n, regions.data(), regions.size()),
+                              "Error: extraction failed (%2$s: %1$s)\n");
 }
