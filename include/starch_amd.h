@@ -739,6 +739,76 @@ int starch_map_get_stats(starch_ctx* ctx, starch_map_stats* out);
  * largest window, in elements, that is staged in LDS (0: there is no such path). */
 int starch_map_constants(uint32_t* tile_refs, uint32_t* lds_window);
 
+/* ---- closest-features: nearest query elements left and right ---------------------
+ * Two sorted BED inputs, both required: the reference is input 0, the query
+ * input 1.  Line validity, archive inputs and errors with their kinds, order and
+ * naming are those of starch_map_host: stop > start, each input in
+ * starch_sort_host's order, a last line without '\n' is a line, an empty input
+ * is valid, a bzip2-method archive is decoded in HBM and a gzip-method archive is
+ * STARCH_ERR_ARG.  Error texts begin "closest-features: input K, line N:".  2^32
+ * lines or more over both inputs is STARCH_ERR_ARG.
+ * Only lines of one chromosome relate to each other.  For a reference line
+ * r = (c, s, e) and a query line q = (c, a, b):
+ *   q overlaps r when a < e and b > s; then dist(q) = 0;
+ *   when b <= s, dist(q) = -(s - b + 1): an abutting element to the left is at -1;
+ *   when a >= e, dist(q) = a - e + 1: an abutting element to the right is at +1.
+ * The left candidates are the query lines on c with (a, b) < (s, e)
+ * lexicographically, as numbers; the right candidates those with
+ * (a, b) >= (s, e), so a query line equal to the reference line is a right
+ * candidate.  Every query line on c is a candidate on exactly one side; a left
+ * candidate is never to the right of r and a right candidate never to its left.
+ * With no_overlaps, overlapping lines are removed from both sides.
+ *   left(r)   the left candidate with the greatest dist (the one nearest 0);
+ *             ties go to the last in the query's order;
+ *   right(r)  the right candidate with the least dist; ties go to the first in
+ *             the query's order.
+ * Either is NA when its side has no candidate; a chromosome the query lacks gives
+ * NA on both sides.  With closest, the one of the two with the smaller |dist| is
+ * kept, a tie goes to the left, an NA side loses to the other, and two NA give NA.
+ * The output (starch_output_size / _copy / _device) is one line per reference
+ * line, in reference order, its fields joined by delim (1 to 8 bytes;
+ * closest-features' default is "|"), then '\n':
+ *   the reference line, every column, without its '\n', unless no_ref is set;
+ *   the left element: the query line's bytes, every column, or NA;
+ *   with dist, the left element's distance as a signed decimal (-12, 0, 7), or NA;
+ *   the same two fields for the right element.
+ * With closest there is one element and one distance instead of two.  Distances
+ * are exact for coordinates up to 2^63-1.
+ * This is a definition by sets, modelled on BEDOPS' closest-features for
+ * --closest, --dist, --no-overlaps, --no-ref and --delim, but it is unverified
+ * against a BEDOPS binary.
+ * Errors leave no output.  A NULL context, input or options, an empty or
+ * over-long delimiter and a flag other than 0 or 1 are STARCH_ERR_ARG, answered
+ * before anything touches a device. */
+typedef struct {
+    uint32_t closest;        /* 0 or 1: keep the nearer of left and right */
+    uint32_t dist;           /* 0 or 1: a distance field after every element */
+    uint32_t no_overlaps;    /* 0 or 1: overlapping query lines are no candidates */
+    uint32_t no_ref;         /* 0 or 1: leave out the reference line */
+    uint32_t delim_len;      /* 1 to 8 */
+    char delim[8];
+} starch_closest_options;
+int starch_closest_host(starch_ctx* ctx, const starch_setop_input* ref, const starch_setop_input* query,
+                        const starch_closest_options* opt);
+/* BED text only, back to back in HBM: the reference is d_bed[offs[0], offs[1]),
+ * the query d_bed[offs[1], offs[2]) (offs: three host values, not decreasing). */
+int starch_closest_device(starch_ctx* ctx, const void* d_bed, const uint64_t* offs, const starch_closest_options* opt);
+typedef struct {
+    uint64_t n_ref, n_query;   /* lines */
+    uint64_t n_chromosomes;    /* over both inputs */
+    uint64_t stops_sorted;     /* 1: a query line is nested in another (with no_overlaps the stops were then sorted) */
+    uint64_t left_na, right_na;   /* reference lines without a left / right element, before closest chooses */
+    uint64_t lines_out, output_bytes;
+    /* ms_decode (upload and archive decode) and ms_total are host clock, the others GPU events */
+    float ms_decode, ms_parse, ms_build, ms_query, ms_format, ms_total;
+} starch_closest_stats;
+/* Of the last successful starch_closest_* call on this context. */
+int starch_closest_get_stats(starch_ctx* ctx, starch_closest_stats* out);
+/* Sizes the kernels switch on: reference lines per query workgroup, and the
+ * fan-out of the hierarchy of maxima over the query stops (stops per tile, and
+ * tiles per tile of the level above). */
+int starch_closest_constants(uint32_t* tile_refs, uint32_t* fanout);
+
 int starch_output_size(starch_ctx* ctx, uint64_t* n);
 int starch_output_copy(starch_ctx* ctx, void* dst, uint64_t cap);
 int starch_output_device(starch_ctx* ctx, const void** d_ptr);

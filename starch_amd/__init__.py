@@ -18,7 +18,7 @@ import os
 __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_archive", "plan_units", "assign_shards",
            "archive_layout", "compress_multi", "Unit", "Segment", "Comm", "gather_host", "MAGIC", "HG38", "HG38_LEN",
            "list_archive", "cat_plan", "cat_host", "sort_constants", "setop_constants", "SETOPS",
-           "map_constants", "MAPCOLS", "BEDOPS_OPS", "bedops_constants"]
+           "map_constants", "MAPCOLS", "BEDOPS_OPS", "bedops_constants", "closest_constants"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STARCH_AMD_LIB") or os.path.join(_HERE, "_build", "libstarch_amd.so")
@@ -161,6 +161,19 @@ class MapStats(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("ms_decode", "ms_parse", "ms_build", "ms_query", "ms_format", "ms_total")]
 
 
+class ClosestOptions(ctypes.Structure):
+    """starch_closest_options: the flags and delimiter of closest_features()."""
+    _fields_ = [("closest", ctypes.c_uint32), ("dist", ctypes.c_uint32), ("no_overlaps", ctypes.c_uint32),
+                ("no_ref", ctypes.c_uint32), ("delim_len", ctypes.c_uint32), ("delim", ctypes.c_char * 8)]
+
+
+class ClosestStats(ctypes.Structure):
+    """starch_closest_stats: the last closest_features()."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_ref", "n_query", "n_chromosomes", "stops_sorted", "left_na", "right_na",
+                                               "lines_out", "output_bytes")] + \
+               [(n, ctypes.c_float) for n in ("ms_decode", "ms_parse", "ms_build", "ms_query", "ms_format", "ms_total")]
+
+
 class SortStats(ctypes.Structure):
     """starch_sort_stats: the last sort_bed / sort_check / compress_sorted."""
     _fields_ = [(n, ctypes.c_uint64) for n in ("input_bytes", "n_lines", "n_chromosomes", "already_sorted",
@@ -286,6 +299,11 @@ def load():
         "starch_map_device": ([vp, vp, pu64, u64, ctypes.POINTER(MapOptions)], ctypes.c_int),
         "starch_map_get_stats": ([vp, ctypes.POINTER(MapStats)], ctypes.c_int),
         "starch_map_constants": ([ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+        "starch_closest_host": ([vp, ctypes.POINTER(SetopInput), ctypes.POINTER(SetopInput),
+                                 ctypes.POINTER(ClosestOptions)], ctypes.c_int),
+        "starch_closest_device": ([vp, vp, pu64, ctypes.POINTER(ClosestOptions)], ctypes.c_int),
+        "starch_closest_get_stats": ([vp, ctypes.POINTER(ClosestStats)], ctypes.c_int),
+        "starch_closest_constants": ([ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
         "starch_output_size": ([vp, pu64], ctypes.c_int),
         "starch_output_copy": ([vp, vp, u64], ctypes.c_int),
         "starch_output_device": ([vp, ctypes.POINTER(vp)], ctypes.c_int),
@@ -807,6 +825,45 @@ class Starch:
         _check(self._L.starch_map_get_stats(self._h, ctypes.byref(s)), self._h)
         return {k: getattr(s, k) for k, _ in MapStats._fields_}
 
+    # ---- closest-features ----
+    def closest_features(self, ref, query, closest=False, dist=False, no_overlaps=False, no_ref=False, delim=b"|") -> bytes:
+        """closest-features: one line per line of the sorted reference ``ref``:
+        the line itself (unless ``no_ref``), then the nearest line of the
+        sorted ``query`` to its left and the nearest to its right (``NA`` where
+        a side has none), joined by ``delim``.  With ``dist`` every element is
+        followed by its signed distance (0: it overlaps), with ``no_overlaps``
+        overlapping lines are not considered, with ``closest`` only the nearer
+        of the two is written (a tie goes to the left).  Either input is BED
+        text or an archive.  The definitions are in include/starch_amd.h.  A
+        malformed or unsorted line is StarchError -12 naming input (ref 0,
+        query 1) and line; a bad argument is -2."""
+        o = _closest_options(closest, dist, no_overlaps, no_ref, delim)
+        r = SetopInput(bytes(ref), len(ref))
+        q = SetopInput(bytes(query), len(query))
+        _check(self._L.starch_closest_host(self._h, ctypes.byref(r), ctypes.byref(q), ctypes.byref(o)), self._h)
+        return self._output()
+
+    def closest_device(self, d_ptr: int, offs, closest=False, dist=False, no_overlaps=False, no_ref=False, delim=b"|") -> int:
+        """The same for BED text in HBM: the reference at d_ptr + [offs[0],
+        offs[1]), the query at d_ptr + [offs[1], offs[2]); returns the output
+        size (output_device_ptr())."""
+        o = _closest_options(closest, dist, no_overlaps, no_ref, delim)
+        offs = [int(x) for x in offs]
+        if len(offs) != 3:
+            raise ValueError("closest_device: offs holds three values")
+        a = (ctypes.c_uint64 * 3)(*offs)
+        _check(self._L.starch_closest_device(self._h, ctypes.c_void_p(d_ptr), a, ctypes.byref(o)), self._h)
+        k = ctypes.c_uint64()
+        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
+        return k.value
+
+    def closest_stats(self) -> dict:
+        """Of the last closest_features(): n_ref / n_query / n_chromosomes /
+        stops_sorted / left_na / right_na / lines_out / output_bytes / ms_*."""
+        s = ClosestStats()
+        _check(self._L.starch_closest_get_stats(self._h, ctypes.byref(s)), self._h)
+        return {k: getattr(s, k) for k, _ in ClosestStats._fields_}
+
     def cat(self, archives) -> bytes:
         """starchcat: the archives (bytes, in order) merged into one, with this
         instance's note, block_size_100k and base_counts.  A chromosome held
@@ -892,6 +949,27 @@ def _map_options(cols, range_, skip_unmapped, delim):
     o.skip_unmapped = 1 if skip_unmapped else 0
     o.delim_len = len(delim)
     ctypes.memmove(ctypes.addressof(o) + MapOptions.delim.offset, delim, min(len(delim), 8))
+    return o
+
+
+def closest_constants():
+    """(reference lines per query workgroup, fan-out of the hierarchy of maxima
+    over the query stops) of closest-features' kernels; no GPU needed."""
+    a, b = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(load().starch_closest_constants(ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def _closest_options(closest, dist, no_overlaps, no_ref, delim):
+    """starch_closest_options; the delimiter's length is left to the library."""
+    delim = bytes(delim)
+    o = ClosestOptions()
+    o.closest = 1 if closest else 0
+    o.dist = 1 if dist else 0
+    o.no_overlaps = 1 if no_overlaps else 0
+    o.no_ref = 1 if no_ref else 0
+    o.delim_len = len(delim)
+    ctypes.memmove(ctypes.addressof(o) + ClosestOptions.delim.offset, delim, min(len(delim), 8))
     return o
 
 

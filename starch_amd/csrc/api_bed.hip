@@ -1,4 +1,4 @@
-// starch_amd/csrc/api_bed.hip -- the C ABI of sort-bed, bedops and bedmap.
+// starch_amd/csrc/api_bed.hip -- the C ABI of sort-bed, bedops, bedmap and closest-features.
 #include <string.h>
 
 #include <algorithm>
@@ -436,6 +436,101 @@ int starch_map_constants(uint32_t* tile_refs, uint32_t* lds_window)
 {
     if (tile_refs) *tile_refs = (uint32_t)bm::kTileRefs;
     if (lds_window) *lds_window = bm::kLdsWindow;
+    return STARCH_OK;
+}
+
+}  // extern "C"
+
+// ---- closest-features (include/starch_amd.h; kernels in bed_closest.hip) -----------
+namespace {
+bool closest_options_ok(const starch_closest_options* o, bc::ClosestOptions* out)
+{
+    if (!o || o->delim_len < 1 || o->delim_len > 8) return false;
+    if (o->closest > 1 || o->dist > 1 || o->no_overlaps > 1 || o->no_ref > 1) return false;
+    out->closest = o->closest;
+    out->dist = o->dist;
+    out->no_overlaps = o->no_overlaps;
+    out->no_ref = o->no_ref;
+    out->delim_len = o->delim_len;
+    memcpy(out->delim, o->delim, o->delim_len);
+    return true;
+}
+
+void closest_run(starch_ctx* c, const bc::ClosestOptions& opt, uint64_t len, const std::vector<uint64_t>& in_end,
+                 double ms_decode, const std::chrono::steady_clock::time_point& t0)
+{
+    bc::ClosestResult r;
+    c->closer.run(c->sorter, c->setop, opt, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, c->st, c->setop_out, r);
+    starch_closest_stats& s = c->kstats;
+    s = starch_closest_stats{};
+    s.n_ref = r.n_ref;
+    s.n_query = r.n_query;
+    s.n_chromosomes = r.n_chromosomes;
+    s.stops_sorted = r.stops_sorted;
+    s.left_na = r.left_na;
+    s.right_na = r.right_na;
+    s.lines_out = r.lines_out;
+    s.output_bytes = r.out_bytes;
+    s.ms_decode = (float)ms_decode;
+    s.ms_parse = r.ms_parse;
+    s.ms_build = r.ms_build;
+    s.ms_query = r.ms_query;
+    s.ms_format = r.ms_format;
+    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->have_kstats = true;
+    publish(c, c->setop_out, r.out_bytes);
+}
+}  // namespace
+
+extern "C" {
+
+int starch_closest_host(starch_ctx* c, const starch_setop_input* ref, const starch_setop_input* query,
+                        const starch_closest_options* opt)
+{
+    bc::ClosestOptions co;
+    if (!c || !ref || !query || !closest_options_ok(opt, &co)) return STARCH_ERR_ARG;
+    if ((ref->len && !ref->data) || (query->len && !query->data)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_kstats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    const starch_setop_input inputs[2] = {*ref, *query};
+    std::vector<uint64_t> in_end;
+    const uint64_t len = setop_load_host(c, inputs, 2, "closest-features", in_end, nullptr);
+    const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    closest_run(c, co, len, in_end, ms_decode, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_closest_device(starch_ctx* c, const void* d_bed, const uint64_t* offs, const starch_closest_options* opt)
+{
+    bc::ClosestOptions co;
+    if (!c || !offs || !closest_options_ok(opt, &co)) return STARCH_ERR_ARG;
+    if (!offs_ok(d_bed, offs, 2)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_kstats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> in_end;
+    const uint64_t len = setop_load_device(c, d_bed, offs, 2, in_end);
+    closest_run(c, co, len, in_end, 0.0, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_closest_get_stats(starch_ctx* c, starch_closest_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_kstats) return STARCH_ERR_STATE;
+    *out = c->kstats;
+    return STARCH_OK;
+}
+
+int starch_closest_constants(uint32_t* tile_refs, uint32_t* fanout)
+{
+    if (tile_refs) *tile_refs = (uint32_t)bc::kTileRefs;
+    if (fanout) *fanout = bc::kFanout;
     return STARCH_OK;
 }
 

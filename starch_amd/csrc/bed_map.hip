@@ -38,55 +38,19 @@
 
 #include "../../include/starch_amd.h"
 #include "bed_map.hpp"
+#include "bed_search.hpp"
 #include "seg_max.hpp"
 
 namespace bm {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kBoundsThreads;
 enum : int { S_BYTES = 0, S_KEPT, S_COUNT = 4 };   // device scalars (u64)
 enum : uint32_t { W_COUNT = 1, W_BASES = 2, W_UNIQ = 4 };
 
 inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return (unsigned)ceil_div(items, per_block); }
 
-// first index in [lo, hi) with v[index] >= x (hi: none)
-__device__ __forceinline__ uint64_t lower(const uint64_t* __restrict__ v, uint64_t lo, uint64_t hi, uint64_t x)
-{
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (v[mid] < x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// first index in [lo, hi) with v[index] > x
-__device__ __forceinline__ uint64_t upper(const uint64_t* __restrict__ v, uint64_t lo, uint64_t hi, uint64_t x)
-{
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (v[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // ---- 2. map arrays ------------------------------------------------------------------
-// lo[c], c in [0, C]: the first of n ordered ranks that is >= c
-__global__ void __launch_bounds__(kThreads)
-k_bm_bounds(const uint32_t* __restrict__ rank, uint64_t n, uint64_t C, uint64_t* __restrict__ lo_out)
-{
-    const uint64_t c = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (c > C) return;
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint64_t mid = lo + ((hi - lo) >> 1);
-        if (rank[mid] < c) lo = mid + 1;
-        else hi = mid;
-    }
-    lo_out[c] = lo;
-}
-
 __global__ void __launch_bounds__(kThreads)
 k_bm_gather(const uint32_t* __restrict__ idx, const uint64_t* __restrict__ v, uint64_t n, uint64_t* __restrict__ out)
 {

@@ -24,6 +24,7 @@
 #include "sort_bed.hpp"
 #include "bed_setops.hpp"
 #include "bed_map.hpp"
+#include "bed_closest.hpp"
 #include "transform.hpp"
 #include "untransform.hpp"
 
@@ -223,6 +224,10 @@ struct starch_ctx {
     bm::MapWorkspace mapper;
     starch_map_stats mstats{};       // the last starch_map_* call
     bool have_mstats = false;
+    // closest-features (bed_closest.hip): reads setop_in, writes setop_out
+    bc::ClosestWorkspace closer;
+    starch_closest_stats kstats{};   // the last starch_closest_* call
+    bool have_kstats = false;
     std::string err;
     // last result
     bool have = false;
