@@ -856,10 +856,18 @@ __global__ void k_fb_heads(const uint32_t* __restrict__ key, const uint64_t* __r
     if (mixed[(uint32_t)hp[i]] == stamp && key[i] != key[i - 1]) head[i] = 1;
 }
 
+// A block of ONE byte value of mainSort's size (nblock >= 10000,
+// bz:blocksort.c:1055) never reaches fallbackSort: every rotation lies in the
+// big bucket [ss][ss], mainSort has no small bucket to sort, so its budget
+// stays whole, and its copy loops do not run (the case its assertion 1007
+// allows): ptr[i] = i as the bucket fill left it, origPtr = 0.  (Any other
+// periodic block has small buckets of equal rotations, which exhaust the
+// budget.)
 __global__ void k_fb_origptr(const uint32_t* __restrict__ fmap, BlockDesc* __restrict__ blocks, uint32_t b, uint32_t n)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && fmap[i] == 0) blocks[b].orig_ptr = i;
+    const bool main_sorted = blocks[b].n_in_use == 1 && n >= 10000;
+    if (i < n && fmap[i] == 0) blocks[b].orig_ptr = main_sorted ? 0u : i;
 }
 
 void launch_bwt(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blkbytes, uint64_t stride,

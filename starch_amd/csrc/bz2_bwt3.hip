@@ -15,11 +15,12 @@
 // segmented sort of (block, 64-bit key) pairs, done for ALL blocks of a batch
 // at once:
 //
-//   k3_pss      packed symbol stream (PSS) of every block: its symbols as
+//   k3_pss_hist packed symbol stream (PSS) of every block: its symbols as
 //               B-bit fields, MSB first, in u64 words, wrapped past the end;
 //               the key of rotation r is bits [rB, rB+KB) -- two word loads
-//               and a shift, so keys are never stored
-//   k3_hist     per 32k-rotation tile: 4096-bucket histogram of the top 12 bits
+//               and a shift, so keys are never stored; and, from the same
+//               registers, per 32k-rotation tile the 4096-bucket histogram
+//               of the top 12 bits
 //   k3_scan     per block: bucket starts, per-tile cursors, size-class lists
 //   k3_scatter_lds  rotations -> bucket order in SA, staged in LDS.  Persistent,
 //               per-XCD queues: each XCD streams ITS blocks one at a time, so
@@ -401,54 +402,6 @@ __device__ __forceinline__ void load_qsizes_binned(const Ctx& c, uint32_t* qs)
     __syncthreads();
 }
 
-// ---------------------------------------------------------------------------
-// k3_pss: packed symbol stream; also the block's key geometry and nInUse
-// ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k3_pss(Ctx c)
-{
-    __shared__ uint8_t sym[256];
-    const uint32_t slot = blockIdx.y, b = c.b0 + slot;
-    const uint32_t n = c.blocks[b].n;
-    uint32_t nin;
-    load_sym(c.blocks[b], sym, &nin);
-    const uint32_t B = nin > 1 ? (uint32_t)bits_for3(nin - 1) : 1u;
-    const uint32_t nw = (uint32_t)(((uint64_t)(n + 128) * B + 63) / 64 + 1);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        Geo g;
-        g.B = B;
-        g.D = 64 / B;
-        g.KB = g.D * B;
-        g.Dp = (64 - PDIG) / B;
-        g.nin = nin;
-        g.D1 = (c.nbins == PNB_WIDE && B == 5 && nin <= 20) ? 3u : 0u;
-        g.SH = g.D1 ? 3 * B : PDIG;
-        g.pad = 0;
-        c.L.geo[slot] = g;
-        c.blocks[b].n_in_use = nin;
-    }
-    __syncthreads();
-    const uint32_t w = blockIdx.x * 256 + threadIdx.x;
-    if (w >= nw) return;
-    const uint8_t* blk = c.blkbytes + (uint64_t)b * c.stride;
-    const uint64_t bit0 = (uint64_t)w * 64;
-    const uint64_t j0 = bit0 / B, j1 = (bit0 + 63) / B;
-    uint64_t word = 0;
-    if (B == 4 && j1 < n) {                      // 16 whole symbols: one aligned 16-B load
-        const uint4 v = *reinterpret_cast<const uint4*>(blk + j0);
-        const uint32_t q[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 16; ++k) word = (word << 4) | sym[(q[k >> 2] >> (8 * (k & 3))) & 0xffu];
-        c.scr.K[(uint64_t)slot * c.scr.stride + w] = word;
-        return;
-    }
-    for (uint64_t j = j0; j <= j1; ++j) {
-        const uint64_t s = sym[blk[j < n ? j : j % n]];
-        const int sh = 64 - (int)B - (int)(j * B - bit0);
-        word |= sh >= 0 ? (s << sh) : (s >> (-sh));
-    }
-    c.scr.K[(uint64_t)slot * c.scr.stride + w] = word;
-}
-
 // tile cursors / totals live in K after the PSS
 __device__ __forceinline__ uint32_t* tile_hist(const Ctx& c, uint32_t slot)
 {
@@ -456,38 +409,138 @@ __device__ __forceinline__ uint32_t* tile_hist(const Ctx& c, uint32_t slot)
 }
 
 // ---------------------------------------------------------------------------
-// k3_hist: per-tile bucket histogram -> thist[slot][tile][NB]
+// k3_pss_hist: the packed symbol stream and the per-tile bucket histogram
+// (-> thist[slot][tile][NB]) in one pass over the block bytes; also the
+// block's key geometry and nInUse (tile 0).
+//
+// The unit of work is a group of 64 consecutive rotations: their symbols are
+// exactly B PSS words (so a tile, PTILE / 64 groups, owns whole words), built
+// in registers, stored, and funnel-shifted for the 64 top-level digits without
+// reading the PSS back.  The digits of a group's last rotations reach up to 15
+// bits into the next group, so a group also packs the first ceil(16 / B)
+// symbols after it.  A group whose 80 bytes lie inside the block takes five
+// 16-byte loads; the block's last groups read byte by byte, wrapped mod n.
+// The workgroup of a block's last tile also writes the wrapped tail of the
+// PSS ((n + 128) * B bits plus one word, which the key loads of the last
+// rotations read).  B is a template parameter of the group code: every shift
+// and word index below is a constant.
 // ---------------------------------------------------------------------------
+constexpr uint32_t PGRP = 64;           // rotations per group
+static_assert(PTILE % PGRP == 0, "tiles own whole groups, groups own whole PSS words");
+
+template <int B>
+__device__ __forceinline__ void pss_hist_group(const uint8_t* __restrict__ blk, const uint8_t* sym, uint32_t n,
+                                               uint32_t g, uint32_t nw, uint64_t* __restrict__ pss, uint32_t* cnt,
+                                               Geo geo)
+{
+    constexpr int NTAIL = (16 + B - 1) / B;         // symbols after the group a digit can reach
+    constexpr int NRAW = (int)(PGRP + 16) / 4;      // the group's bytes and the 16 after it, as u32
+    static_assert(NTAIL <= 16, "the tail symbols come from one more 16-byte load");
+    const uint32_t j0 = g * PGRP;
+    uint32_t raw[NRAW];
+    if (j0 + PGRP + 16 <= n) {
+        const uint4* q = reinterpret_cast<const uint4*>(blk + j0);
+        const uint4 v0 = q[0], v1 = q[1], v2 = q[2], v3 = q[3], v4 = q[4];
+        raw[0] = v0.x; raw[1] = v0.y; raw[2] = v0.z; raw[3] = v0.w;
+        raw[4] = v1.x; raw[5] = v1.y; raw[6] = v1.z; raw[7] = v1.w;
+        raw[8] = v2.x; raw[9] = v2.y; raw[10] = v2.z; raw[11] = v2.w;
+        raw[12] = v3.x; raw[13] = v3.y; raw[14] = v3.z; raw[15] = v3.w;
+        raw[16] = v4.x; raw[17] = v4.y; raw[18] = v4.z; raw[19] = v4.w;
+    } else {                                        // positions at or past n wrap
+        uint32_t jj = j0 < n ? j0 : j0 % n;
+#pragma unroll
+        for (int i = 0; i < NRAW; ++i) {
+            uint32_t x = 0;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                if (4 * i + t < (int)PGRP + NTAIL) {
+                    x |= (uint32_t)blk[jj] << (8 * t);
+                    jj = jj + 1 == n ? 0u : jj + 1;
+                }
+            }
+            raw[i] = x;
+        }
+    }
+    uint64_t w[B + 1];
+#pragma unroll
+    for (int i = 0; i <= B; ++i) w[i] = 0;
+#pragma unroll
+    for (int k = 0; k < (int)PGRP + NTAIL; ++k) {    // symbol k at bits [k * B, k * B + B), MSB first
+        const uint64_t sy = sym[(raw[k >> 2] >> (8 * (k & 3))) & 0xffu];
+        const int bit = k * B, ix = bit >> 6, sh = 64 - B - (bit & 63);
+        if (sh >= 0) {
+            w[ix] |= sy << sh;
+        } else {
+            w[ix] |= sy >> (-sh);
+            if (ix < B) w[ix + 1] |= sy << (64 + sh);
+        }
+    }
+    const uint32_t w0 = g * B;
+    if (w0 + B <= nw) {
+#pragma unroll
+        for (int i = 0; i < B; ++i) pss[w0 + i] = w[i];
+    } else {
+#pragma unroll
+        for (int i = 0; i < B; ++i)
+            if (w0 + i < nw) pss[w0 + i] = w[i];
+    }
+    if (j0 >= n) return;                            // the wrapped tail holds no rotations
+    geo.B = B;
+#pragma unroll
+    for (int k = 0; k < (int)PGRP; ++k) {
+        const int bit = k * B, ix = bit >> 6, p = bit & 63;
+        const uint64_t v = (w[ix] << p) | ((w[ix + 1] >> 1) >> (63 - p));
+        if (j0 + k < n) atomicAdd(&cnt[top_digit(v, geo)], 1u);
+    }
+}
+
 template <int NB>
-__global__ void __launch_bounds__(PT) k3_hist(Ctx c)
+__global__ void __launch_bounds__(PT) k3_pss_hist(Ctx c)
 {
     __shared__ uint32_t cnt[NB];
+    __shared__ uint8_t sym[256];
     const uint32_t slot = blockIdx.y, b = c.b0 + slot, tile = blockIdx.x;
     const uint32_t n = c.blocks[b].n;
+    // every workgroup derives the block's geometry itself (it waits on no
+    // other); tile 0 publishes it for k3_scan and everything after
+    uint32_t nin;
+    load_sym(c.blocks[b], sym, &nin);
+    Geo geo;
+    geo.B = nin > 1 ? (uint32_t)bits_for3(nin - 1) : 1u;
+    geo.D = 64 / geo.B;
+    geo.KB = geo.D * geo.B;
+    geo.Dp = (64 - PDIG) / geo.B;
+    geo.nin = nin;
+    geo.D1 = (c.nbins == PNB_WIDE && geo.B == 5 && nin <= 20) ? 3u : 0u;
+    geo.SH = geo.D1 ? 3 * geo.B : PDIG;
+    geo.pad = 0;
+    if (tile == 0 && threadIdx.x == 0) {
+        c.L.geo[slot] = geo;
+        c.blocks[b].n_in_use = nin;
+    }
     const uint32_t t0 = tile * PTILE;
     if (t0 >= n) return;
-    const Geo geo = c.L.geo[slot];
-    const uint32_t B = geo.B;
-    const uint64_t* pss = c.scr.K + (uint64_t)slot * c.scr.stride;
     for (int i = threadIdx.x; i < NB; i += PT) cnt[i] = 0;
     __syncthreads();
-    const uint32_t e = n - t0 < (uint32_t)PTILE ? n - t0 : (uint32_t)PTILE;
-    // 16 consecutive rotations per thread and step: their top-level digits all
-    // come from four PSS words (funnel shifts), not two loads per rotation
-    for (uint32_t k0 = threadIdx.x * 16u; k0 < e; k0 += PT * 16u) {
-        const uint64_t bit0 = (uint64_t)(t0 + k0) * B;
-        const uint64_t q0 = bit0 >> 6;
-        const uint32_t p0 = (uint32_t)(bit0 & 63u);
-        const uint64_t w[4] = {pss[q0], pss[q0 + 1], pss[q0 + 2], pss[q0 + 3]};
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const uint32_t bit = p0 + (uint32_t)k * B;      // < 64 + 15 * 8
-            const uint32_t ix = bit >> 6, p = bit & 63u;
-            const uint64_t a = ix == 0 ? w[0] : ix == 1 ? w[1] : w[2];
-            const uint64_t nx = ix == 0 ? w[1] : ix == 1 ? w[2] : w[3];
-            const uint64_t v = (a << p) | ((nx >> 1) >> (63u - p));
-            if (k0 + k < e) atomicAdd(&cnt[top_digit(v, geo)], 1u);
-        }
+    const uint32_t B = geo.B;
+    const uint32_t nw = (uint32_t)(((uint64_t)(n + 128) * B + 63) / 64 + 1);
+    const uint32_t g0 = tile * (PTILE / PGRP);
+    const uint32_t g1 = n - t0 <= (uint32_t)PTILE ? (nw + B - 1) / B : g0 + PTILE / PGRP;
+    const uint8_t* blk = c.blkbytes + (uint64_t)b * c.stride;
+    uint64_t* pss = c.scr.K + (uint64_t)slot * c.scr.stride;
+    auto run = [&](auto bc) {
+        for (uint32_t g = g0 + threadIdx.x; g < g1; g += PT)
+            pss_hist_group<decltype(bc)::value>(blk, sym, n, g, nw, pss, cnt, geo);
+    };
+    switch (B) {
+    case 1: run(std::integral_constant<int, 1>{}); break;
+    case 2: run(std::integral_constant<int, 2>{}); break;
+    case 3: run(std::integral_constant<int, 3>{}); break;
+    case 4: run(std::integral_constant<int, 4>{}); break;
+    case 5: run(std::integral_constant<int, 5>{}); break;
+    case 6: run(std::integral_constant<int, 6>{}); break;
+    case 7: run(std::integral_constant<int, 7>{}); break;
+    default: run(std::integral_constant<int, 8>{}); break;
     }
     __syncthreads();
     uint32_t* th = tile_hist(c, slot) + (uint64_t)tile * NB;
@@ -3249,13 +3302,11 @@ bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blk
     // ---- round 0: packed prefix keys gathered from the PSS by every sort, as
     // the text rounds do ----
     {
-        const uint32_t maxw = (uint32_t)pss_words(scr.stride);
-        hipLaunchKernelGGL(k3_pss, dim3((maxw + 255) / 256, nb), dim3(256), 0, st, c);
         if (wide) {
-            hipLaunchKernelGGL(k3_hist<PNB_WIDE>, dim3(MAXT, nb), dim3(PT), 0, st, c);
+            hipLaunchKernelGGL(k3_pss_hist<PNB_WIDE>, dim3(MAXT, nb), dim3(PT), 0, st, c);
             hipLaunchKernelGGL(k3_scan<PNB_WIDE>, dim3(nb), dim3(ST), 0, st, c);
         } else {
-            hipLaunchKernelGGL(k3_hist<PNB>, dim3(MAXT, nb), dim3(PT), 0, st, c);
+            hipLaunchKernelGGL(k3_pss_hist<PNB>, dim3(MAXT, nb), dim3(PT), 0, st, c);
             hipLaunchKernelGGL(k3_scan<PNB>, dim3(nb), dim3(ST), 0, st, c);
         }
         uint32_t* head;

@@ -153,13 +153,18 @@ __device__ __forceinline__ void put_run(Out8& out, uint32_t z)   // bijective ba
     }
 }
 
-// ---- alphabets <= 32: five launches over (block, 512-symbol chunk) ----
+// ---- alphabets <= 32: five launches fused to three, over (block, 512-symbol chunk) ----
+// (tests/test_out8_host.py cuts this source at the opening words of the line
+// above.)  k_mtf_pre reads every chunk once for its local recency list and its
+// zero-run summary, k_mtf_scan composes both per block, k_mtf_emit re-runs the
+// MTF and writes the values.
 // Per-chunk state lives in the (free) key scratch of the block's batch slot:
-//   [0, SW*C)          local recency list + set    (k_mtf_local)
-//   [SW*C, (SW+LW)*C)  start list of the chunk     (k_mtf_scan_lists)
-//   then RunSum (2 words) and (zeros carried in, output offset) (1 word)
-// (u64 words, C = chunks per slot).  The three chunk passes are flat grids,
-// so every CU has work whatever the block count; the two scans are one
+//   [0, SW*C)          local recency list + set    (k_mtf_pre)
+//   [SW*C, (SW+LW)*C)  start list of the chunk     (k_mtf_scan)
+//   then RunSum (2 words, k_mtf_pre) and (zeros carried in, output offset)
+//   (1 word, k_mtf_scan)
+// (u64 words, C = chunks per slot).  The two chunk passes are flat grids,
+// so every CU has work whatever the block count; the scan is one
 // workgroup per block over <= 2 chunks per thread.  The list lives in
 // registers: 16 nibbles of a u64 for <= 16 symbols (NibP, BED3 text), 32
 // bytes in three / four u64 for 17..24 / 25..30 symbols (ByteP<3> / ByteP<4>, narrowPeak and other BED6+
@@ -174,13 +179,8 @@ struct NibP {
     using List = uint64_t;
     static constexpr uint32_t LO = 1, HI = 16;        // nInUse range handled
     static constexpr uint32_t SW = 2, LW = 1;         // u64 words per State / List
-    static constexpr uint32_t IXB = 4;                // bits per stored MTF index (k_mtf_runs -> k_mtf_emit)
     // nibble MTF is cheap: k_mtf_emit re-runs it from the last column (storing
     // the indices measured slower: the stores queue behind the chunk's loads)
-#ifndef STARCH_NIB_SIX
-#define STARCH_NIB_SIX 0
-#endif
-    static constexpr bool SIX = STARCH_NIB_SIX != 0;
     __device__ static State empty() { State r; r.list = 0; r.set = 0; r.cnt = 0; return r; }
     __device__ static void add(State& st, uint32_t s)
     {
@@ -217,14 +217,8 @@ struct ByteP {
     // counts mtfFreq itself (k_tables reads the counts k_mtf_big leaves)
     static constexpr uint32_t LO = NW == 3 ? 17 : 25, HI = NW == 3 ? 24 : 30;
     static constexpr uint32_t SW = 5, LW = 4;
-    static constexpr uint32_t IXB = 8;
-    // the zero runs from neighbour compares (k_mtf_runs) and the byte-list MTF
-    // run once, in k_mtf_emit (STARCH_BYTE_SIX=1: k_mtf_runs runs the MTF and
-    // stores the indices, k_mtf_emit reads them)
-#ifndef STARCH_BYTE_SIX
-#define STARCH_BYTE_SIX 0
-#endif
-    static constexpr bool SIX = STARCH_BYTE_SIX != 0;
+    // the zero runs come from neighbour compares (k_mtf_pre) and the byte-list
+    // MTF runs once, in k_mtf_emit
     __device__ static void put(uint64_t* w, uint32_t i, uint32_t s)
     {
         const uint32_t j = i >> 3, sh = 8 * (i & 7);
@@ -310,8 +304,6 @@ struct MtfScr {
     __device__ typename P::List* l0() const { return reinterpret_cast<typename P::List*>(base + (uint64_t)P::SW * C); }
     __device__ RunSum* rs() const { return reinterpret_cast<RunSum*>(base + (uint64_t)(P::SW + P::LW) * C); }
     __device__ uint2* zo() const { return reinterpret_cast<uint2*>(base + (uint64_t)(P::SW + P::LW + 2) * C); }
-    // the MTF indices of the whole block (P::IXB bits each, chunk c at c * cs symbols)
-    __device__ uint8_t* ix() const { return reinterpret_cast<uint8_t*>(base + (uint64_t)(P::SW + P::LW + 3) * C); }
 };
 
 template <class P>
@@ -326,33 +318,8 @@ __device__ __forceinline__ MtfScr<P> mtf_scr(uint64_t* K, uint64_t kstride, uint
 template <class P>
 __device__ __forceinline__ bool mtf_mine(uint32_t nin) { return nin >= P::LO && nin <= P::HI; }
 
-// visit symbols [a, e) of a chunk in order: 16-byte pieces, the next piece's
-// load issued before the current one is processed (one load in flight, few
-// registers: the per-symbol chains stay short-lived); the final partial
-// piece is bounds-tested
-template <class F>
-__device__ __forceinline__ void visit_chunk(const uint8_t* ll, uint32_t a, uint32_t e, F&& f)
-{
-    const uint4* q = reinterpret_cast<const uint4*>(ll + a);
-    const uint32_t np = (e - a + 15) / 16;
-    uint4 cur = q[0];
-#pragma unroll 1
-    for (uint32_t i = 0; i < np; ++i) {
-        const uint4 nxt = q[i + 1 < np ? i + 1 : i];
-        const uint32_t lim = e - a - 16 * i;
-        if (lim >= 16) {
-            auto all = [&](int, uint32_t s) { f(s); };
-            piece<true>(cur, 0, all);
-        } else {
-            auto some = [&](int k, uint32_t s) { if ((uint32_t)k < lim) f(s); };
-            piece<true>(cur, 0, some);
-        }
-        cur = nxt;
-    }
-}
-
-// the same, whole 128-byte lines at a time (eight loads in flight): faster
-// for the emit pass, whose branchy per-symbol code keeps few values live
+// visit symbols [a, e) of a chunk in order, whole 128-byte lines at a time
+// (eight loads in flight); the final partial line is bounds-tested
 template <class F>
 __device__ __forceinline__ void visit_chunk_lines(const uint8_t* ll, uint32_t a, uint32_t e, F&& f)
 {
@@ -365,10 +332,12 @@ __device__ __forceinline__ void visit_chunk_lines(const uint8_t* ll, uint32_t a,
     }
 }
 
+// One pass over each chunk's lines: its zero-run summary, then its local
+// recency state while the lines are still in cache.
 template <class P>
-__global__ void __launch_bounds__(MCT) k_mtf_local(const BlockDesc* __restrict__ blocks, uint32_t b0,
-                                                   const uint8_t* __restrict__ LL, uint64_t ll_stride,
-                                                   uint64_t* __restrict__ K, uint64_t kstride, uint32_t C, uint32_t cs)
+__global__ void __launch_bounds__(MCT) k_mtf_pre(const BlockDesc* __restrict__ blocks, uint32_t b0,
+                                                 const uint8_t* __restrict__ LL, uint64_t ll_stride,
+                                                 uint64_t* __restrict__ K, uint64_t kstride, uint32_t C, uint32_t cs)
 {
     const uint32_t slot = blockIdx.y, b = b0 + slot;
     const uint32_t n = blocks[b].n, nin = blocks[b].n_in_use;
@@ -377,8 +346,31 @@ __global__ void __launch_bounds__(MCT) k_mtf_local(const BlockDesc* __restrict__
     if (!mtf_mine<P>(nin) || a >= n) return;
     const uint32_t e = a + cs < n ? a + cs : n;
     const uint8_t* ll = LL + (uint64_t)slot * ll_stride;
+    const MtfScr<P> ms = mtf_scr<P>(K, kstride, slot, C);
+    // An MTF index is 0 exactly when the symbol equals the one before it
+    // (the list's front is the last symbol coded; the block's first symbol
+    // meets the initial list, whose front is symbol 0), so the zero runs --
+    // all the run summary needs -- come from comparing neighbours, without
+    // the move-to-front chain (k_mtf_emit runs that once)
+    uint32_t z = 0, nz = 0, lz = 0, inner = 0;
+    uint32_t prev = a ? ll[a - 1] : 0u;
+    visit_chunk_lines(ll, a, e, [&](uint32_t s) {
+        const uint32_t nzf = s != prev ? 1u : 0u;
+        prev = s;
+        inner += (nzf & nz) ? 1u + (31u - __clz(z + 1u)) : 0u;
+        lz = (nzf & (nz ^ 1u)) ? z : lz;
+        nz |= nzf;
+        z = nzf ? 0u : z + 1u;
+    });
+    RunSum r;
+    r.nz = nz;
+    r.lz = nz ? lz : z;
+    r.tz = nz ? z : 0u;
+    r.inner = inner;
+    ms.rs()[ch] = r;
     // local(c): the chunk's symbols by last occurrence, most recent first;
-    // backward, line by line, until every symbol of the block has been seen
+    // backward from the line the forward pass ended on, line by line, until
+    // every symbol of the block has been seen
     typename P::State loc = P::empty();
     const uint32_t full = a + ((e - a) & ~(LINE - 1));
     auto add = [&](uint32_t s) { P::add(loc, s); };
@@ -391,16 +383,20 @@ __global__ void __launch_bounds__(MCT) k_mtf_local(const BlockDesc* __restrict__
         j0 -= LINE;
         visit_line<false>(ll + j0, [&](int, uint32_t s) { add(s); });
     }
-    mtf_scr<P>(K, kstride, slot, C).st()[ch] = loc;
+    ms.st()[ch] = loc;
 }
 
-// start list of every chunk: exclusive scan of the local-list composition
+// Both exclusive scans of a block, over the same per-thread chunk ranges:
+// the local-list composition gives every chunk's start list; the run
+// summaries give the zeros carried into each chunk and its first output
+// index, and the block's trailing run, EOB and n_mtf
 template <class P>
-__global__ void __launch_bounds__(MST) k_mtf_scan_lists(const BlockDesc* __restrict__ blocks, uint32_t b0,
-                                                        uint64_t* __restrict__ K, uint64_t kstride, uint32_t C,
-                                                        uint32_t cs)
+__global__ void __launch_bounds__(MST) k_mtf_scan(BlockDesc* __restrict__ blocks, uint32_t b0,
+                                                  uint64_t* __restrict__ K, uint64_t kstride, uint32_t C, uint32_t cs,
+                                                  uint16_t* __restrict__ mtfv_all, uint64_t mtf_stride)
 {
     __shared__ typename P::State sh[MST];
+    __shared__ RunSum shr[MST];
     const int tid = threadIdx.x;
     const uint32_t slot = blockIdx.x, b = b0 + slot;
     const uint32_t n = blocks[b].n, nin = blocks[b].n_in_use;
@@ -410,150 +406,42 @@ __global__ void __launch_bounds__(MST) k_mtf_scan_lists(const BlockDesc* __restr
     const MtfScr<P> ms = mtf_scr<P>(K, kstride, slot, C);
     const uint32_t c0 = tid * per;
     typename P::State agg = P::empty();
+    RunSum ragg;
+    ragg.nz = 0; ragg.lz = 0; ragg.tz = 0; ragg.inner = 0;
     for (uint32_t q = 0; q < per; ++q)
-        if (c0 + q < nch) agg = P::compose(agg, ms.st()[c0 + q]);
+        if (c0 + q < nch) {
+            agg = P::compose(agg, ms.st()[c0 + q]);
+            ragg = run_compose(ragg, ms.rs()[c0 + q]);
+        }
     sh[tid] = agg;
+    shr[tid] = ragg;
     __syncthreads();
-    for (int d = 1; d < MST; d <<= 1) {                 // inclusive scan of the composition
+    for (int d = 1; d < MST; d <<= 1) {                 // inclusive scans of the two compositions
         const typename P::State v = (tid >= d) ? P::compose(sh[tid - d], sh[tid]) : sh[tid];
+        const RunSum rv = (tid >= d) ? run_compose(shr[tid - d], shr[tid]) : shr[tid];
         __syncthreads();
         sh[tid] = v;
+        shr[tid] = rv;
         __syncthreads();
     }
     typename P::State st = P::identity(nin);
-    if (tid) st = P::compose(st, sh[tid - 1]);
+    RunSum ex;
+    ex.nz = 0; ex.lz = 0; ex.tz = 0; ex.inner = 0;
+    if (tid) {
+        st = P::compose(st, sh[tid - 1]);
+        ex = shr[tid - 1];
+    }
     for (uint32_t q = 0; q < per; ++q) {
         if (c0 + q >= nch) break;
         ms.l0()[c0 + q] = P::list_of(st);
         st = P::compose(st, ms.st()[c0 + q]);
-    }
-}
-
-// MTF of each chunk: its indices, stored for k_mtf_emit (P::IXB bits each,
-// one store per 16 symbols), and their zero-run summary (branch-free per symbol)
-template <class P>
-__global__ void __launch_bounds__(MCT) k_mtf_runs(const BlockDesc* __restrict__ blocks, uint32_t b0,
-                                                  const uint8_t* __restrict__ LL, uint64_t ll_stride,
-                                                  uint64_t* __restrict__ K, uint64_t kstride, uint32_t C, uint32_t cs)
-{
-    const uint32_t slot = blockIdx.y, b = b0 + slot;
-    const uint32_t n = blocks[b].n, nin = blocks[b].n_in_use;
-    const uint32_t ch = blockIdx.x * MCT + threadIdx.x;
-    const uint32_t a = ch * cs;
-    if (!mtf_mine<P>(nin) || a >= n) return;
-    const uint32_t e = a + cs < n ? a + cs : n;
-    const MtfScr<P> ms = mtf_scr<P>(K, kstride, slot, C);
-    uint32_t z = 0, nz = 0, lz = 0, inner = 0;
-    if constexpr (!P::SIX) {
-        // An MTF index is 0 exactly when the symbol equals the one before it
-        // (the list's front is the last symbol coded; the block's first symbol
-        // meets the initial list, whose front is symbol 0), so the zero runs --
-        // all the run summary needs -- come from comparing neighbours, without
-        // the move-to-front chain (k_mtf_emit runs that once)
-        const uint8_t* ll = LL + (uint64_t)slot * ll_stride;
-        uint32_t prev = a ? ll[a - 1] : 0u;
-        visit_chunk_lines(ll, a, e, [&](uint32_t s) {
-            const uint32_t nzf = s != prev ? 1u : 0u;
-            prev = s;
-            inner += (nzf & nz) ? 1u + (31u - __clz(z + 1u)) : 0u;
-            lz = (nzf & (nz ^ 1u)) ? z : lz;
-            nz |= nzf;
-            z = nzf ? 0u : z + 1u;
-        });
-        RunSum r;
-        r.nz = nz;
-        r.lz = nz ? lz : z;
-        r.tz = nz ? z : 0u;
-        r.inner = inner;
-        ms.rs()[ch] = r;
-        return;
-    }
-    typename P::List L = ms.l0()[ch];
-    uint8_t* ixp = ms.ix() + (uint64_t)a * P::IXB / 8;     // 16 symbols = 8 (IXB 4) or 16 (IXB 8) bytes
-    // indices enter at the top of a 64-bit (IXB 4) / 128-bit (IXB 8) shift
-    // register; after 16 symbols the first sits in the lowest bits
-    uint64_t lo = 0, hi = 0;
-    uint32_t k16 = 0, piece_no = 0;
-    visit_chunk(LL + (uint64_t)slot * ll_stride, a, e, [&](uint32_t s) {
-        const uint32_t x = P::mtf(L, s);
-        if constexpr (P::IXB == 4) {
-            lo = (lo >> 4) | ((uint64_t)x << 60);
-        } else {
-            lo = (lo >> 8) | (hi << 56);
-            hi = (hi >> 8) | ((uint64_t)x << 56);
-        }
-        if (P::SIX && ++k16 == 16) {
-            if constexpr (P::IXB == 4) reinterpret_cast<uint64_t*>(ixp)[piece_no] = lo;
-            else reinterpret_cast<uint4*>(ixp)[piece_no] = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32),
-                                                                      (uint32_t)hi, (uint32_t)(hi >> 32));
-            k16 = 0;
-            ++piece_no;
-        }
-        const uint32_t nzf = x != 0 ? 1u : 0u;
-        inner += (nzf & nz) ? 1u + (31u - __clz(z + 1u)) : 0u;
-        lz = (nzf & (nz ^ 1u)) ? z : lz;
-        nz |= nzf;
-        z = nzf ? 0u : z + 1u;
-    });
-    if (P::SIX && k16) {                                 // partial last piece: align its first symbol to bit 0
-        const uint32_t sh = (16 - k16) * P::IXB;
-        if constexpr (P::IXB == 4) {
-            reinterpret_cast<uint64_t*>(ixp)[piece_no] = lo >> sh;
-        } else {
-            const uint64_t l2 = sh >= 64 ? hi >> (sh - 64) : ((lo >> sh) | (hi << (64 - sh)));
-            const uint64_t h2 = sh >= 64 ? 0 : hi >> sh;
-            reinterpret_cast<uint4*>(ixp)[piece_no] = make_uint4((uint32_t)l2, (uint32_t)(l2 >> 32), (uint32_t)h2,
-                                                                 (uint32_t)(h2 >> 32));
-        }
-    }
-    RunSum r;
-    r.nz = nz;
-    r.lz = nz ? lz : z;
-    r.tz = nz ? z : 0u;
-    r.inner = inner;
-    ms.rs()[ch] = r;
-}
-
-// exclusive scan of the run summaries: zeros carried into each chunk and its
-// first output index; the block's trailing run, EOB and n_mtf
-template <class P>
-__global__ void __launch_bounds__(MST) k_mtf_scan_runs(BlockDesc* __restrict__ blocks, uint32_t b0,
-                                                       uint64_t* __restrict__ K, uint64_t kstride, uint32_t C,
-                                                       uint32_t cs, uint16_t* __restrict__ mtfv_all, uint64_t mtf_stride)
-{
-    __shared__ RunSum sh[MST];
-    const int tid = threadIdx.x;
-    const uint32_t slot = blockIdx.x, b = b0 + slot;
-    const uint32_t n = blocks[b].n, nin = blocks[b].n_in_use;
-    if (!mtf_mine<P>(nin)) return;
-    const uint32_t nch = (n + cs - 1) / cs;
-    const uint32_t per = (nch + MST - 1) / MST;
-    const MtfScr<P> ms = mtf_scr<P>(K, kstride, slot, C);
-    const uint32_t c0 = tid * per;
-    RunSum agg;
-    agg.nz = 0; agg.lz = 0; agg.tz = 0; agg.inner = 0;
-    for (uint32_t q = 0; q < per; ++q)
-        if (c0 + q < nch) agg = run_compose(agg, ms.rs()[c0 + q]);
-    sh[tid] = agg;
-    __syncthreads();
-    for (int d = 1; d < MST; d <<= 1) {
-        const RunSum v = (tid >= d) ? run_compose(sh[tid - d], sh[tid]) : sh[tid];
-        __syncthreads();
-        sh[tid] = v;
-        __syncthreads();
-    }
-    RunSum ex;
-    ex.nz = 0; ex.lz = 0; ex.tz = 0; ex.inner = 0;
-    if (tid) ex = sh[tid - 1];
-    for (uint32_t q = 0; q < per; ++q) {
-        if (c0 + q >= nch) break;
         const uint32_t zin = ex.nz ? ex.tz : ex.lz;
         const uint32_t obase = ex.nz ? nsym_run(ex.lz) + 1 + ex.inner : 0;
         ms.zo()[c0 + q] = make_uint2(zin, obase);
         ex = run_compose(ex, ms.rs()[c0 + q]);
     }
     if (tid == MST - 1) {
-        const RunSum T = sh[MST - 1];
+        const RunSum T = shr[MST - 1];
         uint8_t* mtfv = reinterpret_cast<uint8_t*>(mtfv_all + (uint64_t)b * mtf_stride);   // u8 values
         uint32_t z = T.nz ? T.tz : T.lz;
         uint32_t o = T.nz ? nsym_run(T.lz) + 1 + T.inner : 0;
@@ -567,8 +455,8 @@ __global__ void __launch_bounds__(MST) k_mtf_scan_runs(BlockDesc* __restrict__ b
     }
 }
 
-// emit each chunk's RUNA/RUNB + symbols at its offset, from the MTF indices
-// k_mtf_runs stored
+// emit each chunk's RUNA/RUNB + symbols at its offset: the MTF re-run from
+// the chunk's start list
 template <class P>
 __global__ void __launch_bounds__(MCT) k_mtf_emit(const BlockDesc* __restrict__ blocks, uint32_t b0,
                                                   const uint8_t* __restrict__ LL, uint64_t ll_stride,
@@ -595,33 +483,8 @@ __global__ void __launch_bounds__(MCT) k_mtf_emit(const BlockDesc* __restrict__ 
             z = 0;
         }
     };
-    if constexpr (!P::SIX) {                           // re-run the MTF from the chunk's start list
-        typename P::List L = ms.l0()[ch];
-        visit_chunk_lines(LL + (uint64_t)slot * ll_stride, a, e, [&](uint32_t s) { f(P::mtf(L, s)); });
-        out.flush();
-        return;
-    }
-    // one 16-B piece (32 or 16 indices) at a time, the next piece's load in flight
-    constexpr uint32_t SPP = 128 / P::IXB;             // symbols per 16-B piece
-    const uint4* q = reinterpret_cast<const uint4*>(ms.ix() + (uint64_t)a * P::IXB / 8);
-    const uint32_t cnt = e - a, np = (cnt + SPP - 1) / SPP;
-    uint4 cur = q[0];
-#pragma unroll 1
-    for (uint32_t i = 0; i < np; ++i) {
-        const uint4 nxt = q[i + 1 < np ? i + 1 : i];
-        const uint32_t wv[4] = {cur.x, cur.y, cur.z, cur.w};
-        const uint32_t lim = cnt - i * SPP;
-        if (lim >= SPP) {
-#pragma unroll
-            for (uint32_t k = 0; k < SPP; ++k)
-                f(P::IXB == 4 ? (wv[k >> 3] >> (4 * (k & 7))) & 15u : (wv[k >> 2] >> (8 * (k & 3))) & 255u);
-        } else {
-#pragma unroll
-            for (uint32_t k = 0; k < SPP; ++k)
-                if (k < lim) f(P::IXB == 4 ? (wv[k >> 3] >> (4 * (k & 7))) & 15u : (wv[k >> 2] >> (8 * (k & 3))) & 255u);
-        }
-        cur = nxt;
-    }
+    typename P::List L = ms.l0()[ch];
+    visit_chunk_lines(LL + (uint64_t)slot * ll_stride, a, e, [&](uint32_t s) { f(P::mtf(L, s)); });
     out.flush();
 }
 
@@ -847,11 +710,8 @@ void launch_mtf(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blkb
     const dim3 gch((C + MCT - 1) / MCT, nb);
     auto run = [&](auto pol) {
         using P = decltype(pol);
-        hipLaunchKernelGGL(k_mtf_local<P>, gch, dim3(MCT), 0, st, blocks, b0, scr.LL, scr.stride, scr.K, kstride, C, cs);
-        hipLaunchKernelGGL(k_mtf_scan_lists<P>, dim3(nb), dim3(MST), 0, st, blocks, b0, scr.K, kstride, C, cs);
-        hipLaunchKernelGGL(k_mtf_runs<P>, gch, dim3(MCT), 0, st, blocks, b0, scr.LL, scr.stride, scr.K, kstride, C,
-                           cs);
-        hipLaunchKernelGGL(k_mtf_scan_runs<P>, dim3(nb), dim3(MST), 0, st, blocks, b0, scr.K, kstride, C, cs, mtfv,
+        hipLaunchKernelGGL(k_mtf_pre<P>, gch, dim3(MCT), 0, st, blocks, b0, scr.LL, scr.stride, scr.K, kstride, C, cs);
+        hipLaunchKernelGGL(k_mtf_scan<P>, dim3(nb), dim3(MST), 0, st, blocks, b0, scr.K, kstride, C, cs, mtfv,
                            mtf_stride);
         hipLaunchKernelGGL(k_mtf_emit<P>, gch, dim3(MCT), 0, st, blocks, b0, scr.LL, scr.stride, scr.K, kstride, C,
                            cs, mtfv, mtf_stride);

@@ -446,7 +446,7 @@ __global__ void __launch_bounds__(T32) __attribute__((amdgpu_waves_per_eu(STARCH
     const uint32_t b = b0 + blockIdx.x;
     const int32_t alpha = (int32_t)blocks[b].n_in_use + 2;
     if (alpha > 32) return;                        // uniform: k_tables handles it
-    // alphabets <= 32: the MTF values are bytes (k_mtf_emit / k_mtf_scan_runs)
+    // alphabets <= 32: the MTF values are bytes (k_mtf_emit / k_mtf_scan)
     const uint8_t* mtfv = reinterpret_cast<const uint8_t*>(mtfv_all + (uint64_t)b * mtf_stride);
     uint8_t* sel = sel_all + (uint64_t)b * (2 * kMaxSelectors);
     uint8_t* selmtf = sel + kMaxSelectors;
