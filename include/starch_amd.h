@@ -809,6 +809,107 @@ int starch_closest_get_stats(starch_ctx* ctx, starch_closest_stats* out);
  * tiles per tile of the level above). */
 int starch_closest_constants(uint32_t* tile_refs, uint32_t* fanout);
 
+/* ---- convert2bed: GFF3, GTF, VCF and WIG to BED ----------------------------------
+ * Text in one of four formats becomes BED lines, one thread per input line, and
+ * unless no_sort is set the lines then go through starch_sort_device unchanged,
+ * without leaving HBM.  The definitions are modelled on BEDOPS' convert2bed but
+ * are unverified against a BEDOPS binary; the known differences are marked (*).
+ * Framing.  The input is cut into lines at '\n'; a last line without '\n' is a
+ * line; '\r' is an ordinary byte.  Fields of GFF, GTF and VCF are separated by
+ * TAB.  A coordinate is 1 to 19 ASCII digits with a value up to 2^63-1, as in
+ * starch_sort_host, and is written as a plain decimal number.
+ * Header lines.  An empty line and a line that begins with '#' are header lines;
+ * in WIG also a line whose first token is track or browser.  They are dropped,
+ * or with keep_header header line K (from 0, in input order) becomes
+ *   _header TAB K TAB K+1 TAB <the line>
+ * which the sort then orders as a chromosome named _header.
+ * Errors.  Any other line that does not fit its format is STARCH_ERR_DATA: the
+ * text is "convert2bed: line N: <what is wrong>" for the lowest such line (from
+ * 1), and there is no output.
+ *   gff   A line that is exactly ##FASTA ends the input: it and everything after
+ *         it is ignored and is no header.  A record has exactly 9 fields, a
+ *         non-empty first one, field 4 the start >= 1 and field 5 the end >=
+ *         start.  Output: seqid, start-1, end, ID, score, strand, source, type,
+ *         phase, attributes.  ID is the value of the first ';'-separated piece
+ *         of the attributes that begins with ID=, up to the next ';'; '.' when
+ *         there is none or the value is empty.  (*) BEDOPS adds a
+ *         zero_length_insertion=True attribute when start equals end.
+ *   gtf   As gff, without the ##FASTA rule.  ID is the value inside the first
+ *         gene_id "..." whose gene_id stands at the start of the attributes or
+ *         directly after ';' or a space; '.' when there is none, when it has no
+ *         closing quote or when the value is empty.  (*) BEDOPS refuses a record
+ *         without gene_id.
+ *   vcf   A record has 8 or more fields, a non-empty CHROM, POS >= 1 and
+ *         non-empty REF and ALT.  start = POS-1 and stop = start + len(REF): the
+ *         REF-length rule (*: BEDOPS' rule has changed between releases); a stop
+ *         above 2^63-1 is an error.  With STARCH_VCF_ALL one line per record:
+ *         CHROM, start, stop, ID, QUAL, REF, ALT, FILTER, INFO, and every field
+ *         after INFO unchanged.  With STARCH_VCF_SNVS, _INSERTIONS or _DELETIONS,
+ *         ALT is split at ',' and one line is written per allele of the class, in
+ *         allele order, its ALT column holding that allele alone: an snv has
+ *         len(allele) == len(REF), an insertion is longer, a deletion shorter.  A
+ *         record without such an allele writes nothing; an empty allele is an
+ *         error.
+ *   wig   Tokens are separated by runs of spaces and TABs.  A declaration is
+ *         variableStep chrom=C [span=N] or fixedStep chrom=C start=N [step=N]
+ *         [span=N], keys in any order; span and step default to 1; start, step
+ *         and span are 1 to 2^63-1.  A missing or empty chrom, a missing start,
+ *         a repeated key and an unknown key are errors.  A data line has 1, 2 or
+ *         4 tokens.  pos score (pos >= 1) is valid only under variableStep:
+ *         C, pos-1, pos-1+span.  score alone is valid only under fixedStep: the
+ *         k-th such line since the declaration (k from 0) gives C,
+ *         start-1+k*step, start-1+k*step+span.  chrom start stop score is valid
+ *         anywhere, needs stop > start and is copied with its coordinates
+ *         unchanged.  Every data line is named id-N, N its number among the data
+ *         lines of the input from 1 (4-token lines count towards N, not towards
+ *         k).  Output: chrom, start, stop, id-N, score.  (*) The score is copied
+ *         byte for byte; BEDOPS re-parses it and prints it with %f.  A data line
+ *         before any declaration (but for the 4-token form), one that does not
+ *         fit the declaration in force, any other token count and a coordinate
+ *         that would exceed 2^63-1 are errors on that line.
+ * 2^32 input lines or more, or 2^32 output lines or more, is STARCH_ERR_ARG.  A
+ * NULL context or options, an unknown format or class and a class other than
+ * STARCH_VCF_ALL with a format other than VCF are STARCH_ERR_ARG, answered
+ * before anything touches a device. */
+#define STARCH_CONVERT_GFF 0
+#define STARCH_CONVERT_GTF 1
+#define STARCH_CONVERT_VCF 2
+#define STARCH_CONVERT_WIG 3
+#define STARCH_VCF_ALL 0
+#define STARCH_VCF_SNVS 1
+#define STARCH_VCF_INSERTIONS 2
+#define STARCH_VCF_DELETIONS 3
+typedef struct {
+    uint32_t format;         /* STARCH_CONVERT_* */
+    uint32_t vcf_class;      /* STARCH_VCF_* */
+    uint32_t keep_header;    /* header lines become _header lines */
+    uint32_t no_sort;        /* leave the lines in input order */
+} starch_convert_options;
+/* The BED is read through starch_output_size / _copy / _device. */
+int starch_convert_host(starch_ctx* ctx, const void* data, uint64_t n, const starch_convert_options* opt);
+int starch_convert_device(starch_ctx* ctx, const void* d_data, uint64_t n, const starch_convert_options* opt);
+/* Convert, sort (copt->no_sort is STARCH_ERR_ARG) and encode from the sorted bytes
+ * while they are in HBM, as starch_sort_encode_host chains sort and encode: the
+ * archive is read as after starch_encode_host, the sorted BED through
+ * starch_output_*.  sopt == NULL: the defaults. */
+int starch_convert_encode_host(starch_ctx* ctx, const void* data, uint64_t n, const starch_convert_options* copt,
+                               const starch_options* sopt);
+typedef struct {
+    uint64_t input_bytes, input_lines;   /* every line, those after ##FASTA too */
+    uint64_t header_lines, data_lines;   /* before ##FASTA; data lines: records, WIG data lines */
+    uint64_t declarations;               /* WIG */
+    uint64_t lines_out, output_bytes;
+    uint64_t sorted;                     /* 1: the sort ran */
+    /* GPU events; ms_total is host clock and holds the upload too */
+    float ms_frame, ms_parse, ms_write, ms_sort, ms_total;
+} starch_convert_stats;
+/* Of the last successful starch_convert_* call on this context. */
+int starch_convert_get_stats(starch_ctx* ctx, starch_convert_stats* out);
+/* Sizes the kernels switch on: threads per block of the per-line kernels (one
+ * line each), and the bytes from which a copied tail (attributes, INFO and the
+ * sample columns, a kept header line) is left to a whole wave. */
+int starch_convert_constants(uint32_t* block_lines, uint32_t* wave_copy_bytes);
+
 int starch_output_size(starch_ctx* ctx, uint64_t* n);
 int starch_output_copy(starch_ctx* ctx, void* dst, uint64_t cap);
 int starch_output_device(starch_ctx* ctx, const void** d_ptr);

@@ -18,7 +18,8 @@ import os
 __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_archive", "plan_units", "assign_shards",
            "archive_layout", "compress_multi", "Unit", "Segment", "Comm", "gather_host", "MAGIC", "HG38", "HG38_LEN",
            "list_archive", "cat_plan", "cat_host", "sort_constants", "setop_constants", "SETOPS",
-           "map_constants", "MAPCOLS", "BEDOPS_OPS", "bedops_constants", "closest_constants"]
+           "map_constants", "MAPCOLS", "BEDOPS_OPS", "bedops_constants", "closest_constants",
+           "convert_constants", "CONVERT_FORMATS", "VCF_CLASSES", "ConvertOptions", "ConvertStats"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STARCH_AMD_LIB") or os.path.join(_HERE, "_build", "libstarch_amd.so")
@@ -174,6 +175,23 @@ class ClosestStats(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("ms_decode", "ms_parse", "ms_build", "ms_query", "ms_format", "ms_total")]
 
 
+CONVERT_FORMATS = {"gff": 0, "gtf": 1, "vcf": 2, "wig": 3}                       # STARCH_CONVERT_*
+VCF_CLASSES = {"all": 0, "snvs": 1, "insertions": 2, "deletions": 3}              # STARCH_VCF_*
+
+
+class ConvertOptions(ctypes.Structure):
+    """starch_convert_options: the format, VCF class and flags of convert()."""
+    _fields_ = [("format", ctypes.c_uint32), ("vcf_class", ctypes.c_uint32), ("keep_header", ctypes.c_uint32),
+                ("no_sort", ctypes.c_uint32)]
+
+
+class ConvertStats(ctypes.Structure):
+    """starch_convert_stats: the last convert()."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("input_bytes", "input_lines", "header_lines", "data_lines", "declarations",
+                                               "lines_out", "output_bytes", "sorted")] + \
+               [(n, ctypes.c_float) for n in ("ms_frame", "ms_parse", "ms_write", "ms_sort", "ms_total")]
+
+
 class SortStats(ctypes.Structure):
     """starch_sort_stats: the last sort_bed / sort_check / compress_sorted."""
     _fields_ = [(n, ctypes.c_uint64) for n in ("input_bytes", "n_lines", "n_chromosomes", "already_sorted",
@@ -304,6 +322,12 @@ def load():
         "starch_closest_device": ([vp, vp, pu64, ctypes.POINTER(ClosestOptions)], ctypes.c_int),
         "starch_closest_get_stats": ([vp, ctypes.POINTER(ClosestStats)], ctypes.c_int),
         "starch_closest_constants": ([ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+        "starch_convert_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(ConvertOptions)], ctypes.c_int),
+        "starch_convert_device": ([vp, vp, u64, ctypes.POINTER(ConvertOptions)], ctypes.c_int),
+        "starch_convert_encode_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(ConvertOptions), ctypes.POINTER(Options)],
+                                       ctypes.c_int),
+        "starch_convert_get_stats": ([vp, ctypes.POINTER(ConvertStats)], ctypes.c_int),
+        "starch_convert_constants": ([ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
         "starch_output_size": ([vp, pu64], ctypes.c_int),
         "starch_output_copy": ([vp, vp, u64], ctypes.c_int),
         "starch_output_device": ([vp, ctypes.POINTER(vp)], ctypes.c_int),
@@ -864,6 +888,42 @@ class Starch:
         _check(self._L.starch_closest_get_stats(self._h, ctypes.byref(s)), self._h)
         return {k: getattr(s, k) for k, _ in ClosestStats._fields_}
 
+    # ---- convert2bed ----
+    def convert(self, data: bytes, fmt: str, vcf_class="all", keep_header=False, sort=True) -> bytes:
+        """convert2bed: text in format ``fmt`` (a name of CONVERT_FORMATS: GFF3,
+        GTF, VCF or WIG) -> BED, in sort_bed()'s order unless ``sort`` is
+        False.  ``vcf_class`` (a name of VCF_CLASSES, vcf only) splits ALT and
+        keeps the alleles of one class; ``keep_header`` turns header lines
+        into ``_header`` lines instead of dropping them.  The definitions are
+        in include/starch_amd.h.  A line that does not fit its format is
+        StarchError -12 naming its number; a bad argument is -2."""
+        o = _convert_options(fmt, vcf_class, keep_header, sort)
+        _check(self._L.starch_convert_host(self._h, data, len(data), ctypes.byref(o)), self._h)
+        return self._output()
+
+    def convert_device(self, d_ptr: int, n: int, fmt: str, vcf_class="all", keep_header=False, sort=True) -> int:
+        """The same for text in HBM; returns the output size (output_device_ptr())."""
+        o = _convert_options(fmt, vcf_class, keep_header, sort)
+        _check(self._L.starch_convert_device(self._h, ctypes.c_void_p(d_ptr), n, ctypes.byref(o)), self._h)
+        k = ctypes.c_uint64()
+        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
+        return k.value
+
+    def compress_converted(self, data: bytes, fmt: str, vcf_class="all", keep_header=False, emit_index=True) -> bytes:
+        """convert, sort and compress without leaving HBM: the archive
+        compress(convert(data, fmt, ...)) gives."""
+        o = _convert_options(fmt, vcf_class, keep_header, True)
+        so = self._opts(emit_index)
+        _check(self._L.starch_convert_encode_host(self._h, data, len(data), ctypes.byref(o), ctypes.byref(so)), self._h)
+        return self.archive()
+
+    def convert_stats(self) -> dict:
+        """Of the last convert(): input_bytes / input_lines / header_lines /
+        data_lines / declarations / lines_out / output_bytes / sorted / ms_*."""
+        s = ConvertStats()
+        _check(self._L.starch_convert_get_stats(self._h, ctypes.byref(s)), self._h)
+        return {k: getattr(s, k) for k, _ in ConvertStats._fields_}
+
     def cat(self, archives) -> bytes:
         """starchcat: the archives (bytes, in order) merged into one, with this
         instance's note, block_size_100k and base_counts.  A chromosome held
@@ -970,6 +1030,29 @@ def _closest_options(closest, dist, no_overlaps, no_ref, delim):
     o.no_ref = 1 if no_ref else 0
     o.delim_len = len(delim)
     ctypes.memmove(ctypes.addressof(o) + ClosestOptions.delim.offset, delim, min(len(delim), 8))
+    return o
+
+
+def convert_constants():
+    """(threads per block of convert2bed's per-line kernels, bytes from which a
+    copied tail is left to a whole wave); no GPU needed."""
+    a, b = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(load().starch_convert_constants(ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def _convert_options(fmt, vcf_class, keep_header, sort):
+    """starch_convert_options; unknown names are ValueError, their combination is left to the library."""
+    fmt = fmt.lower() if isinstance(fmt, str) else fmt
+    if fmt not in CONVERT_FORMATS:
+        raise ValueError("convert: fmt must be one of %s" % ", ".join(CONVERT_FORMATS))
+    if vcf_class not in VCF_CLASSES:
+        raise ValueError("convert: vcf_class must be one of %s" % ", ".join(VCF_CLASSES))
+    o = ConvertOptions()
+    o.format = CONVERT_FORMATS[fmt]
+    o.vcf_class = VCF_CLASSES[vcf_class]
+    o.keep_header = 1 if keep_header else 0
+    o.no_sort = 0 if sort else 1
     return o
 
 

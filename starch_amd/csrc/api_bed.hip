@@ -1,4 +1,4 @@
-// starch_amd/csrc/api_bed.hip -- the C ABI of sort-bed, bedops, bedmap and closest-features.
+// starch_amd/csrc/api_bed.hip -- the C ABI of sort-bed, bedops, bedmap, closest-features and convert2bed.
 #include <string.h>
 
 #include <algorithm>
@@ -531,6 +531,110 @@ int starch_closest_constants(uint32_t* tile_refs, uint32_t* fanout)
 {
     if (tile_refs) *tile_refs = (uint32_t)bc::kTileRefs;
     if (fanout) *fanout = bc::kFanout;
+    return STARCH_OK;
+}
+
+}  // extern "C"
+
+// ---- convert2bed (include/starch_amd.h; kernels in bed_convert.hip) ------------------
+namespace {
+bool convert_options_ok(const starch_convert_options* o, cv::ConvertOptions* out)
+{
+    if (!o || o->format > STARCH_CONVERT_WIG || o->vcf_class > STARCH_VCF_DELETIONS) return false;
+    if (o->vcf_class != STARCH_VCF_ALL && o->format != STARCH_CONVERT_VCF) return false;
+    out->format = o->format;
+    out->vcf_class = o->vcf_class;
+    out->keep_header = o->keep_header ? 1 : 0;
+    return true;
+}
+
+// d[0, n) converted into setop_out and, unless no_sort, sorted from there into sort_out
+void convert_run(starch_ctx* c, const cv::ConvertOptions& opt, bool no_sort, const uint8_t* d, uint64_t n,
+                 const std::chrono::steady_clock::time_point& t0)
+{
+    cv::ConvertResult r;
+    c->converter.run(c->sorter, opt, d, n, c->st, c->setop_out, r);
+    starch_convert_stats& s = c->vstats;
+    s = starch_convert_stats{};
+    s.input_bytes = n;
+    s.input_lines = r.n_lines;
+    s.header_lines = r.header_lines;
+    s.data_lines = r.data_lines;
+    s.declarations = r.declarations;
+    s.lines_out = r.lines_out;
+    s.output_bytes = r.out_bytes;
+    s.ms_frame = r.ms_frame;
+    s.ms_parse = r.ms_parse;
+    s.ms_write = r.ms_write;
+    if (no_sort) publish(c, c->setop_out, r.out_bytes);
+    else {
+        sort_run(c, static_cast<const uint8_t*>(c->setop_out.p), r.out_bytes, false);
+        s.sorted = 1;
+        s.ms_sort = c->sstats.ms_total;
+    }
+    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->have_vstats = true;
+}
+}  // namespace
+
+extern "C" {
+
+int starch_convert_device(starch_ctx* c, const void* d_data, uint64_t n, const starch_convert_options* opt)
+{
+    cv::ConvertOptions co;
+    if (!c || !convert_options_ok(opt, &co) || (n && !d_data)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_vstats = false;
+    convert_run(c, co, opt->no_sort != 0, static_cast<const uint8_t*>(d_data), n, std::chrono::steady_clock::now());
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_convert_host(starch_ctx* c, const void* data, uint64_t n, const starch_convert_options* opt)
+{
+    cv::ConvertOptions co;
+    if (!c || !convert_options_ok(opt, &co) || (n && !data)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_vstats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    convert_run(c, co, opt->no_sort != 0, sort_upload(c, data, n), n, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_convert_encode_host(starch_ctx* c, const void* data, uint64_t n, const starch_convert_options* copt,
+                               const starch_options* sopt)
+{
+    cv::ConvertOptions co;
+    if (!c || !convert_options_ok(copt, &co) || copt->no_sort || (n && !data)) return STARCH_ERR_ARG;
+    const starch_options o = options_of(sopt);
+    if (!options_ok(o)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have = false;
+    c->have_out = false;
+    c->have_vstats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    convert_run(c, co, false, sort_upload(c, data, n), n, t0);
+    // the sorted text is in sort_out, which no encoder stage writes
+    encode_device(c, c->out_dev, c->out_bytes, o);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_convert_get_stats(starch_ctx* c, starch_convert_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_vstats) return STARCH_ERR_STATE;
+    *out = c->vstats;
+    return STARCH_OK;
+}
+
+int starch_convert_constants(uint32_t* block_lines, uint32_t* wave_copy_bytes)
+{
+    if (block_lines) *block_lines = (uint32_t)cv::kThreads;
+    if (wave_copy_bytes) *wave_copy_bytes = sb::kWaveCopyBytes;
     return STARCH_OK;
 }
 

@@ -1,0 +1,36 @@
+// starch_amd/csrc/bed_convert.hpp -- host interface of convert2bed
+// (bed_convert.hip): GFF3, GTF, VCF and WIG text into BED lines, unsorted.
+#pragma once
+#include "common.hpp"
+#include "sort_bed.hpp"
+
+namespace cv {
+
+constexpr int kThreads = 256;           // threads per block of the per-line kernels (one line each)
+constexpr uint32_t kSlots = 10;         // 32-bit offsets kept per line (field starts, the ID, a declaration's record)
+
+struct ConvertOptions {                 // checked by the caller (api_convert.hip)
+    uint32_t format = 0;                // STARCH_CONVERT_*
+    uint32_t vcf_class = 0;             // STARCH_VCF_*
+    uint32_t keep_header = 0;
+};
+
+struct ConvertResult {
+    uint64_t n_lines = 0, header_lines = 0, data_lines = 0, declarations = 0, lines_out = 0, out_bytes = 0;
+    float ms_frame = 0, ms_parse = 0, ms_write = 0;
+};
+
+struct ConvertWorkspace {
+    DevBuf b_scal, b_tmp, b_cls, b_fo, b_a, b_b, b_aux, b_cnt, b_ob, b_off, b_hflag, b_hord, b_pk, b_dmax;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // The text d_in[0, n) in the format of opt, converted line by line as
+    // include/starch_amd.h defines, into out (res.out_bytes of it, in input
+    // order).  sorter supplies the framing (stage_frame) and is free again when
+    // run returns.  Throws StarchError: STARCH_ERR_DATA naming the lowest line
+    // that does not fit its format, STARCH_ERR_ARG for 2^32 lines or more.
+    void run(sb::SortWorkspace& sorter, const ConvertOptions& opt, const uint8_t* d_in, uint64_t n, hipStream_t st, DevBuf& out,
+             ConvertResult& res);
+    ~ConvertWorkspace();
+};
+
+}  // namespace cv

@@ -25,6 +25,7 @@
 #include "bed_setops.hpp"
 #include "bed_map.hpp"
 #include "bed_closest.hpp"
+#include "bed_convert.hpp"
 #include "transform.hpp"
 #include "untransform.hpp"
 
@@ -228,6 +229,11 @@ struct starch_ctx {
     bc::ClosestWorkspace closer;
     starch_closest_stats kstats{};   // the last starch_closest_* call
     bool have_kstats = false;
+    // convert2bed (bed_convert.hip): reads input (or the caller's HBM), writes
+    // setop_out; the sort then fills sort_out
+    cv::ConvertWorkspace converter;
+    starch_convert_stats vstats{};   // the last starch_convert_* call
+    bool have_vstats = false;
     std::string err;
     // last result
     bool have = false;

@@ -506,10 +506,9 @@ SortWorkspace::~SortWorkspace()
         if (e) (void)hipEventDestroy(e);
 }
 
-uint64_t SortWorkspace::stage_parse(const uint8_t* d_bed, uint64_t n, hipStream_t st, uint64_t* bad)
+uint64_t SortWorkspace::stage_frame(const uint8_t* d_bed, uint64_t n, hipStream_t st)
 {
     uint64_t* scal = b_scal.as<uint64_t>(S_COUNT);
-    unsigned long long* uscal = reinterpret_cast<unsigned long long*>(scal);
     HIP_CHECK(hipMemsetAsync(scal, 0, 16 * sizeof(uint64_t), st));
     HIP_CHECK(hipMemsetAsync(scal + 16, 0xff, 16 * sizeof(uint64_t), st));
     const uint64_t ntile = ceil_div(n, kTileBytes);
@@ -531,6 +530,15 @@ uint64_t SortWorkspace::stage_parse(const uint8_t* d_bed, uint64_t n, hipStream_
     ln.line_end = b_line_end.as<uint64_t>(L + 1);
     if (nl) hipLaunchKernelGGL(k_sb_index_nl, dim3((unsigned)ntile), dim3(kThreads), 0, st, d_bed, n, tile_off, ln.line_end);
     if (open_end) hipLaunchKernelGGL(k_sb_set_u64, dim3(1), dim3(1), 0, st, ln.line_end + nl, n + 1);
+    HIP_CHECK(hipGetLastError());
+    return L;
+}
+
+uint64_t SortWorkspace::stage_parse(const uint8_t* d_bed, uint64_t n, hipStream_t st, uint64_t* bad)
+{
+    const uint64_t L = stage_frame(d_bed, n, st);
+    uint64_t* scal = b_scal.as<uint64_t>(S_COUNT);
+    unsigned long long* uscal = reinterpret_cast<unsigned long long*>(scal);
     ln.start = b_start.as<uint64_t>(L);
     ln.stop = b_stop.as<uint64_t>(L);
     ln.chr_len = b_chr_len.as<uint32_t>(L);

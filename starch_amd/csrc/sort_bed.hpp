@@ -51,7 +51,11 @@ struct SortWorkspace {
     uint64_t n_chromosomes = 0;                // after stage_rank
     std::vector<uint64_t> chrom_off;           // by rank: the name's bytes in d_bed (its representative line's)
     std::vector<uint32_t> chrom_len;
-    // 1. line ends and parse of d_bed[0, n), n > 0.  Returns the number of
+    // 1a. line ends of d_bed[0, n), n > 0, cut at '\n': ln.L, ln.open_end and
+    // ln.line_end alone (bed_convert.hip frames text that is not BED yet).
+    // Returns the number of lines.
+    uint64_t stage_frame(const uint8_t* d_bed, uint64_t n, hipStream_t st);
+    // 1. stage_frame and the parse of every line.  Returns the number of
     // lines; *bad is ~0, or (line << 8) | kind of the first malformed line.
     uint64_t stage_parse(const uint8_t* d_bed, uint64_t n, hipStream_t st, uint64_t* bad);
     // 2. chromosome ranks of the parsed lines (none of them malformed)
