@@ -809,6 +809,121 @@ int starch_closest_get_stats(starch_ctx* ctx, starch_closest_stats* out);
  * tiles per tile of the level above). */
 int starch_closest_constants(uint32_t* tile_refs, uint32_t* fanout);
 
+/* ---- bedmap-elements: the map lines that overlap each reference line ------------
+ * bedmap's sibling for everything that needs the overlapping map lines one by
+ * one: the --echo-map columns and the overlap criteria other than one base.
+ * Inputs, line validity, archive inputs, the reference as its own map (no map
+ * given) and errors with their kinds, order and naming are those of
+ * starch_map_host.  Error texts begin "bedmap-elements: input K, line N:".
+ * For a reference line (c, s, e) and range r the window is [s', e') =
+ * [max(0, s - r), e + r) on c (e + r stops at 2^64-1).  For a map line (c, a, b)
+ * ov = min(b, e') - max(a, s'); the line is a candidate when a < e' and b > s'.
+ * Criterion: exactly one (BEDOPS: at most one overlap option; the commands'
+ * default is BP_OVR with n = 1).  A candidate is a hit when
+ *   BP_OVR n (n >= 1)   ov >= n;
+ *   RANGE r             always (the only criterion with r > 0);
+ *   FRACTION_REF f      ov / (e - s) >= f;
+ *   FRACTION_MAP f      ov / (b - a) >= f;
+ *   FRACTION_BOTH f     both of the two above;
+ *   FRACTION_EITHER f   either of them;
+ *   EXACT               a == s and b == e.
+ * f is an exact decimal, frac_num / 10^frac_digits with frac_digits 0 to 9 and
+ * 0 < f <= 1; the test is ov * 10^frac_digits >= frac_num * len in 128-bit
+ * unsigned arithmetic, with no floating point anywhere.  The fields of a
+ * criterion that is not the chosen one must be 0 (n, range, frac_num,
+ * frac_digits): a second criterion, like n == 0 under BP_OVR, a fraction outside
+ * (0, 1] or an unknown code, is STARCH_ERR_ARG.
+ * Per-line columns:
+ *   ECHO, COUNT (the number of hits), INDICATOR, ECHO_REF_SIZE as in bedmap;
+ *   ECHO_REF_NAME     chrom:start-stop of the reference line;
+ *   ECHO_REF_ROW_ID   id-N, N the reference line's number from 1.
+ * Per-hit list columns: the hits' values in map order, joined by multidelim (1
+ * to 8 bytes; the command's default is ";"), empty when there is no hit:
+ *   ECHO_MAP            the whole map line, without its '\n';
+ *   ECHO_MAP_ID         its column 4, byte for byte;
+ *   ECHO_MAP_SCORE      its column 5, byte for byte;
+ *   ECHO_MAP_SIZE       b - a, in decimal;
+ *   ECHO_OVERLAP_SIZE   ov, in decimal.
+ * ECHO_MAP_RANGE is no list: one BED3 `chrom TAB min a TAB max b` over the hits.
+ * A hit that lacks the column ECHO_MAP_ID or ECHO_MAP_SCORE asks for (columns
+ * are separated by TAB; an empty column is there) is STARCH_ERR_DATA naming
+ * input 1 (0 when the reference is its own map) and the lowest such map line
+ * that is a hit of some reference line; map lines that are never hits are not
+ * checked.
+ * The output is one line per reference line, in reference order: 1 to 12
+ * columns, none twice, in the order given, joined by delim (1 to 8 bytes,
+ * default "|"), then '\n'.  With skip_unmapped, lines with no hit are left out.
+ * 2^32 hits or more in all, or 2^40 output bytes or more, is STARCH_ERR_ARG,
+ * "result too large", answered from the scanned counts before the hit list (or,
+ * for the bytes, the output) is allocated.
+ * This is a definition by sets, modelled on BEDOPS' bedmap for the options
+ * named, but it is unverified against a BEDOPS binary.  Known differences:
+ * scores are copied, not reformatted; there is no --echo-map-id-uniq;
+ * ECHO_MAP_RANGE is empty when there are no hits.
+ * A repeated column, no columns or more than 12, an unknown code, an empty or
+ * over-long delimiter or multi-delimiter and a NULL context, reference or
+ * options are STARCH_ERR_ARG, answered before anything touches a device. */
+#define STARCH_MAPEL_ECHO 0
+#define STARCH_MAPEL_COUNT 1
+#define STARCH_MAPEL_INDICATOR 2
+#define STARCH_MAPEL_ECHO_REF_SIZE 3
+#define STARCH_MAPEL_ECHO_REF_NAME 4
+#define STARCH_MAPEL_ECHO_REF_ROW_ID 5
+#define STARCH_MAPEL_ECHO_MAP 6
+#define STARCH_MAPEL_ECHO_MAP_ID 7
+#define STARCH_MAPEL_ECHO_MAP_SCORE 8
+#define STARCH_MAPEL_ECHO_MAP_SIZE 9
+#define STARCH_MAPEL_ECHO_OVERLAP_SIZE 10
+#define STARCH_MAPEL_ECHO_MAP_RANGE 11
+#define STARCH_MAPEL_CRIT_BP_OVR 0
+#define STARCH_MAPEL_CRIT_RANGE 1
+#define STARCH_MAPEL_CRIT_FRACTION_REF 2
+#define STARCH_MAPEL_CRIT_FRACTION_MAP 3
+#define STARCH_MAPEL_CRIT_FRACTION_BOTH 4
+#define STARCH_MAPEL_CRIT_FRACTION_EITHER 5
+#define STARCH_MAPEL_CRIT_EXACT 6
+typedef struct {
+    uint32_t ncols;          /* 1 to 12 */
+    uint8_t cols[12];        /* STARCH_MAPEL_*, none twice */
+    uint32_t criterion;      /* STARCH_MAPEL_CRIT_* */
+    uint32_t frac_digits;    /* FRACTION_*: 0 to 9 */
+    uint64_t n;              /* BP_OVR: 1 or more */
+    uint64_t range;          /* RANGE */
+    uint64_t frac_num;       /* FRACTION_*: f = frac_num / 10^frac_digits */
+    uint32_t skip_unmapped;
+    uint32_t delim_len;      /* 1 to 8 */
+    uint32_t multidelim_len; /* 1 to 8 */
+    char delim[8];
+    char multidelim[8];
+} starch_mapel_options;      /* 80 bytes, every field naturally aligned */
+/* map_or_null == NULL: the reference is its own map. */
+int starch_mapel_host(starch_ctx* ctx, const starch_setop_input* ref, const starch_setop_input* map_or_null,
+                      const starch_mapel_options* opt);
+/* BED text only, back to back in HBM: the reference is d_bed[offs[0], offs[1]),
+ * the map d_bed[offs[1], offs[2]); ninputs is 1 (no map) or 2. */
+int starch_mapel_device(starch_ctx* ctx, const void* d_bed, const uint64_t* offs, uint64_t ninputs,
+                        const starch_mapel_options* opt);
+typedef struct {
+    uint64_t n_ref, n_map;     /* lines; n_map == n_ref when there is no map */
+    uint64_t n_chromosomes;    /* over both inputs */
+    uint64_t hits;             /* over all reference lines */
+    uint64_t heavy_lines;      /* reference lines whose run of candidates was tested by a whole wave */
+    uint64_t walk_steps;       /* probes of the binary searches and of the hierarchy while the hits were counted */
+    uint64_t lines_out, output_bytes;
+    /* ms_decode (upload and archive decode) and ms_total are host clock, the others GPU events */
+    float ms_decode, ms_parse, ms_build, ms_query, ms_format, ms_total;
+} starch_mapel_stats;
+/* Of the last successful starch_mapel_* call on this context. */
+int starch_mapel_get_stats(starch_ctx* ctx, starch_mapel_stats* out);
+/* Sizes the kernels switch on: reference lines per workgroup of the passes that
+ * find the hits; the fan-out of the hierarchy of maxima over the map stops;
+ * heavy_threshold: a reference line takes the whole-wave path when the run of
+ * its candidates that start inside the window has that many lines or more; and
+ * the bound on walk_steps: at most steps_per_hit_bound for every reference line
+ * plus as many for every candidate that starts before the window (each of
+ * these is a hit under BP_OVR and RANGE), whatever lies between them. */
+int starch_mapel_constants(uint32_t* tile_refs, uint32_t* fanout, uint32_t* heavy_threshold, uint32_t* steps_per_hit_bound);
+
 /* ---- convert2bed: GFF3, GTF, VCF and WIG to BED ----------------------------------
  * Text in one of four formats becomes BED lines, one thread per input line, and
  * unless no_sort is set the lines then go through starch_sort_device unchanged,

@@ -19,6 +19,7 @@ __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_arc
            "archive_layout", "compress_multi", "Unit", "Segment", "Comm", "gather_host", "MAGIC", "HG38", "HG38_LEN",
            "list_archive", "cat_plan", "cat_host", "sort_constants", "setop_constants", "SETOPS",
            "map_constants", "MAPCOLS", "BEDOPS_OPS", "bedops_constants", "closest_constants",
+           "mapel_constants", "mapel_fraction", "MAPEL_COLS", "MAPEL_CRITERIA", "MapelOptions", "MapelStats",
            "convert_constants", "CONVERT_FORMATS", "VCF_CLASSES", "ConvertOptions", "ConvertStats"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -175,6 +176,28 @@ class ClosestStats(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("ms_decode", "ms_parse", "ms_build", "ms_query", "ms_format", "ms_total")]
 
 
+MAPEL_COLS = {"echo": 0, "count": 1, "indicator": 2, "echo_ref_size": 3, "echo_ref_name": 4, "echo_ref_row_id": 5,
+              "echo_map": 6, "echo_map_id": 7, "echo_map_score": 8, "echo_map_size": 9, "echo_overlap_size": 10,
+              "echo_map_range": 11}                                               # STARCH_MAPEL_*
+MAPEL_CRITERIA = {"bp_ovr": 0, "range": 1, "fraction_ref": 2, "fraction_map": 3, "fraction_both": 4,
+                  "fraction_either": 5, "exact": 6}                               # STARCH_MAPEL_CRIT_*
+
+
+class MapelOptions(ctypes.Structure):
+    """starch_mapel_options: the columns, criterion and delimiters of map_elements()."""
+    _fields_ = [("ncols", ctypes.c_uint32), ("cols", ctypes.c_uint8 * 12), ("criterion", ctypes.c_uint32),
+                ("frac_digits", ctypes.c_uint32), ("n", ctypes.c_uint64), ("range", ctypes.c_uint64),
+                ("frac_num", ctypes.c_uint64), ("skip_unmapped", ctypes.c_uint32), ("delim_len", ctypes.c_uint32),
+                ("multidelim_len", ctypes.c_uint32), ("delim", ctypes.c_char * 8), ("multidelim", ctypes.c_char * 8)]
+
+
+class MapelStats(ctypes.Structure):
+    """starch_mapel_stats: the last map_elements()."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_ref", "n_map", "n_chromosomes", "hits", "heavy_lines", "walk_steps",
+                                               "lines_out", "output_bytes")] + \
+               [(n, ctypes.c_float) for n in ("ms_decode", "ms_parse", "ms_build", "ms_query", "ms_format", "ms_total")]
+
+
 CONVERT_FORMATS = {"gff": 0, "gtf": 1, "vcf": 2, "wig": 3}                       # STARCH_CONVERT_*
 VCF_CLASSES = {"all": 0, "snvs": 1, "insertions": 2, "deletions": 3}              # STARCH_VCF_*
 
@@ -322,6 +345,11 @@ def load():
         "starch_closest_device": ([vp, vp, pu64, ctypes.POINTER(ClosestOptions)], ctypes.c_int),
         "starch_closest_get_stats": ([vp, ctypes.POINTER(ClosestStats)], ctypes.c_int),
         "starch_closest_constants": ([ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+        "starch_mapel_host": ([vp, ctypes.POINTER(SetopInput), ctypes.POINTER(SetopInput), ctypes.POINTER(MapelOptions)],
+                              ctypes.c_int),
+        "starch_mapel_device": ([vp, vp, pu64, u64, ctypes.POINTER(MapelOptions)], ctypes.c_int),
+        "starch_mapel_get_stats": ([vp, ctypes.POINTER(MapelStats)], ctypes.c_int),
+        "starch_mapel_constants": ([ctypes.POINTER(ctypes.c_uint32)] * 4, ctypes.c_int),
         "starch_convert_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(ConvertOptions)], ctypes.c_int),
         "starch_convert_device": ([vp, vp, u64, ctypes.POINTER(ConvertOptions)], ctypes.c_int),
         "starch_convert_encode_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(ConvertOptions), ctypes.POINTER(Options)],
@@ -888,6 +916,51 @@ class Starch:
         _check(self._L.starch_closest_get_stats(self._h, ctypes.byref(s)), self._h)
         return {k: getattr(s, k) for k, _ in ClosestStats._fields_}
 
+    # ---- bedmap-elements ----
+    def map_elements(self, ref, map=None, cols=("echo", "echo_map"), criterion=("bp_ovr", 1), skip_unmapped=False,
+                     delim=b"|", multidelim=b";") -> bytes:
+        """bedmap-elements: one line per line of the sorted reference ``ref``
+        with the columns ``cols`` (names of MAPEL_COLS, in this order, none
+        twice) joined by ``delim``.  The hits of a reference line are the
+        lines of the sorted ``map`` (None: ``ref`` itself) that satisfy
+        ``criterion``: ``("bp_ovr", N)``, ``("range", N)``, ``("exact",)`` or
+        ``("fraction_ref" | "fraction_map" | "fraction_both" |
+        "fraction_either", F)`` with F a string or decimal.Decimal such as
+        "0.5" (never a float: the comparison is exact).  The echo_map columns
+        list one value per hit, joined by ``multidelim``.  Either input is BED
+        text or an archive.  The definitions are in include/starch_amd.h.  A
+        malformed or unsorted line, or a hit without the column echo_map_id or
+        echo_map_score asks for, is StarchError -12 naming input (ref 0, map
+        1) and line; a bad argument is -2."""
+        o = _mapel_options(cols, criterion, skip_unmapped, delim, multidelim)
+        r = SetopInput(bytes(ref), len(ref))
+        m = None if map is None else ctypes.byref(SetopInput(bytes(map), len(map)))
+        _check(self._L.starch_mapel_host(self._h, ctypes.byref(r), m, ctypes.byref(o)), self._h)
+        return self._output()
+
+    def map_elements_device(self, d_ptr: int, offs, cols=("echo", "echo_map"), criterion=("bp_ovr", 1), skip_unmapped=False,
+                            delim=b"|", multidelim=b";") -> int:
+        """The same for BED text in HBM: the reference at d_ptr + [offs[0],
+        offs[1]), the map (if offs has a third entry) at d_ptr + [offs[1],
+        offs[2]); returns the output size (output_device_ptr())."""
+        o = _mapel_options(cols, criterion, skip_unmapped, delim, multidelim)
+        offs = [int(x) for x in offs]
+        a = (ctypes.c_uint64 * len(offs))(*offs)
+        _check(self._L.starch_mapel_device(self._h, ctypes.c_void_p(d_ptr), a, len(offs) - 1, ctypes.byref(o)), self._h)
+        k = ctypes.c_uint64()
+        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
+        return k.value
+
+    def mapel_stats(self) -> dict:
+        """Of the last map_elements(): n_ref / n_map / n_chromosomes / hits /
+        heavy_lines / walk_steps / lines_out / output_bytes (also under the
+        name out_bytes) / ms_*."""
+        s = MapelStats()
+        _check(self._L.starch_mapel_get_stats(self._h, ctypes.byref(s)), self._h)
+        d = {k: getattr(s, k) for k, _ in MapelStats._fields_}
+        d["out_bytes"] = d["output_bytes"]
+        return d
+
     # ---- convert2bed ----
     def convert(self, data: bytes, fmt: str, vcf_class="all", keep_header=False, sort=True) -> bytes:
         """convert2bed: text in format ``fmt`` (a name of CONVERT_FORMATS: GFF3,
@@ -1030,6 +1103,73 @@ def _closest_options(closest, dist, no_overlaps, no_ref, delim):
     o.no_ref = 1 if no_ref else 0
     o.delim_len = len(delim)
     ctypes.memmove(ctypes.addressof(o) + ClosestOptions.delim.offset, delim, min(len(delim), 8))
+    return o
+
+
+def mapel_constants():
+    """(reference lines per workgroup, fan-out of the hierarchy of maxima over
+    the map stops, candidates from which a reference line's run is tested by a
+    whole wave, bound on walk_steps per reference line and per hit) of
+    bedmap-elements' kernels; no GPU needed."""
+    v = [ctypes.c_uint32() for _ in range(4)]
+    _check(load().starch_mapel_constants(*[ctypes.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def mapel_fraction(f):
+    """(numerator, digits) of the exact decimal ``f``, a str, bytes or
+    decimal.Decimal: digits, optionally a point and up to 9 more digits, with a
+    value above 0 and up to 1.  Anything else (a float, an exponent, 0, 1.01,
+    ten digits) is ValueError."""
+    import decimal
+    import re
+    if isinstance(f, decimal.Decimal):
+        if not f.is_finite():
+            raise ValueError("bedmap-elements: the fraction is not finite")
+        f = format(f, "f")
+    elif isinstance(f, (bytes, bytearray)):
+        f = bytes(f).decode("ascii", "replace")
+    if not isinstance(f, str):
+        raise ValueError("bedmap-elements: a fraction is a str or decimal.Decimal such as '0.5', never a float")
+    m = re.fullmatch(r"([0-9]*)(?:\.([0-9]*))?", f)
+    if not m or not ((m.group(1) or "") + (m.group(2) or "")):
+        raise ValueError("bedmap-elements: %r is no plain decimal" % f)
+    frac = m.group(2) or ""
+    if len(frac) > 9:
+        raise ValueError("bedmap-elements: a fraction has at most 9 digits after the point")
+    num = int(m.group(1) or "0") * 10 ** len(frac) + int(frac or "0")
+    if not 0 < num <= 10 ** len(frac):
+        raise ValueError("bedmap-elements: a fraction is above 0 and up to 1")
+    return num, len(frac)
+
+
+def _mapel_options(cols, criterion, skip_unmapped, delim, multidelim):
+    """starch_mapel_options; unknown names and a fraction that is no exact
+    decimal in (0, 1] are ValueError, everything else is left to the library."""
+    cols = list(cols)
+    for c in cols:
+        if c not in MAPEL_COLS:
+            raise ValueError("bedmap-elements: a column must be one of %s" % ", ".join(MAPEL_COLS))
+    criterion = (criterion,) if isinstance(criterion, str) else tuple(criterion)
+    if not criterion or criterion[0] not in MAPEL_CRITERIA or len(criterion) != (1 if criterion[0] == "exact" else 2):
+        raise ValueError("bedmap-elements: criterion is ('exact',) or (name, value) with a name of %s" % ", ".join(MAPEL_CRITERIA))
+    delim, multidelim = bytes(delim), bytes(multidelim)
+    o = MapelOptions()
+    o.ncols = len(cols)
+    for k, c in enumerate(cols[:12]):
+        o.cols[k] = MAPEL_COLS[c]
+    o.criterion = MAPEL_CRITERIA[criterion[0]]
+    if criterion[0] == "bp_ovr":
+        o.n = int(criterion[1])
+    elif criterion[0] == "range":
+        o.range = int(criterion[1])
+    elif criterion[0] != "exact":
+        o.frac_num, o.frac_digits = mapel_fraction(criterion[1])
+    o.skip_unmapped = 1 if skip_unmapped else 0
+    o.delim_len = len(delim)
+    o.multidelim_len = len(multidelim)
+    ctypes.memmove(ctypes.addressof(o) + MapelOptions.delim.offset, delim, min(len(delim), 8))
+    ctypes.memmove(ctypes.addressof(o) + MapelOptions.multidelim.offset, multidelim, min(len(multidelim), 8))
     return o
 
 

@@ -1,4 +1,5 @@
-// starch_amd/csrc/api_bed.hip -- the C ABI of sort-bed, bedops, bedmap, closest-features and convert2bed.
+// starch_amd/csrc/api_bed.hip -- the C ABI of sort-bed, bedops, bedmap, closest-features, bedmap-elements and
+// convert2bed.
 #include <string.h>
 
 #include <algorithm>
@@ -531,6 +532,129 @@ int starch_closest_constants(uint32_t* tile_refs, uint32_t* fanout)
 {
     if (tile_refs) *tile_refs = (uint32_t)bc::kTileRefs;
     if (fanout) *fanout = bc::kFanout;
+    return STARCH_OK;
+}
+
+}  // extern "C"
+
+// ---- bedmap-elements (include/starch_amd.h; kernels in bed_mapel.hip) ---------------
+namespace {
+bool mapel_options_ok(const starch_mapel_options* o, me::MapelOptions* out)
+{
+    if (!o || o->ncols < 1 || o->ncols > me::kMaxCols || o->delim_len < 1 || o->delim_len > 8 || o->multidelim_len < 1 ||
+        o->multidelim_len > 8)
+        return false;
+    uint32_t seen = 0;
+    for (uint32_t k = 0; k < o->ncols; ++k) {
+        if (o->cols[k] > STARCH_MAPEL_ECHO_MAP_RANGE || ((seen >> o->cols[k]) & 1)) return false;
+        seen |= 1u << o->cols[k];
+        out->cols[k] = o->cols[k];
+    }
+    out->ncols = o->ncols;
+    // exactly one criterion: the fields of the others are 0
+    const uint32_t c = o->criterion;
+    if (c > STARCH_MAPEL_CRIT_EXACT) return false;
+    const bool frac = c >= STARCH_MAPEL_CRIT_FRACTION_REF && c <= STARCH_MAPEL_CRIT_FRACTION_EITHER;
+    if ((c == STARCH_MAPEL_CRIT_BP_OVR) != (o->n != 0)) return false;
+    if (c != STARCH_MAPEL_CRIT_RANGE && o->range != 0) return false;
+    if (!frac && (o->frac_num != 0 || o->frac_digits != 0)) return false;
+    out->criterion = c;
+    out->n = o->n;
+    out->range = o->range;
+    if (frac) {
+        if (o->frac_digits > 9) return false;
+        uint64_t den = 1;
+        for (uint32_t k = 0; k < o->frac_digits; ++k) den *= 10;
+        if (o->frac_num == 0 || o->frac_num > den) return false;
+        out->frac_num = o->frac_num;
+        out->frac_den = den;
+    }
+    out->skip_unmapped = o->skip_unmapped ? 1 : 0;
+    out->delim_len = o->delim_len;
+    memcpy(out->delim, o->delim, o->delim_len);
+    out->multi_len = o->multidelim_len;
+    memcpy(out->multi, o->multidelim, o->multidelim_len);
+    return true;
+}
+
+void mapel_run(starch_ctx* c, const me::MapelOptions& opt, uint64_t len, const std::vector<uint64_t>& in_end, double ms_decode,
+               const std::chrono::steady_clock::time_point& t0)
+{
+    me::MapelResult r;
+    c->mapel.run(c->sorter, c->setop, opt, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, c->st, c->setop_out, r);
+    starch_mapel_stats& s = c->estats;
+    s = starch_mapel_stats{};
+    s.n_ref = r.n_ref;
+    s.n_map = r.n_map;
+    s.n_chromosomes = r.n_chromosomes;
+    s.hits = r.hits;
+    s.heavy_lines = r.heavy_lines;
+    s.walk_steps = r.walk_steps;
+    s.lines_out = r.lines_out;
+    s.output_bytes = r.out_bytes;
+    s.ms_decode = (float)ms_decode;
+    s.ms_parse = r.ms_parse;
+    s.ms_build = r.ms_build;
+    s.ms_query = r.ms_query;
+    s.ms_format = r.ms_format;
+    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->have_estats = true;
+    publish(c, c->setop_out, r.out_bytes);
+}
+}  // namespace
+
+extern "C" {
+
+int starch_mapel_host(starch_ctx* c, const starch_setop_input* ref, const starch_setop_input* map,
+                      const starch_mapel_options* opt)
+{
+    me::MapelOptions mo;
+    if (!c || !ref || !mapel_options_ok(opt, &mo)) return STARCH_ERR_ARG;
+    if ((ref->len && !ref->data) || (map && map->len && !map->data)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_estats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<starch_setop_input> inputs{*ref};
+    if (map) inputs.push_back(*map);
+    std::vector<uint64_t> in_end;
+    const uint64_t len = setop_load_host(c, inputs.data(), inputs.size(), "bedmap-elements", in_end, nullptr);
+    const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    mapel_run(c, mo, len, in_end, ms_decode, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_mapel_device(starch_ctx* c, const void* d_bed, const uint64_t* offs, uint64_t ninputs, const starch_mapel_options* opt)
+{
+    me::MapelOptions mo;
+    if (!c || !offs || ninputs < 1 || ninputs > 2 || !mapel_options_ok(opt, &mo)) return STARCH_ERR_ARG;
+    if (!offs_ok(d_bed, offs, ninputs)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_estats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> in_end;
+    const uint64_t len = setop_load_device(c, d_bed, offs, ninputs, in_end);
+    mapel_run(c, mo, len, in_end, 0.0, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_mapel_get_stats(starch_ctx* c, starch_mapel_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_estats) return STARCH_ERR_STATE;
+    *out = c->estats;
+    return STARCH_OK;
+}
+
+int starch_mapel_constants(uint32_t* tile_refs, uint32_t* fanout, uint32_t* heavy_threshold, uint32_t* steps_per_hit_bound)
+{
+    if (tile_refs) *tile_refs = (uint32_t)me::kTileRefs;
+    if (fanout) *fanout = bc::kFanout;
+    if (heavy_threshold) *heavy_threshold = me::kHeavy;
+    if (steps_per_hit_bound) *steps_per_hit_bound = me::kStepsPerHit;
     return STARCH_OK;
 }
 

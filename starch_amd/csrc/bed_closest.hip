@@ -34,6 +34,7 @@
 
 #include "../../include/starch_amd.h"
 #include "bed_closest.hpp"
+#include "bed_hier.hpp"
 #include "bed_search.hpp"
 
 namespace bc {
@@ -48,31 +49,13 @@ enum : int { S_BYTES = 0, S_LEFT_NA, S_RIGHT_NA, S_COUNT = 4 };   // device scal
 
 inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return (unsigned)ceil_div(items, per_block); }
 
-// ---- 2. query arrays ------------------------------------------------------------------
-// out[g] = the largest of in[g * kFanout, min((g + 1) * kFanout, n))
-__global__ void __launch_bounds__(kThreads)
-k_bc_level(const uint64_t* __restrict__ in, uint64_t n, uint64_t groups, uint64_t* __restrict__ out)
-{
-    const uint64_t g = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (g >= groups) return;
-    const uint64_t b = g << kFanShift, e = b + kFanout < n ? b + kFanout : n;
-    uint64_t m = 0;
-    for (uint64_t k = b; k < e; ++k) m = in[k] > m ? in[k] : m;
-    out[g] = m;
-}
-
+// ---- 2. query arrays (the hierarchy's level kernel and builder: bed_hier.hpp) ----------
 __global__ void __launch_bounds__(kThreads)
 k_bc_gather(const uint32_t* __restrict__ idx, const uint64_t* __restrict__ v, uint64_t n, uint64_t* __restrict__ out)
 {
     const uint64_t j = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     if (j < n) out[j] = v[idx[j]];
 }
-
-struct Hier {
-    const uint64_t* lev[kMaxLevels];   // lev[0]: the stops themselves
-    uint64_t cnt[kMaxLevels];
-    int nlev;
-};
 
 // ---- 3. query -------------------------------------------------------------------------
 // The last j in [lo, p) with S[j] >= t, where lo < p and such a j exists.  Item
@@ -358,23 +341,7 @@ void ClosestWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines,
         (void)lines.stage_merge(start + m0, stop + m0, lines.head + m0, Lq, st);
         q.M = lines.incl;
         // the levels above the stops, one after the other in b_hier
-        uint64_t total = 0, c = Lq;
-        int nlev = 1;
-        while (c > 1) { c = ceil_div(c, kFanout); total += c; ++nlev; }
-        if (nlev > kMaxLevels) throw StarchError(STARCH_ERR_INTERNAL, "closest-features: too many levels");
-        uint64_t* hb = b_hier.as<uint64_t>(total);
-        q.h.nlev = nlev;
-        q.h.lev[0] = q.S;
-        q.h.cnt[0] = Lq;
-        for (int k = 1; k < nlev; ++k) {
-            const uint64_t groups = ceil_div(q.h.cnt[k - 1], kFanout);
-            hipLaunchKernelGGL(k_bc_level, dim3(blocks_for(groups, kThreads)), dim3(kThreads), 0, st, q.h.lev[k - 1],
-                               q.h.cnt[k - 1], groups, hb);
-            q.h.lev[k] = hb;
-            q.h.cnt[k] = groups;
-            hb += groups;
-        }
-        HIP_CHECK(hipGetLastError());
+        build_hier(q.S, Lq, b_hier, st, "closest-features", &q.h);
         const sb::KeyBits kb = sorter.stage_check(rank + m0, stop + m0, stop + m0, Lq, st);
         if (kb.desc != ~0ull) {   // a query line ends below the one before it: it is nested
             res.stops_sorted = 1;

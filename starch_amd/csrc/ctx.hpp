@@ -25,6 +25,7 @@
 #include "bed_setops.hpp"
 #include "bed_map.hpp"
 #include "bed_closest.hpp"
+#include "bed_mapel.hpp"
 #include "bed_convert.hpp"
 #include "transform.hpp"
 #include "untransform.hpp"
@@ -229,6 +230,10 @@ struct starch_ctx {
     bc::ClosestWorkspace closer;
     starch_closest_stats kstats{};   // the last starch_closest_* call
     bool have_kstats = false;
+    // bedmap-elements (bed_mapel.hip): reads setop_in, writes setop_out
+    me::MapelWorkspace mapel;
+    starch_mapel_stats estats{};     // the last starch_mapel_* call
+    bool have_estats = false;
     // convert2bed (bed_convert.hip): reads input (or the caller's HBM), writes
     // setop_out; the sort then fills sort_out
     cv::ConvertWorkspace converter;
