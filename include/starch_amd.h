@@ -924,6 +924,117 @@ int starch_mapel_get_stats(starch_ctx* ctx, starch_mapel_stats* out);
  * these is a hit under BP_OVR and RANGE), whatever lies between them. */
 int starch_mapel_constants(uint32_t* tile_refs, uint32_t* fanout, uint32_t* heavy_threshold, uint32_t* steps_per_hit_bound);
 
+/* ---- bedmap-scores: statistics of the scores of the hits of each reference line ----
+ * bedmap-elements' sibling for the score operations.  Inputs, line validity,
+ * archive inputs, the reference as its own map (no map given), the window, the
+ * candidates, the seven criteria (STARCH_MAPEL_CRIT_*, the same codes and the
+ * same rule that the fields of the criteria not chosen are 0) and errors with
+ * their kinds, order and naming are those of starch_mapel_host.  Error texts
+ * begin "bedmap-scores: input K, line N:".  The hits of a reference line are
+ * in map order.  2^32 hits or more in all, or 2^40 output bytes or more, is
+ * STARCH_ERR_ARG, "result too large", answered from the scanned counts before
+ * the hit list (or, for the bytes, the output) is allocated.
+ * Score.  The score of a hit is column 5 of its map line (columns are
+ * separated by TAB), the whole of it:
+ *   [+-]? D{1,9} ( '.' D{0,9} )?    or    [+-]? '.' D{1,9}
+ * at most 9 digits before the point and at most 9 after it, no exponent, no
+ * inf or nan, no spaces.  Its value is that exact decimal, held as a signed
+ * 64-bit count of 10^-9 units of magnitude below 10^18.  When a column from SUM
+ * on is asked for, a hit whose line has no column 5, or one outside this
+ * grammar, is STARCH_ERR_DATA naming input 1 (0 when the reference is its own
+ * map) and the lowest such map line that is a hit of some reference line; map
+ * lines that are never hits are not checked.  There is no floating point
+ * anywhere: every value below is an exact rational.
+ * Columns, for a reference line with the hits' scores v_1..v_n in map order and
+ * w_1 <= .. <= w_n the same values ascending:
+ *   ECHO         the reference line;
+ *   COUNT        n;
+ *   INDICATOR    1 or 0;
+ *   SUM          v_1 + .. + v_n;
+ *   MEAN         SUM / n;
+ *   MIN, MAX     the least and the greatest v_i;
+ *   MEDIAN       w_((n+1)/2) for odd n, (w_(n/2) + w_(n/2+1)) / 2 for even n;
+ *   KTH          w_k with k = ceil(f * n); f = kth_num / 10^kth_digits is an
+ *                exact decimal with kth_digits 0 to 9 and 0 < f <= 1, like the
+ *                fractions of bedmap-elements; kth_num and kth_digits must be 0
+ *                when KTH is no column;
+ *   MIN_ELEMENT  the whole map line, without its '\n', of the hit with the
+ *                least score; among equal scores the first in map order;
+ *   MAX_ELEMENT  the same for the greatest score.
+ * With n = 0 the columns from SUM on are the three bytes NAN.  SUM to KTH are
+ * written with prec decimals, prec 0 to 9 (the command's default is 6): for a
+ * value x let m be the integer nearest to x * 10^prec, ties to even; the
+ * output is '-' if m < 0, the decimal digits of |m| div 10^prec (at least 0)
+ * and, if prec > 0, '.' and exactly prec digits.  A value that rounds to zero
+ * carries no sign.  (A sum has magnitude below 2^32 * 10^18 < 2^92 units and is
+ * kept in 128 bits; the mean's denominator n * 10^(9-prec) is below 2^62.)
+ * The output is one line per reference line, in reference order: 1 to 12
+ * columns, none twice, in the order given, joined by delim (1 to 8 bytes,
+ * default "|"), then '\n'.  With skip_unmapped, lines with no hit are left out.
+ * This is a definition by sets, modelled on BEDOPS' bedmap for the options
+ * named, but it is unverified against a BEDOPS binary.  Known differences:
+ * scores are exact decimals, not strtod doubles, so an exponent form or more
+ * than 9+9 digits is a data error; rounding is exact on the rational, ties to
+ * even, not printf of a double; there is no negative zero; element ties go to
+ * map order; KTH is defined as above; --stdev, --variance, --cv, --mad,
+ * --tmean, --wmean and --echo-map-id-uniq are not supported (they need square
+ * roots or products beyond 128 bits).
+ * A NULL context, reference or options, no columns or more than 12, a column
+ * twice, an unknown code, prec above 9, a bad or stray kth, a second criterion
+ * and an empty or over-long delimiter are STARCH_ERR_ARG, answered before
+ * anything touches a device. */
+#define STARCH_MAPSC_ECHO 0
+#define STARCH_MAPSC_COUNT 1
+#define STARCH_MAPSC_INDICATOR 2
+#define STARCH_MAPSC_SUM 3
+#define STARCH_MAPSC_MEAN 4
+#define STARCH_MAPSC_MIN 5
+#define STARCH_MAPSC_MAX 6
+#define STARCH_MAPSC_MEDIAN 7
+#define STARCH_MAPSC_KTH 8
+#define STARCH_MAPSC_MIN_ELEMENT 9
+#define STARCH_MAPSC_MAX_ELEMENT 10
+typedef struct {
+    uint32_t ncols;          /* 1 to 12 */
+    uint8_t cols[12];        /* STARCH_MAPSC_*, none twice */
+    uint32_t criterion;      /* STARCH_MAPEL_CRIT_* */
+    uint32_t frac_digits;    /* FRACTION_*: 0 to 9 */
+    uint64_t n;              /* BP_OVR: 1 or more */
+    uint64_t range;          /* RANGE */
+    uint64_t frac_num;       /* FRACTION_*: f = frac_num / 10^frac_digits */
+    uint64_t kth_num;        /* KTH: f = kth_num / 10^kth_digits */
+    uint32_t kth_digits;     /* KTH: 0 to 9 */
+    uint32_t prec;           /* 0 to 9 */
+    uint32_t skip_unmapped;
+    uint32_t delim_len;      /* 1 to 8 */
+    char delim[8];
+} starch_mapsc_options;      /* 80 bytes, every field naturally aligned */
+/* map_or_null == NULL: the reference is its own map. */
+int starch_mapsc_host(starch_ctx* ctx, const starch_setop_input* ref, const starch_setop_input* map_or_null,
+                      const starch_mapsc_options* opt);
+/* BED text only, back to back in HBM: the reference is d_bed[offs[0], offs[1]),
+ * the map d_bed[offs[1], offs[2]); ninputs is 1 (no map) or 2. */
+int starch_mapsc_device(starch_ctx* ctx, const void* d_bed, const uint64_t* offs, uint64_t ninputs,
+                        const starch_mapsc_options* opt);
+typedef struct {
+    uint64_t n_ref, n_map;     /* lines; n_map == n_ref when there is no map */
+    uint64_t n_chromosomes;    /* over both inputs */
+    uint64_t hits;             /* over all reference lines */
+    uint64_t straddling;       /* reference lines whose hits lie in more than one tile: combined through atomics */
+    uint64_t sorted_hits;      /* MEDIAN, KTH: hits when the radix stage ran, 0 when they were in order already */
+    uint64_t radix_passes;     /* of that stage */
+    uint64_t lines_out, output_bytes;
+    /* ms_decode (upload and archive decode) and ms_total are host clock, the others GPU events */
+    float ms_decode, ms_parse, ms_build, ms_query, ms_reduce, ms_format, ms_total;
+} starch_mapsc_stats;
+/* Of the last successful starch_mapsc_* call on this context. */
+int starch_mapsc_get_stats(starch_ctx* ctx, starch_mapsc_stats* out);
+/* Sizes the kernels switch on: contiguous hits per workgroup of the segmented
+ * reduction (tile t holds the hits [t * tile_hits, (t + 1) * tile_hits) of the
+ * hit list), and the bytes from which an echoed line is copied by a whole
+ * wave. */
+int starch_mapsc_constants(uint32_t* tile_hits, uint32_t* wave_copy_threshold);
+
 /* ---- convert2bed: GFF3, GTF, VCF and WIG to BED ----------------------------------
  * Text in one of four formats becomes BED lines, one thread per input line, and
  * unless no_sort is set the lines then go through starch_sort_device unchanged,

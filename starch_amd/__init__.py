@@ -20,6 +20,7 @@ __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_arc
            "list_archive", "cat_plan", "cat_host", "sort_constants", "setop_constants", "SETOPS",
            "map_constants", "MAPCOLS", "BEDOPS_OPS", "bedops_constants", "closest_constants",
            "mapel_constants", "mapel_fraction", "MAPEL_COLS", "MAPEL_CRITERIA", "MapelOptions", "MapelStats",
+           "mapsc_constants", "MAPSC_COLS", "MapscOptions", "MapscStats",
            "convert_constants", "CONVERT_FORMATS", "VCF_CLASSES", "ConvertOptions", "ConvertStats"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -198,6 +199,27 @@ class MapelStats(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("ms_decode", "ms_parse", "ms_build", "ms_query", "ms_format", "ms_total")]
 
 
+MAPSC_COLS = {"echo": 0, "count": 1, "indicator": 2, "sum": 3, "mean": 4, "min": 5, "max": 6, "median": 7, "kth": 8,
+              "min_element": 9, "max_element": 10}                                # STARCH_MAPSC_*
+
+
+class MapscOptions(ctypes.Structure):
+    """starch_mapsc_options: the columns, criterion, kth, precision and delimiter of map_scores()."""
+    _fields_ = [("ncols", ctypes.c_uint32), ("cols", ctypes.c_uint8 * 12), ("criterion", ctypes.c_uint32),
+                ("frac_digits", ctypes.c_uint32), ("n", ctypes.c_uint64), ("range", ctypes.c_uint64),
+                ("frac_num", ctypes.c_uint64), ("kth_num", ctypes.c_uint64), ("kth_digits", ctypes.c_uint32),
+                ("prec", ctypes.c_uint32), ("skip_unmapped", ctypes.c_uint32), ("delim_len", ctypes.c_uint32),
+                ("delim", ctypes.c_char * 8)]
+
+
+class MapscStats(ctypes.Structure):
+    """starch_mapsc_stats: the last map_scores()."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n_ref", "n_map", "n_chromosomes", "hits", "straddling", "sorted_hits",
+                                               "radix_passes", "lines_out", "output_bytes")] + \
+               [(n, ctypes.c_float) for n in ("ms_decode", "ms_parse", "ms_build", "ms_query", "ms_reduce", "ms_format",
+                                              "ms_total")]
+
+
 CONVERT_FORMATS = {"gff": 0, "gtf": 1, "vcf": 2, "wig": 3}                       # STARCH_CONVERT_*
 VCF_CLASSES = {"all": 0, "snvs": 1, "insertions": 2, "deletions": 3}              # STARCH_VCF_*
 
@@ -350,6 +372,11 @@ def load():
         "starch_mapel_device": ([vp, vp, pu64, u64, ctypes.POINTER(MapelOptions)], ctypes.c_int),
         "starch_mapel_get_stats": ([vp, ctypes.POINTER(MapelStats)], ctypes.c_int),
         "starch_mapel_constants": ([ctypes.POINTER(ctypes.c_uint32)] * 4, ctypes.c_int),
+        "starch_mapsc_host": ([vp, ctypes.POINTER(SetopInput), ctypes.POINTER(SetopInput), ctypes.POINTER(MapscOptions)],
+                              ctypes.c_int),
+        "starch_mapsc_device": ([vp, vp, pu64, u64, ctypes.POINTER(MapscOptions)], ctypes.c_int),
+        "starch_mapsc_get_stats": ([vp, ctypes.POINTER(MapscStats)], ctypes.c_int),
+        "starch_mapsc_constants": ([ctypes.POINTER(ctypes.c_uint32)] * 2, ctypes.c_int),
         "starch_convert_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(ConvertOptions)], ctypes.c_int),
         "starch_convert_device": ([vp, vp, u64, ctypes.POINTER(ConvertOptions)], ctypes.c_int),
         "starch_convert_encode_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(ConvertOptions), ctypes.POINTER(Options)],
@@ -961,6 +988,49 @@ class Starch:
         d["out_bytes"] = d["output_bytes"]
         return d
 
+    # ---- bedmap-scores ----
+    def map_scores(self, ref, map=None, cols=("echo", "mean"), criterion=("bp_ovr", 1), prec=6, kth=None, skip_unmapped=False,
+                   delim=b"|") -> bytes:
+        """bedmap-scores: one line per line of the sorted reference ``ref``
+        with the columns ``cols`` (names of MAPSC_COLS, in this order, none
+        twice) joined by ``delim``.  The hits are those of map_elements()
+        under the same ``criterion``; the score of a hit is column 5 of its
+        map line, an exact decimal with up to 9 digits on either side of the
+        point.  sum, mean, min, max, median and kth are exact and are written
+        with ``prec`` (0 to 9) decimals, rounded once, ties to even; a line
+        without a hit has NAN there.  ``kth`` is a string or decimal.Decimal
+        in (0, 1] such as "0.5" (never a float), needed exactly when "kth" is
+        a column.  The definitions are in include/starch_amd.h.  A malformed
+        or unsorted line, or a hit without a valid score when a column from
+        sum on is asked for, is StarchError -12 naming input (ref 0, map 1)
+        and line; a bad argument is -2."""
+        o = _mapsc_options(cols, criterion, prec, kth, skip_unmapped, delim)
+        r = SetopInput(bytes(ref), len(ref))
+        m = None if map is None else ctypes.byref(SetopInput(bytes(map), len(map)))
+        _check(self._L.starch_mapsc_host(self._h, ctypes.byref(r), m, ctypes.byref(o)), self._h)
+        return self._output()
+
+    def map_scores_device(self, d_ptr: int, offs, cols=("echo", "mean"), criterion=("bp_ovr", 1), prec=6, kth=None,
+                          skip_unmapped=False, delim=b"|") -> int:
+        """The same for BED text in HBM: the reference at d_ptr + [offs[0],
+        offs[1]), the map (if offs has a third entry) at d_ptr + [offs[1],
+        offs[2]); returns the output size (output_device_ptr())."""
+        o = _mapsc_options(cols, criterion, prec, kth, skip_unmapped, delim)
+        offs = [int(x) for x in offs]
+        a = (ctypes.c_uint64 * len(offs))(*offs)
+        _check(self._L.starch_mapsc_device(self._h, ctypes.c_void_p(d_ptr), a, len(offs) - 1, ctypes.byref(o)), self._h)
+        k = ctypes.c_uint64()
+        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
+        return k.value
+
+    def mapsc_stats(self) -> dict:
+        """Of the last map_scores(): n_ref / n_map / n_chromosomes / hits /
+        straddling / sorted_hits / radix_passes / lines_out / output_bytes /
+        ms_*."""
+        s = MapscStats()
+        _check(self._L.starch_mapsc_get_stats(self._h, ctypes.byref(s)), self._h)
+        return {k: getattr(s, k) for k, _ in MapscStats._fields_}
+
     # ---- convert2bed ----
     def convert(self, data: bytes, fmt: str, vcf_class="all", keep_header=False, sort=True) -> bytes:
         """convert2bed: text in format ``fmt`` (a name of CONVERT_FORMATS: GFF3,
@@ -1170,6 +1240,41 @@ def _mapel_options(cols, criterion, skip_unmapped, delim, multidelim):
     o.multidelim_len = len(multidelim)
     ctypes.memmove(ctypes.addressof(o) + MapelOptions.delim.offset, delim, min(len(delim), 8))
     ctypes.memmove(ctypes.addressof(o) + MapelOptions.multidelim.offset, multidelim, min(len(multidelim), 8))
+    return o
+
+
+def mapsc_constants():
+    """(contiguous hits per workgroup of bedmap-scores' segmented reduction,
+    bytes from which an echoed line is copied by a whole wave); no GPU
+    needed."""
+    a, b = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(load().starch_mapsc_constants(ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def _mapsc_options(cols, criterion, prec, kth, skip_unmapped, delim):
+    """starch_mapsc_options; unknown names, a criterion fraction or a kth that
+    is no exact decimal in (0, 1], and a prec that is no integer are
+    ValueError, everything else is left to the library."""
+    cols = list(cols)
+    for c in cols:
+        if c not in MAPSC_COLS:
+            raise ValueError("bedmap-scores: a column must be one of %s" % ", ".join(MAPSC_COLS))
+    if isinstance(prec, bool) or not isinstance(prec, int) or prec < 0:
+        raise ValueError("bedmap-scores: prec is an integer from 0 to 9")
+    e = _mapel_options(("echo",), criterion, skip_unmapped, delim, b";")
+    o = MapscOptions()
+    o.ncols = len(cols)
+    for k, c in enumerate(cols[:12]):
+        o.cols[k] = MAPSC_COLS[c]
+    o.criterion, o.n, o.range, o.frac_num, o.frac_digits = e.criterion, e.n, e.range, e.frac_num, e.frac_digits
+    if kth is not None:
+        o.kth_num, o.kth_digits = mapel_fraction(kth)
+    o.prec = min(prec, 2 ** 32 - 1)
+    o.skip_unmapped = e.skip_unmapped
+    o.delim_len = e.delim_len
+    delim = bytes(delim)
+    ctypes.memmove(ctypes.addressof(o) + MapscOptions.delim.offset, delim, min(len(delim), 8))
     return o
 
 

@@ -539,6 +539,28 @@ int starch_closest_constants(uint32_t* tile_refs, uint32_t* fanout)
 
 // ---- bedmap-elements (include/starch_amd.h; kernels in bed_mapel.hip) ---------------
 namespace {
+// exactly one criterion: the fields of the others are 0 (shared with bedmap-scores)
+bool mapel_criterion_ok(uint32_t c, uint64_t n, uint64_t range, uint64_t frac_num, uint32_t frac_digits, me::MapelOptions* out)
+{
+    if (c > STARCH_MAPEL_CRIT_EXACT) return false;
+    const bool frac = c >= STARCH_MAPEL_CRIT_FRACTION_REF && c <= STARCH_MAPEL_CRIT_FRACTION_EITHER;
+    if ((c == STARCH_MAPEL_CRIT_BP_OVR) != (n != 0)) return false;
+    if (c != STARCH_MAPEL_CRIT_RANGE && range != 0) return false;
+    if (!frac && (frac_num != 0 || frac_digits != 0)) return false;
+    out->criterion = c;
+    out->n = n;
+    out->range = range;
+    if (frac) {
+        if (frac_digits > 9) return false;
+        uint64_t den = 1;
+        for (uint32_t k = 0; k < frac_digits; ++k) den *= 10;
+        if (frac_num == 0 || frac_num > den) return false;
+        out->frac_num = frac_num;
+        out->frac_den = den;
+    }
+    return true;
+}
+
 bool mapel_options_ok(const starch_mapel_options* o, me::MapelOptions* out)
 {
     if (!o || o->ncols < 1 || o->ncols > me::kMaxCols || o->delim_len < 1 || o->delim_len > 8 || o->multidelim_len < 1 ||
@@ -551,24 +573,7 @@ bool mapel_options_ok(const starch_mapel_options* o, me::MapelOptions* out)
         out->cols[k] = o->cols[k];
     }
     out->ncols = o->ncols;
-    // exactly one criterion: the fields of the others are 0
-    const uint32_t c = o->criterion;
-    if (c > STARCH_MAPEL_CRIT_EXACT) return false;
-    const bool frac = c >= STARCH_MAPEL_CRIT_FRACTION_REF && c <= STARCH_MAPEL_CRIT_FRACTION_EITHER;
-    if ((c == STARCH_MAPEL_CRIT_BP_OVR) != (o->n != 0)) return false;
-    if (c != STARCH_MAPEL_CRIT_RANGE && o->range != 0) return false;
-    if (!frac && (o->frac_num != 0 || o->frac_digits != 0)) return false;
-    out->criterion = c;
-    out->n = o->n;
-    out->range = o->range;
-    if (frac) {
-        if (o->frac_digits > 9) return false;
-        uint64_t den = 1;
-        for (uint32_t k = 0; k < o->frac_digits; ++k) den *= 10;
-        if (o->frac_num == 0 || o->frac_num > den) return false;
-        out->frac_num = o->frac_num;
-        out->frac_den = den;
-    }
+    if (!mapel_criterion_ok(o->criterion, o->n, o->range, o->frac_num, o->frac_digits, out)) return false;
     out->skip_unmapped = o->skip_unmapped ? 1 : 0;
     out->delim_len = o->delim_len;
     memcpy(out->delim, o->delim, o->delim_len);
@@ -655,6 +660,118 @@ int starch_mapel_constants(uint32_t* tile_refs, uint32_t* fanout, uint32_t* heav
     if (fanout) *fanout = bc::kFanout;
     if (heavy_threshold) *heavy_threshold = me::kHeavy;
     if (steps_per_hit_bound) *steps_per_hit_bound = me::kStepsPerHit;
+    return STARCH_OK;
+}
+
+}  // extern "C"
+
+// ---- bedmap-scores (include/starch_amd.h; kernels in bed_mapscore.hip) ---------------
+namespace {
+bool mapsc_options_ok(const starch_mapsc_options* o, ms::MapscOptions* out)
+{
+    if (!o || o->ncols < 1 || o->ncols > ms::kMaxCols || o->delim_len < 1 || o->delim_len > 8 || o->prec > 9) return false;
+    uint32_t seen = 0;
+    for (uint32_t k = 0; k < o->ncols; ++k) {
+        if (o->cols[k] > STARCH_MAPSC_MAX_ELEMENT || ((seen >> o->cols[k]) & 1)) return false;
+        seen |= 1u << o->cols[k];
+        out->cols[k] = o->cols[k];
+    }
+    out->ncols = o->ncols;
+    if (!mapel_criterion_ok(o->criterion, o->n, o->range, o->frac_num, o->frac_digits, &out->crit)) return false;
+    if ((seen >> STARCH_MAPSC_KTH) & 1) {
+        if (o->kth_digits > 9) return false;
+        uint64_t den = 1;
+        for (uint32_t k = 0; k < o->kth_digits; ++k) den *= 10;
+        if (o->kth_num == 0 || o->kth_num > den) return false;
+        out->kth_num = o->kth_num;
+        out->kth_den = den;
+    } else if (o->kth_num != 0 || o->kth_digits != 0) return false;
+    out->prec = o->prec;
+    out->skip_unmapped = o->skip_unmapped ? 1 : 0;
+    out->delim_len = o->delim_len;
+    memcpy(out->delim, o->delim, o->delim_len);
+    return true;
+}
+
+void mapsc_run(starch_ctx* c, const ms::MapscOptions& opt, uint64_t len, const std::vector<uint64_t>& in_end, double ms_decode,
+               const std::chrono::steady_clock::time_point& t0)
+{
+    ms::MapscResult r;
+    c->mapsc.run(c->sorter, c->setop, c->mapel, opt, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, c->st, c->setop_out,
+                 r);
+    starch_mapsc_stats& s = c->scstats;
+    s = starch_mapsc_stats{};
+    s.n_ref = r.n_ref;
+    s.n_map = r.n_map;
+    s.n_chromosomes = r.n_chromosomes;
+    s.hits = r.hits;
+    s.straddling = r.straddling;
+    s.sorted_hits = r.sorted_hits;
+    s.radix_passes = r.radix_passes;
+    s.lines_out = r.lines_out;
+    s.output_bytes = r.out_bytes;
+    s.ms_decode = (float)ms_decode;
+    s.ms_parse = r.ms_parse;
+    s.ms_build = r.ms_build;
+    s.ms_query = r.ms_query;
+    s.ms_reduce = r.ms_reduce;
+    s.ms_format = r.ms_format;
+    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->have_scstats = true;
+    publish(c, c->setop_out, r.out_bytes);
+}
+}  // namespace
+
+extern "C" {
+
+int starch_mapsc_host(starch_ctx* c, const starch_setop_input* ref, const starch_setop_input* map,
+                      const starch_mapsc_options* opt)
+{
+    ms::MapscOptions mo;
+    if (!c || !ref || !mapsc_options_ok(opt, &mo)) return STARCH_ERR_ARG;
+    if ((ref->len && !ref->data) || (map && map->len && !map->data)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_scstats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<starch_setop_input> inputs{*ref};
+    if (map) inputs.push_back(*map);
+    std::vector<uint64_t> in_end;
+    const uint64_t len = setop_load_host(c, inputs.data(), inputs.size(), "bedmap-scores", in_end, nullptr);
+    const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    mapsc_run(c, mo, len, in_end, ms_decode, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_mapsc_device(starch_ctx* c, const void* d_bed, const uint64_t* offs, uint64_t ninputs, const starch_mapsc_options* opt)
+{
+    ms::MapscOptions mo;
+    if (!c || !offs || ninputs < 1 || ninputs > 2 || !mapsc_options_ok(opt, &mo)) return STARCH_ERR_ARG;
+    if (!offs_ok(d_bed, offs, ninputs)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_scstats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> in_end;
+    const uint64_t len = setop_load_device(c, d_bed, offs, ninputs, in_end);
+    mapsc_run(c, mo, len, in_end, 0.0, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_mapsc_get_stats(starch_ctx* c, starch_mapsc_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_scstats) return STARCH_ERR_STATE;
+    *out = c->scstats;
+    return STARCH_OK;
+}
+
+int starch_mapsc_constants(uint32_t* tile_hits, uint32_t* wave_copy_threshold)
+{
+    if (tile_hits) *tile_hits = (uint32_t)ms::kTileHits;
+    if (wave_copy_threshold) *wave_copy_threshold = sb::kWaveCopyBytes;
     return STARCH_OK;
 }
 

@@ -499,36 +499,26 @@ MapelWorkspace::~MapelWorkspace()
         if (e) (void)hipEventDestroy(e);
 }
 
-void MapelWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, const MapelOptions& opt, const uint8_t* d_cat,
-                         uint64_t n, const std::vector<uint64_t>& in_end, hipStream_t st, DevBuf& out, MapelResult& res)
+int MapelWorkspace::hits(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, const char* name, const MapelOptions& opt,
+                         const uint8_t* d_cat, uint64_t n, const std::vector<uint64_t>& in_end, hipStream_t st, hipEvent_t* ev3,
+                         HitList& hl)
 {
-    res = MapelResult{};
+    hl = HitList{};
     const uint64_t N = in_end.size();
-    for (auto& e : ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(STARCH_ERR_DEVICE, "hipEventCreate"); }
-    (void)out.as<uint8_t>(64);
-    HIP_CHECK(hipEventRecord(ev[0], st));
-    auto finish = [&](int from) {
-        for (int k = from; k < 5; ++k) HIP_CHECK(hipEventRecord(ev[k], st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_parse, ev[0], ev[1]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_build, ev[1], ev[2]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_query, ev[2], ev[3]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_format, ev[3], ev[4]));
-    };
-    if (n == 0) return finish(1);   // both inputs are empty
+    if (n == 0) return 0;   // both inputs are empty
 
     // 1. parse, ranks, checks; the reference is lines [0, Lr), the map [m0, m0 + Lm)
     std::vector<uint64_t> first;
-    const uint64_t L = lines.stage_lines(sorter, "bedmap-elements", d_cat, n, in_end, st, first);
+    const uint64_t L = lines.stage_lines(sorter, name, d_cat, n, in_end, st, first);
     const uint64_t Lr = first[1], m0 = N == 2 ? Lr : 0, Lm = N == 2 ? L - Lr : L;
     if (Lr + Lm >= (1ull << 32))
-        throw StarchError(STARCH_ERR_ARG, "bedmap-elements: 2^32 lines or more over reference and map");
-    res.n_ref = Lr;
-    res.n_map = Lm;
-    res.n_chromosomes = sorter.n_chromosomes;
-    HIP_CHECK(hipEventRecord(ev[1], st));
-    if (Lr == 0) return finish(2);
+        throw StarchError(STARCH_ERR_ARG, std::string(name) + ": 2^32 lines or more over reference and map");
+    hl.Lr = Lr;
+    hl.Lm = Lm;
+    hl.m0 = m0;
+    hl.n_chromosomes = sorter.n_chromosomes;
+    HIP_CHECK(hipEventRecord(ev3[0], st));
+    if (Lr == 0) return 1;
 
     const uint64_t C = sorter.n_chromosomes;
     const uint32_t* rank = sorter.ln.rank;
@@ -557,9 +547,9 @@ void MapelWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, c
     if (Lm) {
         (void)lines.stage_merge(start + m0, stop + m0, lines.head + m0, Lm, st);
         q.M = lines.incl;
-        bc::build_hier(q.S, Lm, b_hier, st, "bedmap-elements", &q.h);
+        bc::build_hier(q.S, Lm, b_hier, st, name, &q.h);
     }
-    HIP_CHECK(hipEventRecord(ev[2], st));
+    HIP_CHECK(hipEventRecord(ev3[1], st));
 
     // 3. count, scan, fill
     const unsigned qblocks = blocks_for(Lr, kTileRefs);
@@ -574,10 +564,10 @@ void MapelWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, c
     HIP_CHECK(hipMemcpyAsync(counted, scal + S_HEAVY, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     // (a line has fewer than 2^32 hits and there are fewer than 2^32 lines: the sum cannot wrap)
-    if (T >= (1ull << 32)) throw StarchError(STARCH_ERR_ARG, "bedmap-elements: result too large (2^32 hits or more)");
-    res.hits = T;
-    res.heavy_lines = counted[0];
-    res.walk_steps = counted[1];
+    if (T >= (1ull << 32)) throw StarchError(STARCH_ERR_ARG, std::string(name) + ": result too large (2^32 hits or more)");
+    hl.T = T;
+    hl.heavy_lines = counted[0];
+    hl.walk_steps = counted[1];
     uint32_t* H = b_H.as<uint32_t>(T);
     uint32_t* R = b_R.as<uint32_t>(T);
     uint64_t* rmax = b_rmax.as<uint64_t>(Lr);
@@ -590,7 +580,47 @@ void MapelWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, c
         hipLaunchKernelGGL(k_me_find<true>, dim3(qblocks), dim3(kTileRefs), 0, st, q);
         HIP_CHECK(hipGetLastError());
     }
-    HIP_CHECK(hipEventRecord(ev[3], st));
+    HIP_CHECK(hipEventRecord(ev3[2], st));
+    hl.cnt = cnt;
+    hl.hoff = hoff;
+    hl.H = H;
+    hl.R = R;
+    hl.rmax = rmax;
+    return 3;
+}
+
+void MapelWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, const MapelOptions& opt, const uint8_t* d_cat,
+                         uint64_t n, const std::vector<uint64_t>& in_end, hipStream_t st, DevBuf& out, MapelResult& res)
+{
+    res = MapelResult{};
+    const uint64_t N = in_end.size();
+    for (auto& e : ev)
+        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(STARCH_ERR_DEVICE, "hipEventCreate"); }
+    (void)out.as<uint8_t>(64);
+    HIP_CHECK(hipEventRecord(ev[0], st));
+    auto finish = [&](int from) {
+        for (int k = from; k < 5; ++k) HIP_CHECK(hipEventRecord(ev[k], st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        HIP_CHECK(hipEventElapsedTime(&res.ms_parse, ev[0], ev[1]));
+        HIP_CHECK(hipEventElapsedTime(&res.ms_build, ev[1], ev[2]));
+        HIP_CHECK(hipEventElapsedTime(&res.ms_query, ev[2], ev[3]));
+        HIP_CHECK(hipEventElapsedTime(&res.ms_format, ev[3], ev[4]));
+    };
+
+    // 1 to 3. the hit list
+    HitList hl;
+    const int done = hits(sorter, lines, "bedmap-elements", opt, d_cat, n, in_end, st, ev + 1, hl);
+    res.n_ref = hl.Lr;
+    res.n_map = hl.Lm;
+    res.n_chromosomes = hl.n_chromosomes;
+    res.hits = hl.T;
+    res.heavy_lines = hl.heavy_lines;
+    res.walk_steps = hl.walk_steps;
+    if (done < 3) return finish(done + 1);
+    const uint64_t Lr = hl.Lr, m0 = hl.m0, T = hl.T;
+    const uint64_t *start = sorter.ln.start, *stop = sorter.ln.stop, *cnt = hl.cnt, *hoff = hl.hoff, *rmax = hl.rmax;
+    const uint32_t *H = hl.H, *R = hl.R;
+    uint64_t* scal = b_scal.as<uint64_t>(S_COUNT);
 
     // 4. format
     Format f{};

@@ -26,6 +26,7 @@
 #include "bed_map.hpp"
 #include "bed_closest.hpp"
 #include "bed_mapel.hpp"
+#include "bed_mapscore.hpp"
 #include "bed_convert.hpp"
 #include "transform.hpp"
 #include "untransform.hpp"
@@ -234,6 +235,10 @@ struct starch_ctx {
     me::MapelWorkspace mapel;
     starch_mapel_stats estats{};     // the last starch_mapel_* call
     bool have_estats = false;
+    // bedmap-scores (bed_mapscore.hip): reads setop_in, writes setop_out; its hit list is mapel's
+    ms::MapscWorkspace mapsc;
+    starch_mapsc_stats scstats{};    // the last starch_mapsc_* call
+    bool have_scstats = false;
     // convert2bed (bed_convert.hip): reads input (or the caller's HBM), writes
     // setop_out; the sort then fills sort_out
     cv::ConvertWorkspace converter;
