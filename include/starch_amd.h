@@ -1136,6 +1136,114 @@ int starch_convert_get_stats(starch_ctx* ctx, starch_convert_stats* out);
  * sample columns, a kept header line) is left to a whole wave. */
 int starch_convert_constants(uint32_t* block_lines, uint32_t* wave_copy_bytes);
 
+/* ---- sam2bed, psl2bed, rmsk2bed: SAM, PSL and RepeatMasker .out to BED -------------
+ * The three remaining text formats of BEDOPS' convert2bed, converted as
+ * starch_convert_* converts its four: one thread per input line, then the sort
+ * unless no_sort is set, without leaving HBM.  The definitions are modelled on
+ * BEDOPS' convert2bed (its sam2bed, psl2bed and rmsk2bed wrappers) but are
+ * unverified against a BEDOPS binary; the known or possible differences are
+ * marked (*).
+ * Framing.  The input is cut into lines at '\n'; a last line without '\n' is a
+ * line; '\r' is an ordinary byte.  A number is 1 to 19 ASCII digits with a value
+ * up to 2^63-1; a coordinate is written as a plain decimal number, every other
+ * column is copied byte for byte.
+ * Header lines.  An empty line is a header line in all three formats; the others
+ * are named per format.  They are dropped, or with keep_header header line K
+ * (from 0, in input order) becomes
+ *   _header TAB K TAB K+1 TAB <the line>
+ * as starch_convert_* writes it.
+ * Errors.  Any other line that does not fit its format is STARCH_ERR_DATA: the
+ * text is "<command>: line N: <what is wrong>" (sam2bed, psl2bed or rmsk2bed) for
+ * the lowest such line (from 1), and there is no output.
+ *   sam   A line that begins with '@' is a header line.  A record is
+ *         TAB-separated and needs its first six fields: QNAME, FLAG, RNAME, POS,
+ *         MAPQ, CIGAR.  (*) What follows CIGAR (RNEXT to QUAL and the tags) is
+ *         copied byte for byte and is neither counted nor checked; BEDOPS needs
+ *         eleven fields.  FLAG is a decimal number from 0 to 65535.  A record
+ *         with FLAG bit 4 is unmapped: it is dropped and counted, or with
+ *         all_reads written as _unmapped, 0, 1 and then the columns of any
+ *         record, its RNAME, POS and CIGAR unread.  A mapped record needs an
+ *         RNAME that is neither empty nor *, and POS >= 1.  CIGAR is *, or one or
+ *         more pieces of a count of 1 to 9 digits and an operator of MIDNSHP=X.
+ *         The reference length is the sum of the counts of M D N = X, and
+ *         stop = POS-1 + max(1, reference length): *, 5S and 10I give one base, as
+ *         htslib's end position does.  A stop above 2^63-1 is an error.  Output:
+ *         RNAME, POS-1, stop, QNAME, FLAG, strand ('-' when FLAG has bit 16, else
+ *         '+'), MAPQ, then the bytes from CIGAR to the end of the line.  reduced
+ *         writes the first six columns only.  split writes one line per maximal
+ *         run of M D = X operations with a positive reference length: N ends a
+ *         run, with split_deletions D ends one too and is in none; I S H P
+ *         consume nothing and end nothing.  Each line has the run's own start and
+ *         stop and otherwise the record's columns: (*) the whole CIGAR and the
+ *         plain QNAME are kept, where BEDOPS may write a per-piece name.  A record
+ *         without such a run, and an unmapped one, gets its unsplit line.
+ *   psl   When line 1 begins with psLayout, every line up to and including the
+ *         first line that begins with ----- is a header line; without such a
+ *         line that is an error at line 1.  A file that does not begin with
+ *         psLayout has no such header.  A record has exactly 21 TAB-separated
+ *         non-empty fields, matches to tStarts in UCSC's order.  tSize, tStart,
+ *         tEnd and blockCount are numbers, tStart < tEnd, and strand is +, -, or
+ *         two characters each + or -.  Output: tName, tStart, tEnd, qName,
+ *         matches, strand, qSize, misMatches, repMatches, nCount, qNumInsert,
+ *         qBaseInsert, tNumInsert, tBaseInsert, qStart, qEnd, tSize, blockCount,
+ *         blockSizes, qStarts, tStarts.  split writes one line per block k <
+ *         blockCount: [t, t + blockSizes[k]) with t = tStarts[k], or, when the
+ *         strand has two characters and the second is '-', [tSize - t -
+ *         blockSizes[k], tSize - t) (UCSC's reverse-strand coordinates); the other
+ *         columns are the record's.  With split, blockSizes and tStarts must hold
+ *         exactly blockCount comma-terminated numbers, a block of size 0, one that
+ *         exceeds tSize on the reverse strand and a stop above 2^63-1 are errors;
+ *         (*) without split the lists are copied unread.
+ *   rmsk  Tokens are separated by runs of spaces and TABs; leading and trailing
+ *         blanks are ignored.  A line without a token, or whose first token is SW
+ *         or score, is a header line.  A record has 15 tokens, or 16 with the last
+ *         equal to *: SW score, %div, %del, %ins, query, begin, end, (left),
+ *         strand (+ or C), repeat, class/family, three repeat positions, ID.
+ *         begin >= 1 and end >= begin.  Output, TAB-joined: query, begin-1, end,
+ *         repeat, score, strand (C becomes -), %div, %del, %ins, (left),
+ *         class/family, the three positions as written, ID, and * when present.
+ *         (*) The numbers other than begin and end are copied unread.
+ * 2^32 input lines or more, or 2^32 output lines or more, is STARCH_ERR_ARG.  A
+ * NULL context or options, an unknown format, split_deletions without split,
+ * split for rmsk, and split_deletions, all_reads or reduced for a format other
+ * than sam are STARCH_ERR_ARG, answered before anything touches a device. */
+#define STARCH_ALIGN_SAM 0
+#define STARCH_ALIGN_PSL 1
+#define STARCH_ALIGN_RMSK 2
+typedef struct {
+    uint32_t format;            /* STARCH_ALIGN_* */
+    uint32_t split;             /* sam: a line per run; psl: a line per block */
+    uint32_t split_deletions;   /* sam, with split: D ends a run too */
+    uint32_t all_reads;         /* sam: unmapped records become _unmapped lines */
+    uint32_t reduced;           /* sam: the first six columns only */
+    uint32_t keep_header;       /* header lines become _header lines */
+    uint32_t no_sort;           /* leave the lines in input order */
+} starch_align_options;
+/* The BED is read through starch_output_size / _copy / _device. */
+int starch_align_host(starch_ctx* ctx, const void* data, uint64_t n, const starch_align_options* opt);
+int starch_align_device(starch_ctx* ctx, const void* d_data, uint64_t n, const starch_align_options* opt);
+/* Convert, sort (aopt->no_sort is STARCH_ERR_ARG) and encode from the sorted bytes
+ * while they are in HBM, as starch_convert_encode_host does.  sopt == NULL: the
+ * defaults. */
+int starch_align_encode_host(starch_ctx* ctx, const void* data, uint64_t n, const starch_align_options* aopt,
+                             const starch_options* sopt);
+typedef struct {
+    uint64_t input_bytes, input_lines;
+    uint64_t header_lines, records;      /* records: every other line, the unmapped ones too */
+    uint64_t unmapped_dropped;           /* SAM records left out for FLAG bit 4 */
+    uint64_t lines_out, output_bytes;
+    uint64_t sorted;                     /* 1: the sort ran */
+    /* GPU events; ms_total is host clock and holds the upload too */
+    float ms_frame, ms_parse, ms_write, ms_sort, ms_total;
+} starch_align_stats;
+/* Of the last successful starch_align_* call on this context. */
+int starch_align_get_stats(starch_ctx* ctx, starch_align_stats* out);
+/* Sizes the kernels switch on: threads per block of the per-line kernels (one
+ * line each), and the bytes from which a copied tail (CIGAR to the end of a SAM
+ * line, blockCount to the end of a PSL line, a kept header line) is left to a
+ * whole wave. */
+int starch_align_constants(uint32_t* block_lines, uint32_t* wave_copy_bytes);
+
 int starch_output_size(starch_ctx* ctx, uint64_t* n);
 int starch_output_copy(starch_ctx* ctx, void* dst, uint64_t cap);
 int starch_output_device(starch_ctx* ctx, const void** d_ptr);

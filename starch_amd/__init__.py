@@ -21,7 +21,8 @@ __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_arc
            "map_constants", "MAPCOLS", "BEDOPS_OPS", "bedops_constants", "closest_constants",
            "mapel_constants", "mapel_fraction", "MAPEL_COLS", "MAPEL_CRITERIA", "MapelOptions", "MapelStats",
            "mapsc_constants", "MAPSC_COLS", "MapscOptions", "MapscStats",
-           "convert_constants", "CONVERT_FORMATS", "VCF_CLASSES", "ConvertOptions", "ConvertStats"]
+           "convert_constants", "CONVERT_FORMATS", "VCF_CLASSES", "ConvertOptions", "ConvertStats",
+           "align_constants", "ALIGN_FORMATS", "AlignOptions", "AlignStats"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STARCH_AMD_LIB") or os.path.join(_HERE, "_build", "libstarch_amd.so")
@@ -237,6 +238,22 @@ class ConvertStats(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("ms_frame", "ms_parse", "ms_write", "ms_sort", "ms_total")]
 
 
+ALIGN_FORMATS = {"sam": 0, "psl": 1, "rmsk": 2}                                  # STARCH_ALIGN_*
+
+
+class AlignOptions(ctypes.Structure):
+    """starch_align_options: the format and flags of align2bed()."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("format", "split", "split_deletions", "all_reads", "reduced", "keep_header",
+                                               "no_sort")]
+
+
+class AlignStats(ctypes.Structure):
+    """starch_align_stats: the last align2bed()."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("input_bytes", "input_lines", "header_lines", "records", "unmapped_dropped",
+                                               "lines_out", "output_bytes", "sorted")] + \
+               [(n, ctypes.c_float) for n in ("ms_frame", "ms_parse", "ms_write", "ms_sort", "ms_total")]
+
+
 class SortStats(ctypes.Structure):
     """starch_sort_stats: the last sort_bed / sort_check / compress_sorted."""
     _fields_ = [(n, ctypes.c_uint64) for n in ("input_bytes", "n_lines", "n_chromosomes", "already_sorted",
@@ -383,6 +400,12 @@ def load():
                                        ctypes.c_int),
         "starch_convert_get_stats": ([vp, ctypes.POINTER(ConvertStats)], ctypes.c_int),
         "starch_convert_constants": ([ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+        "starch_align_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(AlignOptions)], ctypes.c_int),
+        "starch_align_device": ([vp, vp, u64, ctypes.POINTER(AlignOptions)], ctypes.c_int),
+        "starch_align_encode_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(AlignOptions), ctypes.POINTER(Options)],
+                                     ctypes.c_int),
+        "starch_align_get_stats": ([vp, ctypes.POINTER(AlignStats)], ctypes.c_int),
+        "starch_align_constants": ([ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
         "starch_output_size": ([vp, pu64], ctypes.c_int),
         "starch_output_copy": ([vp, vp, u64], ctypes.c_int),
         "starch_output_device": ([vp, ctypes.POINTER(vp)], ctypes.c_int),
@@ -1067,6 +1090,47 @@ class Starch:
         _check(self._L.starch_convert_get_stats(self._h, ctypes.byref(s)), self._h)
         return {k: getattr(s, k) for k, _ in ConvertStats._fields_}
 
+    # ---- sam2bed, psl2bed, rmsk2bed ----
+    def align2bed(self, data: bytes, fmt: str, split=False, split_deletions=False, all_reads=False, reduced=False,
+                  keep_header=False, sort=True) -> bytes:
+        """sam2bed, psl2bed, rmsk2bed: text in format ``fmt`` (a name of
+        ALIGN_FORMATS: SAM, PSL or RepeatMasker .out) -> BED, in sort_bed()'s
+        order unless ``sort`` is False.  ``split`` writes a line per CIGAR run
+        (sam) or per block (psl); ``split_deletions`` (sam, with split) lets D
+        end a run too; ``all_reads`` (sam) keeps unmapped records as
+        ``_unmapped`` lines; ``reduced`` (sam) writes six columns;
+        ``keep_header`` turns header lines into ``_header`` lines.  The
+        definitions are in include/starch_amd.h.  A line that does not fit its
+        format is StarchError -12 naming its number; a bad argument is -2."""
+        o = _align_options(fmt, split, split_deletions, all_reads, reduced, keep_header, sort)
+        _check(self._L.starch_align_host(self._h, data, len(data), ctypes.byref(o)), self._h)
+        return self._output()
+
+    def align2bed_device(self, d_ptr: int, n: int, fmt: str, split=False, split_deletions=False, all_reads=False,
+                         reduced=False, keep_header=False, sort=True) -> int:
+        """The same for text in HBM; returns the output size (output_device_ptr())."""
+        o = _align_options(fmt, split, split_deletions, all_reads, reduced, keep_header, sort)
+        _check(self._L.starch_align_device(self._h, ctypes.c_void_p(d_ptr), n, ctypes.byref(o)), self._h)
+        k = ctypes.c_uint64()
+        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
+        return k.value
+
+    def compress_aligned(self, data: bytes, fmt: str, split=False, split_deletions=False, all_reads=False, reduced=False,
+                         keep_header=False, emit_index=True) -> bytes:
+        """align2bed, sort and compress without leaving HBM: the archive
+        compress(align2bed(data, fmt, ...)) gives."""
+        o = _align_options(fmt, split, split_deletions, all_reads, reduced, keep_header, True)
+        so = self._opts(emit_index)
+        _check(self._L.starch_align_encode_host(self._h, data, len(data), ctypes.byref(o), ctypes.byref(so)), self._h)
+        return self.archive()
+
+    def align_stats(self) -> dict:
+        """Of the last align2bed(): input_bytes / input_lines / header_lines /
+        records / unmapped_dropped / lines_out / output_bytes / sorted / ms_*."""
+        s = AlignStats()
+        _check(self._L.starch_align_get_stats(self._h, ctypes.byref(s)), self._h)
+        return {k: getattr(s, k) for k, _ in AlignStats._fields_}
+
     def cat(self, archives) -> bytes:
         """starchcat: the archives (bytes, in order) merged into one, with this
         instance's note, block_size_100k and base_counts.  A chromosome held
@@ -1296,6 +1360,31 @@ def _convert_options(fmt, vcf_class, keep_header, sort):
     o = ConvertOptions()
     o.format = CONVERT_FORMATS[fmt]
     o.vcf_class = VCF_CLASSES[vcf_class]
+    o.keep_header = 1 if keep_header else 0
+    o.no_sort = 0 if sort else 1
+    return o
+
+
+def align_constants():
+    """(threads per block of the per-line kernels of sam2bed, psl2bed and
+    rmsk2bed, bytes from which a copied tail is left to a whole wave); no GPU
+    needed."""
+    a, b = ctypes.c_uint32(), ctypes.c_uint32()
+    _check(load().starch_align_constants(ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def _align_options(fmt, split, split_deletions, all_reads, reduced, keep_header, sort):
+    """starch_align_options; an unknown format name is ValueError, the combination of the flags is left to the library."""
+    fmt = fmt.lower() if isinstance(fmt, str) else fmt
+    if fmt not in ALIGN_FORMATS:
+        raise ValueError("align2bed: fmt must be one of %s" % ", ".join(ALIGN_FORMATS))
+    o = AlignOptions()
+    o.format = ALIGN_FORMATS[fmt]
+    o.split = 1 if split else 0
+    o.split_deletions = 1 if split_deletions else 0
+    o.all_reads = 1 if all_reads else 0
+    o.reduced = 1 if reduced else 0
     o.keep_header = 1 if keep_header else 0
     o.no_sort = 0 if sort else 1
     return o

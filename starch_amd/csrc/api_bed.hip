@@ -1,5 +1,5 @@
-// starch_amd/csrc/api_bed.hip -- the C ABI of sort-bed, bedops, bedmap, closest-features, bedmap-elements and
-// convert2bed.
+// starch_amd/csrc/api_bed.hip -- the C ABI of sort-bed, bedops, bedmap, closest-features, bedmap-elements,
+// convert2bed, sam2bed, psl2bed and rmsk2bed.
 #include <string.h>
 
 #include <algorithm>
@@ -875,6 +875,115 @@ int starch_convert_get_stats(starch_ctx* c, starch_convert_stats* out)
 int starch_convert_constants(uint32_t* block_lines, uint32_t* wave_copy_bytes)
 {
     if (block_lines) *block_lines = (uint32_t)cv::kThreads;
+    if (wave_copy_bytes) *wave_copy_bytes = sb::kWaveCopyBytes;
+    return STARCH_OK;
+}
+
+}  // extern "C"
+
+// ---- sam2bed, psl2bed, rmsk2bed (include/starch_amd.h; kernels in bed_align.hip) -----
+namespace {
+bool align_options_ok(const starch_align_options* o, al::AlignOptions* out)
+{
+    if (!o || o->format > STARCH_ALIGN_RMSK) return false;
+    if (o->split_deletions && !o->split) return false;
+    if (o->format == STARCH_ALIGN_RMSK && o->split) return false;
+    if (o->format != STARCH_ALIGN_SAM && (o->split_deletions || o->all_reads || o->reduced)) return false;
+    out->format = o->format;
+    out->split = o->split ? 1 : 0;
+    out->split_deletions = o->split_deletions ? 1 : 0;
+    out->all_reads = o->all_reads ? 1 : 0;
+    out->reduced = o->reduced ? 1 : 0;
+    out->keep_header = o->keep_header ? 1 : 0;
+    return true;
+}
+
+// d[0, n) converted into setop_out and, unless no_sort, sorted from there into sort_out
+void align_run(starch_ctx* c, const al::AlignOptions& opt, bool no_sort, const uint8_t* d, uint64_t n,
+               const std::chrono::steady_clock::time_point& t0)
+{
+    al::AlignResult r;
+    c->aligner.run(c->sorter, opt, d, n, c->st, c->setop_out, r);
+    starch_align_stats& s = c->astats;
+    s = starch_align_stats{};
+    s.input_bytes = n;
+    s.input_lines = r.n_lines;
+    s.header_lines = r.header_lines;
+    s.records = r.records;
+    s.unmapped_dropped = r.unmapped_dropped;
+    s.lines_out = r.lines_out;
+    s.output_bytes = r.out_bytes;
+    s.ms_frame = r.ms_frame;
+    s.ms_parse = r.ms_parse;
+    s.ms_write = r.ms_write;
+    if (no_sort) publish(c, c->setop_out, r.out_bytes);
+    else {
+        sort_run(c, static_cast<const uint8_t*>(c->setop_out.p), r.out_bytes, false);
+        s.sorted = 1;
+        s.ms_sort = c->sstats.ms_total;
+    }
+    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->have_astats = true;
+}
+}  // namespace
+
+extern "C" {
+
+int starch_align_device(starch_ctx* c, const void* d_data, uint64_t n, const starch_align_options* opt)
+{
+    al::AlignOptions ao;
+    if (!c || !align_options_ok(opt, &ao) || (n && !d_data)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_astats = false;
+    align_run(c, ao, opt->no_sort != 0, static_cast<const uint8_t*>(d_data), n, std::chrono::steady_clock::now());
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_align_host(starch_ctx* c, const void* data, uint64_t n, const starch_align_options* opt)
+{
+    al::AlignOptions ao;
+    if (!c || !align_options_ok(opt, &ao) || (n && !data)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->have_astats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    align_run(c, ao, opt->no_sort != 0, sort_upload(c, data, n), n, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_align_encode_host(starch_ctx* c, const void* data, uint64_t n, const starch_align_options* aopt,
+                             const starch_options* sopt)
+{
+    al::AlignOptions ao;
+    if (!c || !align_options_ok(aopt, &ao) || aopt->no_sort || (n && !data)) return STARCH_ERR_ARG;
+    const starch_options o = options_of(sopt);
+    if (!options_ok(o)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have = false;
+    c->have_out = false;
+    c->have_astats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    align_run(c, ao, false, sort_upload(c, data, n), n, t0);
+    // the sorted text is in sort_out, which no encoder stage writes
+    encode_device(c, c->out_dev, c->out_bytes, o);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_align_get_stats(starch_ctx* c, starch_align_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_astats) return STARCH_ERR_STATE;
+    *out = c->astats;
+    return STARCH_OK;
+}
+
+int starch_align_constants(uint32_t* block_lines, uint32_t* wave_copy_bytes)
+{
+    if (block_lines) *block_lines = (uint32_t)al::kThreads;
     if (wave_copy_bytes) *wave_copy_bytes = sb::kWaveCopyBytes;
     return STARCH_OK;
 }

@@ -32,11 +32,12 @@
 
 #include "../../include/starch_amd.h"
 #include "bed_convert.hpp"
+#include "bed_text.hpp"
 
 namespace cv {
 namespace {
 
-constexpr uint64_t kLimit = 0x7fffffffffffffffull;   // the largest coordinate
+using bt::kLimit;
 enum : int { S_BAD = 0, S_FASTA, S_HDR, S_REC, S_DECL, S_LINES, S_BYTES, S_COUNT = 8 };   // device scalars (u64); the first two start as all ones
 enum : uint8_t { C_BAD = 0, C_HEADER, C_REC, C_DECL, C_DATA1, C_DATA2, C_DATA4 };
 enum : uint32_t {
@@ -69,43 +70,17 @@ struct Rec {
     uint32_t vcf_class, keep_header;
 };
 
-__device__ __forceinline__ uint64_t line_beg(const uint64_t* __restrict__ line_end, uint64_t i) { return i ? line_end[i - 1] : 0; }
-
-__device__ __forceinline__ uint32_t dec_digits(uint64_t v)
-{
-    uint32_t d = 1;
-    while (v >= 10) { v /= 10; ++d; }
-    return d;
-}
-
-__device__ __forceinline__ void put_dec(uint8_t* o, uint64_t v, uint32_t d)
-{
-    for (uint32_t k = d; k-- > 0;) { o[k] = (uint8_t)('0' + v % 10); v /= 10; }
-}
-
-// the k bytes at s are the word w
-__device__ __forceinline__ bool is_word(const uint8_t* __restrict__ s, const char* w, uint32_t k)
-{
-    for (uint32_t j = 0; j < k; ++j)
-        if (s[j] != (uint8_t)w[j]) return false;
-    return true;
-}
+using bt::dec_digits;
+using bt::is_blank;
+using bt::is_word;
+using bt::line_beg;
+using bt::Writer;
 
 // decimal field s[b, e): 0, or K_EMPTY, K_DIGIT, K_RANGE (20 digits or more, or above 2^63-1)
 __device__ __forceinline__ uint32_t parse_coord(const uint8_t* __restrict__ s, uint32_t b, uint32_t e, uint64_t* v)
 {
-    if (b == e) return K_EMPTY;
-    for (uint32_t p = b; p < e; ++p)
-        if ((uint32_t)s[p] - '0' > 9u) return K_DIGIT;
-    if (e - b > 19) return K_RANGE;
-    uint64_t x = 0;
-    for (uint32_t p = b; p < e; ++p) x = x * 10 + ((uint32_t)s[p] - '0');   // 19 digits: below 10^19 < 2^64
-    if (x > kLimit) return K_RANGE;
-    *v = x;
-    return 0;
+    return bt::parse_coord<K_EMPTY, K_DIGIT, K_RANGE>(s, b, e, v);
 }
-
-__device__ __forceinline__ bool is_blank(uint8_t c) { return c == ' ' || c == '\t'; }
 
 // ---- 2. classify and measure ---------------------------------------------------------
 struct Line {              // what k_cv_classify leaves of a line
@@ -420,32 +395,6 @@ __global__ void __launch_bounds__(kThreads) k_cv_tally(const Rec r, uint64_t Le,
     }
 }
 
-struct Writer {            // one thread's output cursor, and the tail it leaves to the wave
-    uint8_t* out;
-    uint64_t o;
-    const uint8_t* big_src = nullptr;
-    uint64_t big_dst = 0, big_len = 0;
-    __device__ __forceinline__ void bytes(const uint8_t* __restrict__ s, uint64_t n)
-    {
-        for (uint64_t p = 0; p < n; ++p) out[o + p] = s[p];
-        o += n;
-    }
-    __device__ __forceinline__ void tab() { out[o++] = '\t'; }
-    __device__ __forceinline__ void dec(uint64_t v)
-    {
-        const uint32_t d = dec_digits(v);
-        put_dec(out + o, v, d);
-        o += d;
-    }
-    // the last column and the '\n'
-    __device__ __forceinline__ void tail(const uint8_t* __restrict__ s, uint64_t n)
-    {
-        if (n >= sb::kWaveCopyBytes) { big_src = s; big_dst = o; big_len = n; o += n; }
-        else bytes(s, n);
-        out[o++] = '\n';
-    }
-};
-
 // A thread writes the output lines of its input line, one per round; a tail of
 // kWaveCopyBytes or more is left to the whole wave, line after line.
 template <int kFormat>
@@ -532,14 +481,7 @@ k_cv_write(const Rec r, uint64_t Le, const uint64_t* __restrict__ hord, const ui
                 w.tail(s + f[8], n - f[8]);       // attributes
             }
         }
-        unsigned long long m = __ballot(w.big_len != 0);
-        while (m) {
-            const int l = __ffsll(m) - 1;
-            m &= m - 1;
-            const uint8_t* src = reinterpret_cast<const uint8_t*>(__shfl((uint64_t)reinterpret_cast<uintptr_t>(w.big_src), l, 64));
-            const uint64_t dst = __shfl(w.big_dst, l, 64), len = __shfl(w.big_len, l, 64);
-            for (uint64_t p = lane; p < len; p += 64) out[dst + p] = src[p];
-        }
+        bt::wave_copy_tails(w, out, lane);
     }
 }
 

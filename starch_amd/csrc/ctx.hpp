@@ -27,6 +27,7 @@
 #include "bed_closest.hpp"
 #include "bed_mapel.hpp"
 #include "bed_mapscore.hpp"
+#include "bed_align.hpp"
 #include "bed_convert.hpp"
 #include "transform.hpp"
 #include "untransform.hpp"
@@ -244,6 +245,10 @@ struct starch_ctx {
     cv::ConvertWorkspace converter;
     starch_convert_stats vstats{};   // the last starch_convert_* call
     bool have_vstats = false;
+    // sam2bed, psl2bed, rmsk2bed (bed_align.hip): as convert2bed
+    al::AlignWorkspace aligner;
+    starch_align_stats astats{};     // the last starch_align_* call
+    bool have_astats = false;
     std::string err;
     // last result
     bool have = false;
