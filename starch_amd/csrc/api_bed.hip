@@ -1,5 +1,7 @@
 // starch_amd/csrc/api_bed.hip -- the C ABI of sort-bed, bedops, bedmap, closest-features, bedmap-elements,
-// convert2bed, sam2bed, psl2bed and rmsk2bed.
+// bedmap-scores, convert2bed, sam2bed, psl2bed and rmsk2bed.  The four two-input tools go through pair_host,
+// pair_device and pair_get_stats, the converters through text_call; a tool keeps its option check, its
+// constants and the stats fields that are its own.
 #include <string.h>
 
 #include <algorithm>
@@ -344,6 +346,79 @@ int starch_setop_constants(uint32_t* scan_tile_lines)
 
 }  // extern "C"
 
+// ---- what bedmap, closest-features, bedmap-elements and bedmap-scores share ----------
+// A tool T names its types (Options, Result, Stats), its slot in the context
+// (stats, have), its name in messages, how it runs, and own(): the fields of
+// its stats that no other tool has.
+namespace {
+template <class T>
+void pair_run(starch_ctx* c, const typename T::Options& opt, uint64_t len, const std::vector<uint64_t>& in_end, double ms_decode,
+              const std::chrono::steady_clock::time_point& t0)
+{
+    typename T::Result r;
+    T::run(c, opt, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, r);
+    typename T::Stats& s = T::stats(c);
+    s = typename T::Stats{};
+    s.n_ref = r.n_ref;
+    s.n_chromosomes = r.n_chromosomes;
+    s.lines_out = r.lines_out;
+    s.output_bytes = r.out_bytes;
+    s.ms_decode = (float)ms_decode;
+    s.ms_parse = r.ms_parse;
+    s.ms_build = r.ms_build;
+    s.ms_query = r.ms_query;
+    s.ms_format = r.ms_format;
+    T::own(s, r);
+    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    T::have(c) = true;
+    publish(c, c->setop_out, r.out_bytes);
+}
+
+// the reference and, unless it is NULL, the second input, in host memory; the arguments are checked
+template <class T>
+int pair_host(starch_ctx* c, const typename T::Options& opt, const starch_setop_input* ref, const starch_setop_input* second)
+{
+    GUARD(c)
+    c->have_out = false;
+    T::have(c) = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<starch_setop_input> inputs{*ref};
+    if (second) inputs.push_back(*second);
+    std::vector<uint64_t> in_end;
+    const uint64_t len = setop_load_host(c, inputs.data(), inputs.size(), T::name(), in_end, nullptr);
+    const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    pair_run<T>(c, opt, len, in_end, ms_decode, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+template <class T>
+int pair_device(starch_ctx* c, const typename T::Options& opt, const void* d_bed, const uint64_t* offs, uint64_t ninputs)
+{
+    if (!offs_ok(d_bed, offs, ninputs)) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    T::have(c) = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint64_t> in_end;
+    const uint64_t len = setop_load_device(c, d_bed, offs, ninputs, in_end);
+    pair_run<T>(c, opt, len, in_end, 0.0, t0);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+template <class T>
+int pair_get_stats(starch_ctx* c, typename T::Stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!T::have(c)) return STARCH_ERR_STATE;
+    *out = T::stats(c);
+    return STARCH_OK;
+}
+
+bool input_ok(const starch_setop_input* in) { return !in || !in->len || in->data; }
+}  // namespace
+
 // ---- bedmap (include/starch_amd.h; kernels in bed_map.hip) -------------------------
 namespace {
 bool map_options_ok(const starch_map_options* o, bm::MapOptions* out)
@@ -363,29 +438,24 @@ bool map_options_ok(const starch_map_options* o, bm::MapOptions* out)
     return true;
 }
 
-void map_run(starch_ctx* c, const bm::MapOptions& opt, uint64_t len, const std::vector<uint64_t>& in_end, double ms_decode,
-             const std::chrono::steady_clock::time_point& t0)
-{
-    bm::MapResult r;
-    c->mapper.run(c->sorter, c->setop, opt, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, c->st, c->setop_out, r);
-    starch_map_stats& s = c->mstats;
-    s = starch_map_stats{};
-    s.n_ref = r.n_ref;
-    s.n_map = r.n_map;
-    s.n_chromosomes = r.n_chromosomes;
-    s.map_runs_merged = r.map_runs_merged;
-    s.stops_sorted = r.stops_sorted;
-    s.lines_out = r.lines_out;
-    s.output_bytes = r.out_bytes;
-    s.ms_decode = (float)ms_decode;
-    s.ms_parse = r.ms_parse;
-    s.ms_build = r.ms_build;
-    s.ms_query = r.ms_query;
-    s.ms_format = r.ms_format;
-    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->have_mstats = true;
-    publish(c, c->setop_out, r.out_bytes);
-}
+struct MapTool {
+    typedef bm::MapOptions Options;
+    typedef bm::MapResult Result;
+    typedef starch_map_stats Stats;
+    static const char* name() { return "bedmap"; }
+    static Stats& stats(starch_ctx* c) { return c->mstats; }
+    static bool& have(starch_ctx* c) { return c->have_mstats; }
+    static void run(starch_ctx* c, const Options& o, const uint8_t* d, uint64_t len, const std::vector<uint64_t>& in_end, Result& r)
+    {
+        c->mapper.run(c->sorter, c->setop, o, d, len, in_end, c->st, c->setop_out, r);
+    }
+    static void own(Stats& s, const Result& r)
+    {
+        s.n_map = r.n_map;
+        s.map_runs_merged = r.map_runs_merged;
+        s.stops_sorted = r.stops_sorted;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -394,43 +464,20 @@ int starch_map_host(starch_ctx* c, const starch_setop_input* ref, const starch_s
 {
     bm::MapOptions mo;
     if (!c || !ref || !map_options_ok(opt, &mo)) return STARCH_ERR_ARG;
-    if ((ref->len && !ref->data) || (map && map->len && !map->data)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have_out = false;
-    c->have_mstats = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<starch_setop_input> inputs{*ref};
-    if (map) inputs.push_back(*map);
-    std::vector<uint64_t> in_end;
-    const uint64_t len = setop_load_host(c, inputs.data(), inputs.size(), "bedmap", in_end, nullptr);
-    const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    map_run(c, mo, len, in_end, ms_decode, t0);
-    return STARCH_OK;
-    END_GUARD(c)
+    if (!input_ok(ref) || !input_ok(map)) return STARCH_ERR_ARG;
+    return pair_host<MapTool>(c, mo, ref, map);
 }
 
 int starch_map_device(starch_ctx* c, const void* d_bed, const uint64_t* offs, uint64_t ninputs, const starch_map_options* opt)
 {
     bm::MapOptions mo;
     if (!c || !offs || ninputs < 1 || ninputs > 2 || !map_options_ok(opt, &mo)) return STARCH_ERR_ARG;
-    if (!offs_ok(d_bed, offs, ninputs)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have_out = false;
-    c->have_mstats = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<uint64_t> in_end;
-    const uint64_t len = setop_load_device(c, d_bed, offs, ninputs, in_end);
-    map_run(c, mo, len, in_end, 0.0, t0);
-    return STARCH_OK;
-    END_GUARD(c)
+    return pair_device<MapTool>(c, mo, d_bed, offs, ninputs);
 }
 
 int starch_map_get_stats(starch_ctx* c, starch_map_stats* out)
 {
-    if (!c || !out) return STARCH_ERR_ARG;
-    if (!c->have_mstats) return STARCH_ERR_STATE;
-    *out = c->mstats;
-    return STARCH_OK;
+    return pair_get_stats<MapTool>(c, out);
 }
 
 int starch_map_constants(uint32_t* tile_refs, uint32_t* lds_window)
@@ -457,30 +504,25 @@ bool closest_options_ok(const starch_closest_options* o, bc::ClosestOptions* out
     return true;
 }
 
-void closest_run(starch_ctx* c, const bc::ClosestOptions& opt, uint64_t len, const std::vector<uint64_t>& in_end,
-                 double ms_decode, const std::chrono::steady_clock::time_point& t0)
-{
-    bc::ClosestResult r;
-    c->closer.run(c->sorter, c->setop, opt, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, c->st, c->setop_out, r);
-    starch_closest_stats& s = c->kstats;
-    s = starch_closest_stats{};
-    s.n_ref = r.n_ref;
-    s.n_query = r.n_query;
-    s.n_chromosomes = r.n_chromosomes;
-    s.stops_sorted = r.stops_sorted;
-    s.left_na = r.left_na;
-    s.right_na = r.right_na;
-    s.lines_out = r.lines_out;
-    s.output_bytes = r.out_bytes;
-    s.ms_decode = (float)ms_decode;
-    s.ms_parse = r.ms_parse;
-    s.ms_build = r.ms_build;
-    s.ms_query = r.ms_query;
-    s.ms_format = r.ms_format;
-    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->have_kstats = true;
-    publish(c, c->setop_out, r.out_bytes);
-}
+struct ClosestTool {
+    typedef bc::ClosestOptions Options;
+    typedef bc::ClosestResult Result;
+    typedef starch_closest_stats Stats;
+    static const char* name() { return "closest-features"; }
+    static Stats& stats(starch_ctx* c) { return c->kstats; }
+    static bool& have(starch_ctx* c) { return c->have_kstats; }
+    static void run(starch_ctx* c, const Options& o, const uint8_t* d, uint64_t len, const std::vector<uint64_t>& in_end, Result& r)
+    {
+        c->closer.run(c->sorter, c->setop, o, d, len, in_end, c->st, c->setop_out, r);
+    }
+    static void own(Stats& s, const Result& r)
+    {
+        s.n_query = r.n_query;
+        s.stops_sorted = r.stops_sorted;
+        s.left_na = r.left_na;
+        s.right_na = r.right_na;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -490,42 +532,20 @@ int starch_closest_host(starch_ctx* c, const starch_setop_input* ref, const star
 {
     bc::ClosestOptions co;
     if (!c || !ref || !query || !closest_options_ok(opt, &co)) return STARCH_ERR_ARG;
-    if ((ref->len && !ref->data) || (query->len && !query->data)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have_out = false;
-    c->have_kstats = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    const starch_setop_input inputs[2] = {*ref, *query};
-    std::vector<uint64_t> in_end;
-    const uint64_t len = setop_load_host(c, inputs, 2, "closest-features", in_end, nullptr);
-    const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    closest_run(c, co, len, in_end, ms_decode, t0);
-    return STARCH_OK;
-    END_GUARD(c)
+    if (!input_ok(ref) || !input_ok(query)) return STARCH_ERR_ARG;
+    return pair_host<ClosestTool>(c, co, ref, query);
 }
 
 int starch_closest_device(starch_ctx* c, const void* d_bed, const uint64_t* offs, const starch_closest_options* opt)
 {
     bc::ClosestOptions co;
     if (!c || !offs || !closest_options_ok(opt, &co)) return STARCH_ERR_ARG;
-    if (!offs_ok(d_bed, offs, 2)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have_out = false;
-    c->have_kstats = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<uint64_t> in_end;
-    const uint64_t len = setop_load_device(c, d_bed, offs, 2, in_end);
-    closest_run(c, co, len, in_end, 0.0, t0);
-    return STARCH_OK;
-    END_GUARD(c)
+    return pair_device<ClosestTool>(c, co, d_bed, offs, 2);
 }
 
 int starch_closest_get_stats(starch_ctx* c, starch_closest_stats* out)
 {
-    if (!c || !out) return STARCH_ERR_ARG;
-    if (!c->have_kstats) return STARCH_ERR_STATE;
-    *out = c->kstats;
-    return STARCH_OK;
+    return pair_get_stats<ClosestTool>(c, out);
 }
 
 int starch_closest_constants(uint32_t* tile_refs, uint32_t* fanout)
@@ -582,30 +602,25 @@ bool mapel_options_ok(const starch_mapel_options* o, me::MapelOptions* out)
     return true;
 }
 
-void mapel_run(starch_ctx* c, const me::MapelOptions& opt, uint64_t len, const std::vector<uint64_t>& in_end, double ms_decode,
-               const std::chrono::steady_clock::time_point& t0)
-{
-    me::MapelResult r;
-    c->mapel.run(c->sorter, c->setop, opt, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, c->st, c->setop_out, r);
-    starch_mapel_stats& s = c->estats;
-    s = starch_mapel_stats{};
-    s.n_ref = r.n_ref;
-    s.n_map = r.n_map;
-    s.n_chromosomes = r.n_chromosomes;
-    s.hits = r.hits;
-    s.heavy_lines = r.heavy_lines;
-    s.walk_steps = r.walk_steps;
-    s.lines_out = r.lines_out;
-    s.output_bytes = r.out_bytes;
-    s.ms_decode = (float)ms_decode;
-    s.ms_parse = r.ms_parse;
-    s.ms_build = r.ms_build;
-    s.ms_query = r.ms_query;
-    s.ms_format = r.ms_format;
-    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->have_estats = true;
-    publish(c, c->setop_out, r.out_bytes);
-}
+struct MapelTool {
+    typedef me::MapelOptions Options;
+    typedef me::MapelResult Result;
+    typedef starch_mapel_stats Stats;
+    static const char* name() { return "bedmap-elements"; }
+    static Stats& stats(starch_ctx* c) { return c->estats; }
+    static bool& have(starch_ctx* c) { return c->have_estats; }
+    static void run(starch_ctx* c, const Options& o, const uint8_t* d, uint64_t len, const std::vector<uint64_t>& in_end, Result& r)
+    {
+        c->mapel.run(c->sorter, c->setop, o, d, len, in_end, c->st, c->setop_out, r);
+    }
+    static void own(Stats& s, const Result& r)
+    {
+        s.n_map = r.n_map;
+        s.hits = r.hits;
+        s.heavy_lines = r.heavy_lines;
+        s.walk_steps = r.walk_steps;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -615,43 +630,20 @@ int starch_mapel_host(starch_ctx* c, const starch_setop_input* ref, const starch
 {
     me::MapelOptions mo;
     if (!c || !ref || !mapel_options_ok(opt, &mo)) return STARCH_ERR_ARG;
-    if ((ref->len && !ref->data) || (map && map->len && !map->data)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have_out = false;
-    c->have_estats = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<starch_setop_input> inputs{*ref};
-    if (map) inputs.push_back(*map);
-    std::vector<uint64_t> in_end;
-    const uint64_t len = setop_load_host(c, inputs.data(), inputs.size(), "bedmap-elements", in_end, nullptr);
-    const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    mapel_run(c, mo, len, in_end, ms_decode, t0);
-    return STARCH_OK;
-    END_GUARD(c)
+    if (!input_ok(ref) || !input_ok(map)) return STARCH_ERR_ARG;
+    return pair_host<MapelTool>(c, mo, ref, map);
 }
 
 int starch_mapel_device(starch_ctx* c, const void* d_bed, const uint64_t* offs, uint64_t ninputs, const starch_mapel_options* opt)
 {
     me::MapelOptions mo;
     if (!c || !offs || ninputs < 1 || ninputs > 2 || !mapel_options_ok(opt, &mo)) return STARCH_ERR_ARG;
-    if (!offs_ok(d_bed, offs, ninputs)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have_out = false;
-    c->have_estats = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<uint64_t> in_end;
-    const uint64_t len = setop_load_device(c, d_bed, offs, ninputs, in_end);
-    mapel_run(c, mo, len, in_end, 0.0, t0);
-    return STARCH_OK;
-    END_GUARD(c)
+    return pair_device<MapelTool>(c, mo, d_bed, offs, ninputs);
 }
 
 int starch_mapel_get_stats(starch_ctx* c, starch_mapel_stats* out)
 {
-    if (!c || !out) return STARCH_ERR_ARG;
-    if (!c->have_estats) return STARCH_ERR_STATE;
-    *out = c->estats;
-    return STARCH_OK;
+    return pair_get_stats<MapelTool>(c, out);
 }
 
 int starch_mapel_constants(uint32_t* tile_refs, uint32_t* fanout, uint32_t* heavy_threshold, uint32_t* steps_per_hit_bound)
@@ -693,33 +685,27 @@ bool mapsc_options_ok(const starch_mapsc_options* o, ms::MapscOptions* out)
     return true;
 }
 
-void mapsc_run(starch_ctx* c, const ms::MapscOptions& opt, uint64_t len, const std::vector<uint64_t>& in_end, double ms_decode,
-               const std::chrono::steady_clock::time_point& t0)
-{
-    ms::MapscResult r;
-    c->mapsc.run(c->sorter, c->setop, c->mapel, opt, static_cast<const uint8_t*>(c->setop_in.p), len, in_end, c->st, c->setop_out,
-                 r);
-    starch_mapsc_stats& s = c->scstats;
-    s = starch_mapsc_stats{};
-    s.n_ref = r.n_ref;
-    s.n_map = r.n_map;
-    s.n_chromosomes = r.n_chromosomes;
-    s.hits = r.hits;
-    s.straddling = r.straddling;
-    s.sorted_hits = r.sorted_hits;
-    s.radix_passes = r.radix_passes;
-    s.lines_out = r.lines_out;
-    s.output_bytes = r.out_bytes;
-    s.ms_decode = (float)ms_decode;
-    s.ms_parse = r.ms_parse;
-    s.ms_build = r.ms_build;
-    s.ms_query = r.ms_query;
-    s.ms_reduce = r.ms_reduce;
-    s.ms_format = r.ms_format;
-    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->have_scstats = true;
-    publish(c, c->setop_out, r.out_bytes);
-}
+struct MapscTool {
+    typedef ms::MapscOptions Options;
+    typedef ms::MapscResult Result;
+    typedef starch_mapsc_stats Stats;
+    static const char* name() { return "bedmap-scores"; }
+    static Stats& stats(starch_ctx* c) { return c->scstats; }
+    static bool& have(starch_ctx* c) { return c->have_scstats; }
+    static void run(starch_ctx* c, const Options& o, const uint8_t* d, uint64_t len, const std::vector<uint64_t>& in_end, Result& r)
+    {
+        c->mapsc.run(c->sorter, c->setop, c->mapel, o, d, len, in_end, c->st, c->setop_out, r);
+    }
+    static void own(Stats& s, const Result& r)
+    {
+        s.n_map = r.n_map;
+        s.hits = r.hits;
+        s.straddling = r.straddling;
+        s.sorted_hits = r.sorted_hits;
+        s.radix_passes = r.radix_passes;
+        s.ms_reduce = r.ms_reduce;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -729,43 +715,20 @@ int starch_mapsc_host(starch_ctx* c, const starch_setop_input* ref, const starch
 {
     ms::MapscOptions mo;
     if (!c || !ref || !mapsc_options_ok(opt, &mo)) return STARCH_ERR_ARG;
-    if ((ref->len && !ref->data) || (map && map->len && !map->data)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have_out = false;
-    c->have_scstats = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<starch_setop_input> inputs{*ref};
-    if (map) inputs.push_back(*map);
-    std::vector<uint64_t> in_end;
-    const uint64_t len = setop_load_host(c, inputs.data(), inputs.size(), "bedmap-scores", in_end, nullptr);
-    const double ms_decode = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    mapsc_run(c, mo, len, in_end, ms_decode, t0);
-    return STARCH_OK;
-    END_GUARD(c)
+    if (!input_ok(ref) || !input_ok(map)) return STARCH_ERR_ARG;
+    return pair_host<MapscTool>(c, mo, ref, map);
 }
 
 int starch_mapsc_device(starch_ctx* c, const void* d_bed, const uint64_t* offs, uint64_t ninputs, const starch_mapsc_options* opt)
 {
     ms::MapscOptions mo;
     if (!c || !offs || ninputs < 1 || ninputs > 2 || !mapsc_options_ok(opt, &mo)) return STARCH_ERR_ARG;
-    if (!offs_ok(d_bed, offs, ninputs)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have_out = false;
-    c->have_scstats = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<uint64_t> in_end;
-    const uint64_t len = setop_load_device(c, d_bed, offs, ninputs, in_end);
-    mapsc_run(c, mo, len, in_end, 0.0, t0);
-    return STARCH_OK;
-    END_GUARD(c)
+    return pair_device<MapscTool>(c, mo, d_bed, offs, ninputs);
 }
 
 int starch_mapsc_get_stats(starch_ctx* c, starch_mapsc_stats* out)
 {
-    if (!c || !out) return STARCH_ERR_ARG;
-    if (!c->have_scstats) return STARCH_ERR_STATE;
-    *out = c->scstats;
-    return STARCH_OK;
+    return pair_get_stats<MapscTool>(c, out);
 }
 
 int starch_mapsc_constants(uint32_t* tile_hits, uint32_t* wave_copy_threshold)
@@ -776,6 +739,55 @@ int starch_mapsc_constants(uint32_t* tile_hits, uint32_t* wave_copy_threshold)
 }
 
 }  // extern "C"
+
+// ---- what convert2bed and sam2bed, psl2bed, rmsk2bed share ---------------------------
+// A tool T is as above; run() converts d[0, n) into setop_out.
+namespace {
+// d[0, n) converted into setop_out and, unless no_sort, sorted from there into sort_out
+template <class T>
+void text_run(starch_ctx* c, const typename T::Options& opt, bool no_sort, const uint8_t* d, uint64_t n,
+              const std::chrono::steady_clock::time_point& t0)
+{
+    typename T::Result r;
+    T::run(c, opt, d, n, r);
+    typename T::Stats& s = T::stats(c);
+    s = typename T::Stats{};
+    s.input_bytes = n;
+    s.input_lines = r.n_lines;
+    s.header_lines = r.header_lines;
+    s.lines_out = r.lines_out;
+    s.output_bytes = r.out_bytes;
+    s.ms_frame = r.ms_frame;
+    s.ms_parse = r.ms_parse;
+    s.ms_write = r.ms_write;
+    T::own(s, r);
+    if (no_sort) publish(c, c->setop_out, r.out_bytes);
+    else {
+        sort_run(c, static_cast<const uint8_t*>(c->setop_out.p), r.out_bytes, false);
+        s.sorted = 1;
+        s.ms_sort = c->sstats.ms_total;
+    }
+    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    T::have(c) = true;
+}
+
+// the checked call: the text in HBM (host false) or in host memory; sopt: encode the sorted result with it
+template <class T>
+int text_call(starch_ctx* c, const typename T::Options& opt, bool no_sort, const void* data, uint64_t n, bool host,
+              const starch_options* sopt)
+{
+    GUARD(c)
+    if (sopt) c->have = false;
+    c->have_out = false;
+    T::have(c) = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    text_run<T>(c, opt, no_sort, host ? sort_upload(c, data, n) : static_cast<const uint8_t*>(data), n, t0);
+    // the sorted text is in sort_out, which no encoder stage writes
+    if (sopt) encode_device(c, c->out_dev, c->out_bytes, *sopt);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+}  // namespace
 
 // ---- convert2bed (include/starch_amd.h; kernels in bed_convert.hip) ------------------
 namespace {
@@ -789,33 +801,22 @@ bool convert_options_ok(const starch_convert_options* o, cv::ConvertOptions* out
     return true;
 }
 
-// d[0, n) converted into setop_out and, unless no_sort, sorted from there into sort_out
-void convert_run(starch_ctx* c, const cv::ConvertOptions& opt, bool no_sort, const uint8_t* d, uint64_t n,
-                 const std::chrono::steady_clock::time_point& t0)
-{
-    cv::ConvertResult r;
-    c->converter.run(c->sorter, opt, d, n, c->st, c->setop_out, r);
-    starch_convert_stats& s = c->vstats;
-    s = starch_convert_stats{};
-    s.input_bytes = n;
-    s.input_lines = r.n_lines;
-    s.header_lines = r.header_lines;
-    s.data_lines = r.data_lines;
-    s.declarations = r.declarations;
-    s.lines_out = r.lines_out;
-    s.output_bytes = r.out_bytes;
-    s.ms_frame = r.ms_frame;
-    s.ms_parse = r.ms_parse;
-    s.ms_write = r.ms_write;
-    if (no_sort) publish(c, c->setop_out, r.out_bytes);
-    else {
-        sort_run(c, static_cast<const uint8_t*>(c->setop_out.p), r.out_bytes, false);
-        s.sorted = 1;
-        s.ms_sort = c->sstats.ms_total;
+struct ConvertTool {
+    typedef cv::ConvertOptions Options;
+    typedef cv::ConvertResult Result;
+    typedef starch_convert_stats Stats;
+    static Stats& stats(starch_ctx* c) { return c->vstats; }
+    static bool& have(starch_ctx* c) { return c->have_vstats; }
+    static void run(starch_ctx* c, const Options& o, const uint8_t* d, uint64_t n, Result& r)
+    {
+        c->converter.run(c->sorter, o, d, n, c->st, c->setop_out, r);
     }
-    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->have_vstats = true;
-}
+    static void own(Stats& s, const Result& r)
+    {
+        s.data_lines = r.data_lines;
+        s.declarations = r.declarations;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -824,25 +825,14 @@ int starch_convert_device(starch_ctx* c, const void* d_data, uint64_t n, const s
 {
     cv::ConvertOptions co;
     if (!c || !convert_options_ok(opt, &co) || (n && !d_data)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have_out = false;
-    c->have_vstats = false;
-    convert_run(c, co, opt->no_sort != 0, static_cast<const uint8_t*>(d_data), n, std::chrono::steady_clock::now());
-    return STARCH_OK;
-    END_GUARD(c)
+    return text_call<ConvertTool>(c, co, opt->no_sort != 0, d_data, n, false, nullptr);
 }
 
 int starch_convert_host(starch_ctx* c, const void* data, uint64_t n, const starch_convert_options* opt)
 {
     cv::ConvertOptions co;
     if (!c || !convert_options_ok(opt, &co) || (n && !data)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have_out = false;
-    c->have_vstats = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    convert_run(c, co, opt->no_sort != 0, sort_upload(c, data, n), n, t0);
-    return STARCH_OK;
-    END_GUARD(c)
+    return text_call<ConvertTool>(c, co, opt->no_sort != 0, data, n, true, nullptr);
 }
 
 int starch_convert_encode_host(starch_ctx* c, const void* data, uint64_t n, const starch_convert_options* copt,
@@ -852,24 +842,12 @@ int starch_convert_encode_host(starch_ctx* c, const void* data, uint64_t n, cons
     if (!c || !convert_options_ok(copt, &co) || copt->no_sort || (n && !data)) return STARCH_ERR_ARG;
     const starch_options o = options_of(sopt);
     if (!options_ok(o)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have = false;
-    c->have_out = false;
-    c->have_vstats = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    convert_run(c, co, false, sort_upload(c, data, n), n, t0);
-    // the sorted text is in sort_out, which no encoder stage writes
-    encode_device(c, c->out_dev, c->out_bytes, o);
-    return STARCH_OK;
-    END_GUARD(c)
+    return text_call<ConvertTool>(c, co, false, data, n, true, &o);
 }
 
 int starch_convert_get_stats(starch_ctx* c, starch_convert_stats* out)
 {
-    if (!c || !out) return STARCH_ERR_ARG;
-    if (!c->have_vstats) return STARCH_ERR_STATE;
-    *out = c->vstats;
-    return STARCH_OK;
+    return pair_get_stats<ConvertTool>(c, out);
 }
 
 int starch_convert_constants(uint32_t* block_lines, uint32_t* wave_copy_bytes)
@@ -898,33 +876,22 @@ bool align_options_ok(const starch_align_options* o, al::AlignOptions* out)
     return true;
 }
 
-// d[0, n) converted into setop_out and, unless no_sort, sorted from there into sort_out
-void align_run(starch_ctx* c, const al::AlignOptions& opt, bool no_sort, const uint8_t* d, uint64_t n,
-               const std::chrono::steady_clock::time_point& t0)
-{
-    al::AlignResult r;
-    c->aligner.run(c->sorter, opt, d, n, c->st, c->setop_out, r);
-    starch_align_stats& s = c->astats;
-    s = starch_align_stats{};
-    s.input_bytes = n;
-    s.input_lines = r.n_lines;
-    s.header_lines = r.header_lines;
-    s.records = r.records;
-    s.unmapped_dropped = r.unmapped_dropped;
-    s.lines_out = r.lines_out;
-    s.output_bytes = r.out_bytes;
-    s.ms_frame = r.ms_frame;
-    s.ms_parse = r.ms_parse;
-    s.ms_write = r.ms_write;
-    if (no_sort) publish(c, c->setop_out, r.out_bytes);
-    else {
-        sort_run(c, static_cast<const uint8_t*>(c->setop_out.p), r.out_bytes, false);
-        s.sorted = 1;
-        s.ms_sort = c->sstats.ms_total;
+struct AlignTool {
+    typedef al::AlignOptions Options;
+    typedef al::AlignResult Result;
+    typedef starch_align_stats Stats;
+    static Stats& stats(starch_ctx* c) { return c->astats; }
+    static bool& have(starch_ctx* c) { return c->have_astats; }
+    static void run(starch_ctx* c, const Options& o, const uint8_t* d, uint64_t n, Result& r)
+    {
+        c->aligner.run(c->sorter, o, d, n, c->st, c->setop_out, r);
     }
-    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    c->have_astats = true;
-}
+    static void own(Stats& s, const Result& r)
+    {
+        s.records = r.records;
+        s.unmapped_dropped = r.unmapped_dropped;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -933,25 +900,14 @@ int starch_align_device(starch_ctx* c, const void* d_data, uint64_t n, const sta
 {
     al::AlignOptions ao;
     if (!c || !align_options_ok(opt, &ao) || (n && !d_data)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have_out = false;
-    c->have_astats = false;
-    align_run(c, ao, opt->no_sort != 0, static_cast<const uint8_t*>(d_data), n, std::chrono::steady_clock::now());
-    return STARCH_OK;
-    END_GUARD(c)
+    return text_call<AlignTool>(c, ao, opt->no_sort != 0, d_data, n, false, nullptr);
 }
 
 int starch_align_host(starch_ctx* c, const void* data, uint64_t n, const starch_align_options* opt)
 {
     al::AlignOptions ao;
     if (!c || !align_options_ok(opt, &ao) || (n && !data)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have_out = false;
-    c->have_astats = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    align_run(c, ao, opt->no_sort != 0, sort_upload(c, data, n), n, t0);
-    return STARCH_OK;
-    END_GUARD(c)
+    return text_call<AlignTool>(c, ao, opt->no_sort != 0, data, n, true, nullptr);
 }
 
 int starch_align_encode_host(starch_ctx* c, const void* data, uint64_t n, const starch_align_options* aopt,
@@ -961,24 +917,12 @@ int starch_align_encode_host(starch_ctx* c, const void* data, uint64_t n, const 
     if (!c || !align_options_ok(aopt, &ao) || aopt->no_sort || (n && !data)) return STARCH_ERR_ARG;
     const starch_options o = options_of(sopt);
     if (!options_ok(o)) return STARCH_ERR_ARG;
-    GUARD(c)
-    c->have = false;
-    c->have_out = false;
-    c->have_astats = false;
-    const auto t0 = std::chrono::steady_clock::now();
-    align_run(c, ao, false, sort_upload(c, data, n), n, t0);
-    // the sorted text is in sort_out, which no encoder stage writes
-    encode_device(c, c->out_dev, c->out_bytes, o);
-    return STARCH_OK;
-    END_GUARD(c)
+    return text_call<AlignTool>(c, ao, false, data, n, true, &o);
 }
 
 int starch_align_get_stats(starch_ctx* c, starch_align_stats* out)
 {
-    if (!c || !out) return STARCH_ERR_ARG;
-    if (!c->have_astats) return STARCH_ERR_STATE;
-    *out = c->astats;
-    return STARCH_OK;
+    return pair_get_stats<AlignTool>(c, out);
 }
 
 int starch_align_constants(uint32_t* block_lines, uint32_t* wave_copy_bytes)

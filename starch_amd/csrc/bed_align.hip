@@ -56,8 +56,6 @@ constexpr uint32_t kMaxSlots = kSlotsPsl;
 
 constexpr uint32_t slots_of(int format) { return format == STARCH_ALIGN_SAM ? kSlotsSam : (format == STARCH_ALIGN_PSL ? kSlotsPsl : 0u); }
 
-inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return (unsigned)ceil_div(items, per_block); }
-
 struct Rec {
     const uint8_t* in;
     const uint64_t* line_end;
@@ -408,7 +406,7 @@ k_al_write(const Rec r, const uint64_t* __restrict__ hord, const uint64_t* __res
 #pragma unroll
     for (uint32_t k = 0; k < kSlots; ++k) f[k + 1] = nout ? r.fo[(uint64_t)k * r.L + i] : 0u;
     uint64_t start = nout ? r.a[i] : 0, stop = nout ? r.b[i] : 0;
-    Writer w{out, nout ? off[i] : 0};
+    Writer<> w{out, nout ? off[i] : 0};
     // where the walks of a split record stand
     CigarWalk cw{0, start, 0};
     const bool psl_split = kFormat == STARCH_ALIGN_PSL && r.split && cls == C_REC;
@@ -427,7 +425,7 @@ k_al_write(const Rec r, const uint64_t* __restrict__ hord, const uint64_t* __res
         if (cls == C_REC) nt = tokens16(s, n, ts, te);
     }
     for (uint32_t round = 0; __ballot(round < nout) != 0; ++round) {
-        w.big_len = 0;
+        w.big_len[0] = 0;
         if (round < nout) {
             if (cls == C_HEADER) {
                 const uint64_t k = hord[i];
@@ -556,33 +554,19 @@ const char* command_of(uint32_t format)
     return format == STARCH_ALIGN_SAM ? "sam2bed" : (format == STARCH_ALIGN_PSL ? "psl2bed" : "rmsk2bed");
 }
 
-AlignWorkspace::~AlignWorkspace()
-{
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-}
-
 void AlignWorkspace::run(sb::SortWorkspace& sorter, const AlignOptions& opt, const uint8_t* d_in, uint64_t n, hipStream_t st,
                          DevBuf& out, AlignResult& res)
 {
     res = AlignResult{};
-    for (auto& e : ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(STARCH_ERR_DEVICE, "hipEventCreate"); }
     (void)out.as<uint8_t>(64);
-    HIP_CHECK(hipEventRecord(ev[0], st));
-    auto finish = [&](int from) {
-        for (int k = from; k < 4; ++k) HIP_CHECK(hipEventRecord(ev[k], st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_frame, ev[0], ev[1]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_parse, ev[1], ev[2]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_write, ev[2], ev[3]));
-    };
+    timer.start(st);
+    auto finish = [&](int from) { timer.finish(from, st, {&res.ms_frame, &res.ms_parse, &res.ms_write}); };
     if (n == 0) return finish(1);
 
     // 1. framing
     const uint64_t L = sorter.stage_frame(d_in, n, st);
     res.n_lines = L;
-    HIP_CHECK(hipEventRecord(ev[1], st));
+    timer.mark(1, st);
 
     // 2, 3. the PSL header's end; classify and measure
     const uint32_t slots = opt.format == STARCH_ALIGN_SAM ? kSlotsSam : (opt.format == STARCH_ALIGN_PSL ? kSlotsPsl : 0u);
@@ -637,7 +621,7 @@ void AlignWorkspace::run(sb::SortWorkspace& sorter, const AlignOptions& opt, con
     res.unmapped_dropped = tot[S_DROPPED];
     if (tot[S_LINES] >= (1ull << 32))
         throw StarchError(STARCH_ERR_ARG, std::string(command_of(opt.format)) + ": 2^32 output lines or more");
-    HIP_CHECK(hipEventRecord(ev[2], st));
+    timer.mark(2, st);
     const uint64_t bytes = tot[S_BYTES];
     if (bytes) {
         uint8_t* o = out.as<uint8_t>(bytes + 64);

@@ -27,7 +27,9 @@
 //                 down into the item that does, kFanout items per level at most.
 //                 no_overlaps: the line of the entry before upper(B, s).
 //      closest drops the farther of the two (a tie drops the right one).
-//   4. format: k_bc_len, an exclusive sum, k_bc_write.
+//   4. format: k_bc_len, an exclusive sum, k_bc_write (the writer and its wave
+//      copy: bed_text.hpp; the host steps between the two kernels: format_tail
+//      in common.hpp; both shared with every BED command).
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -36,6 +38,7 @@
 #include "bed_closest.hpp"
 #include "bed_hier.hpp"
 #include "bed_search.hpp"
+#include "bed_text.hpp"
 
 namespace bc {
 namespace {
@@ -47,7 +50,8 @@ constexpr int kThreads = 256;
 constexpr uint32_t kNA = ~0u;
 enum : int { S_BYTES = 0, S_LEFT_NA, S_RIGHT_NA, S_COUNT = 4 };   // device scalars (u64)
 
-inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return (unsigned)ceil_div(items, per_block); }
+using bt::dec_digits;
+using bt::line_beg;
 
 // ---- 2. query arrays (the hierarchy's level kernel and builder: bed_hier.hpp) ----------
 __global__ void __launch_bounds__(kThreads)
@@ -151,18 +155,6 @@ k_bc_query(const Query q)
 }
 
 // ---- 4. format ------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t dec_digits(uint64_t v)
-{
-    uint32_t d = 1;
-    while (v >= 10) { v /= 10; ++d; }
-    return d;
-}
-
-__device__ __forceinline__ void put_dec(uint8_t* o, uint64_t v, uint32_t d)
-{
-    for (uint32_t k = d; k-- > 0;) { o[k] = (uint8_t)('0' + v % 10); v /= 10; }
-}
-
 struct Format {
     const uint64_t *line_end, *start, *stop;   // of every line of the buffer; query line j is line m0 + j
     const uint32_t *left, *right;
@@ -188,8 +180,6 @@ __device__ __forceinline__ uint64_t distance(const Format& f, uint64_t i, uint32
     return b <= s ? s - b + 1 : (a >= e ? a - e + 1 : 0);
 }
 
-__device__ __forceinline__ uint64_t line_begin(const Format& f, uint64_t g) { return g ? f.line_end[g - 1] : 0; }
-
 // len: bytes of output line i with its '\n'
 __global__ void __launch_bounds__(kThreads)
 k_bc_len(const Format f, uint64_t* __restrict__ len)
@@ -200,11 +190,11 @@ k_bc_len(const Format f, uint64_t* __restrict__ len)
     const uint32_t ne = elements(f, i, el);
     const uint32_t fields = (f.opt.no_ref ? 0 : 1) + ne * (f.opt.dist ? 2 : 1);
     uint64_t n = (uint64_t)f.opt.delim_len * (fields - 1) + 1;
-    if (!f.opt.no_ref) n += f.line_end[i] - 1 - line_begin(f, i);
+    if (!f.opt.no_ref) n += f.line_end[i] - 1 - line_beg(f.line_end, i);
     for (uint32_t k = 0; k < ne; ++k) {
         if (el[k] == kNA) { n += f.opt.dist ? 4 : 2; continue; }
         const uint64_t g = f.m0 + el[k];
-        n += f.line_end[g] - 1 - line_begin(f, g);
+        n += f.line_end[g] - 1 - line_beg(f.line_end, g);
         if (f.opt.dist) {
             bool neg;
             const uint64_t d = distance(f, i, el[k], &neg);
@@ -222,22 +212,19 @@ k_bc_write(const uint8_t* __restrict__ bed, const Format f, const uint64_t* __re
 {
     const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    uint64_t big_src[3] = {0, 0, 0}, big_dst[3] = {0, 0, 0}, big_len[3] = {0, 0, 0};
+    bt::Writer<3> w{out, 0};   // slots: the reference line, the first element, the second
     if (i < f.Lr && off[i] + len[i] <= out_bytes) {
-        uint64_t o = off[i];
+        w.o = off[i];
         bool first = true;
         auto delim = [&] {
-            if (!first)
-                for (uint32_t d = 0; d < f.opt.delim_len; ++d) out[o++] = f.opt.delim[d];
+            if (!first) w.delim(f.opt.delim, f.opt.delim_len);
             first = false;
         };
         auto copy_line = [&](uint64_t g, int slot) {
-            const uint64_t b = line_begin(f, g), n = f.line_end[g] - 1 - b;
-            if (n >= sb::kWaveCopyBytes) { big_src[slot] = b; big_dst[slot] = o; big_len[slot] = n; }
-            else
-                for (uint64_t p = 0; p < n; ++p) out[o + p] = bed[b + p];
-            o += n;
+            const uint64_t b = line_beg(f.line_end, g);
+            w.copy(slot, bed + b, f.line_end[g] - 1 - b);
         };
+        auto na_text = [&] { w.bytes(reinterpret_cast<const uint8_t*>("NA"), 2); };
         if (!f.opt.no_ref) { delim(); copy_line(i, 0); }
         uint32_t el[2];
         const uint32_t ne = elements(f, i, el);
@@ -246,61 +233,34 @@ k_bc_write(const uint8_t* __restrict__ bed, const Format f, const uint64_t* __re
             if (k >= ne) break;
             const bool na = el[k] == kNA;
             delim();
-            if (na) { out[o++] = 'N'; out[o++] = 'A'; }
+            if (na) na_text();
             else copy_line(f.m0 + el[k], 1 + (int)k);
             if (f.opt.dist) {
                 delim();
-                if (na) { out[o++] = 'N'; out[o++] = 'A'; }
+                if (na) na_text();
                 else {
                     bool neg;
                     const uint64_t d = distance(f, i, el[k], &neg);
-                    if (neg) out[o++] = '-';
-                    const uint32_t nd = dec_digits(d);
-                    put_dec(out + o, d, nd);
-                    o += nd;
+                    if (neg) out[w.o++] = '-';
+                    w.dec(d);
                 }
             }
         }
-        out[o] = '\n';
+        out[w.o] = '\n';
     }
-#pragma unroll
-    for (int slot = 0; slot < 3; ++slot) {
-        unsigned long long m = __ballot(big_len[slot] != 0);
-        while (m) {
-            const int l = __ffsll(m) - 1;
-            m &= m - 1;
-            const uint64_t src = __shfl(big_src[slot], l, 64), dst = __shfl(big_dst[slot], l, 64),
-                           n = __shfl(big_len[slot], l, 64);
-            for (uint64_t p = lane; p < n; p += 64) out[dst + p] = bed[src + p];
-        }
-    }
+    bt::wave_copy_tails(w, out, lane);
 }
 
 }  // namespace
-
-ClosestWorkspace::~ClosestWorkspace()
-{
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-}
 
 void ClosestWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, const ClosestOptions& opt, const uint8_t* d_cat,
                            uint64_t n, const std::vector<uint64_t>& in_end, hipStream_t st, DevBuf& out, ClosestResult& res)
 {
     res = ClosestResult{};
     if (in_end.size() != 2) throw StarchError(STARCH_ERR_INTERNAL, "closest-features: two inputs are needed");
-    for (auto& e : ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(STARCH_ERR_DEVICE, "hipEventCreate"); }
     (void)out.as<uint8_t>(64);
-    HIP_CHECK(hipEventRecord(ev[0], st));
-    auto finish = [&](int from) {
-        for (int k = from; k < 5; ++k) HIP_CHECK(hipEventRecord(ev[k], st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_parse, ev[0], ev[1]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_build, ev[1], ev[2]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_query, ev[2], ev[3]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_format, ev[3], ev[4]));
-    };
+    timer.start(st);
+    auto finish = [&](int from) { timer.finish(from, st, {&res.ms_parse, &res.ms_build, &res.ms_query, &res.ms_format}); };
     if (n == 0) return finish(1);   // both inputs are empty
 
     // 1. parse, ranks, checks; the reference is lines [0, Lr), the query [Lr, Lr + Lq)
@@ -311,7 +271,7 @@ void ClosestWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines,
     res.n_ref = Lr;
     res.n_query = Lq;
     res.n_chromosomes = sorter.n_chromosomes;
-    HIP_CHECK(hipEventRecord(ev[1], st));
+    timer.mark(1, st);
     if (Lr == 0) return finish(2);
 
     const uint64_t C = sorter.n_chromosomes;
@@ -360,12 +320,12 @@ void ClosestWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines,
     q.left = b_left.as<uint32_t>(Lr);
     q.right = b_right.as<uint32_t>(Lr);
     q.na = reinterpret_cast<unsigned long long*>(scal);
-    HIP_CHECK(hipEventRecord(ev[2], st));
+    timer.mark(2, st);
 
     // 3. query
     hipLaunchKernelGGL(k_bc_query, dim3(blocks_for(Lr, kTileRefs)), dim3(kTileRefs), 0, st, q);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev[3], st));
+    timer.mark(3, st);
 
     // 4. format
     Format f{sorter.ln.line_end, start, stop, q.left, q.right, Lr, m0, opt};
@@ -374,16 +334,14 @@ void ClosestWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines,
     uint64_t* off = b_off.as<uint64_t>(Lr);
     hipLaunchKernelGGL(k_bc_len, dim3(rblocks), dim3(kThreads), 0, st, f, len);
     HIP_CHECK(hipGetLastError());
-    scan::excl_sum_u64(len, off, Lr, scal + S_BYTES, b_tmp, st);
-    uint64_t tot[3] = {0, 0, 0};
-    HIP_CHECK(hipMemcpyAsync(tot, scal, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const uint64_t bytes = tot[S_BYTES];
-    uint8_t* o = out.as<uint8_t>(bytes + 64);
-    hipLaunchKernelGGL(k_bc_write, dim3(rblocks), dim3(kThreads), 0, st, d_cat, f, len, off, bytes, o);
+    uint64_t tot[3] = {0, 0, 0};   // the bytes, and with them the two NA counts of the query
+    const FormatTail ft = format_tail(Lr, len, off, nullptr, nullptr, scal + S_BYTES, tot, 3, b_tmp, out, st,
+                                      "closest-features", false);
+    hipLaunchKernelGGL(k_bc_write, dim3(rblocks), dim3(kThreads), 0, st, d_cat, f, len, off, ft.bytes,
+                       static_cast<uint8_t*>(out.p));
     HIP_CHECK(hipGetLastError());
-    res.out_bytes = bytes;
-    res.lines_out = Lr;
+    res.out_bytes = ft.bytes;
+    res.lines_out = ft.lines_kept;
     res.left_na = tot[S_LEFT_NA];
     res.right_na = tot[S_RIGHT_NA];
     finish(4);

@@ -29,7 +29,7 @@ struct ClosestResult {
 
 struct ClosestWorkspace {
     DevBuf b_scal, b_tmp, b_mlo, b_B, b_hier, b_left, b_right, b_len, b_off;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    StageTimer<5> timer;
     // The inputs lie back to back in d_cat[0, n) as for bm::MapWorkspace::run:
     // in_end has two entries (reference, then query).  One line per reference
     // line goes to out (res.out_bytes of it).  sorter and lines supply parse,
@@ -37,7 +37,6 @@ struct ClosestWorkspace {
     // order.  Throws StarchError as include/starch_amd.h describes.
     void run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, const ClosestOptions& opt, const uint8_t* d_cat, uint64_t n,
              const std::vector<uint64_t>& in_end, hipStream_t st, DevBuf& out, ClosestResult& res);
-    ~ClosestWorkspace();
 };
 
 }  // namespace bc

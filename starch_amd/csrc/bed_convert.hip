@@ -51,8 +51,6 @@ enum : uint32_t {
 enum : uint32_t { O_ID = 8, O_IDLEN = 9, O_CHR = 0, O_CHREND = 1, O_SCORE = 2, O_SCOREEND = 3, O_DECL = 4, O_MODE = 2 };
 enum : uint32_t { M_VARIABLE = 1, M_FIXED = 2 };
 
-inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return (unsigned)ceil_div(items, per_block); }
-
 struct Rec {
     const uint8_t* in;
     const uint64_t* line_end;
@@ -415,10 +413,10 @@ k_cv_write(const Rec r, uint64_t Le, const uint64_t* __restrict__ hord, const ui
     f[0] = 0;
 #pragma unroll
     for (uint32_t k = 0; k < kSlots; ++k) f[k + 1] = nout ? r.fo[(uint64_t)k * r.L + i] : 0u;
-    Writer w{out, nout ? off[i] : 0};
+    Writer<> w{out, nout ? off[i] : 0};
     uint32_t ap = f[4];       // VCF: where the next allele begins
     for (uint32_t round = 0; __ballot(round < nout) != 0; ++round) {
-        w.big_len = 0;
+        w.big_len[0] = 0;
         if (round < nout) {
             if (cls == C_HEADER) {
                 const uint64_t k = hord[i];
@@ -538,33 +536,19 @@ const char* bad_text(uint32_t k)
 
 }  // namespace
 
-ConvertWorkspace::~ConvertWorkspace()
-{
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-}
-
 void ConvertWorkspace::run(sb::SortWorkspace& sorter, const ConvertOptions& opt, const uint8_t* d_in, uint64_t n, hipStream_t st,
                            DevBuf& out, ConvertResult& res)
 {
     res = ConvertResult{};
-    for (auto& e : ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(STARCH_ERR_DEVICE, "hipEventCreate"); }
     (void)out.as<uint8_t>(64);
-    HIP_CHECK(hipEventRecord(ev[0], st));
-    auto finish = [&](int from) {
-        for (int k = from; k < 4; ++k) HIP_CHECK(hipEventRecord(ev[k], st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_frame, ev[0], ev[1]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_parse, ev[1], ev[2]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_write, ev[2], ev[3]));
-    };
+    timer.start(st);
+    auto finish = [&](int from) { timer.finish(from, st, {&res.ms_frame, &res.ms_parse, &res.ms_write}); };
     if (n == 0) return finish(1);
 
     // 1. framing
     const uint64_t L = sorter.stage_frame(d_in, n, st);
     res.n_lines = L;
-    HIP_CHECK(hipEventRecord(ev[1], st));
+    timer.mark(1, st);
 
     // 2. classify and measure
     const bool wig = opt.format == STARCH_CONVERT_WIG;
@@ -630,7 +614,7 @@ void ConvertWorkspace::run(sb::SortWorkspace& sorter, const ConvertOptions& opt,
     res.data_lines = tot[S_REC];
     res.declarations = tot[S_DECL];
     if (tot[S_LINES] >= (1ull << 32)) throw StarchError(STARCH_ERR_ARG, "convert2bed: 2^32 output lines or more");
-    HIP_CHECK(hipEventRecord(ev[2], st));
+    timer.mark(2, st);
     const uint64_t bytes = tot[S_BYTES];
     if (bytes) {
         uint8_t* o = out.as<uint8_t>(bytes + 64);

@@ -22,7 +22,7 @@ struct ConvertResult {
 
 struct ConvertWorkspace {
     DevBuf b_scal, b_tmp, b_cls, b_fo, b_a, b_b, b_aux, b_cnt, b_ob, b_off, b_hflag, b_hord, b_pk, b_dmax;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    StageTimer<4> timer;
     // The text d_in[0, n) in the format of opt, converted line by line as
     // include/starch_amd.h defines, into out (res.out_bytes of it, in input
     // order).  sorter supplies the framing (stage_frame) and is free again when
@@ -30,7 +30,6 @@ struct ConvertWorkspace {
     // that does not fit its format, STARCH_ERR_ARG for 2^32 lines or more.
     void run(sb::SortWorkspace& sorter, const ConvertOptions& opt, const uint8_t* d_in, uint64_t n, hipStream_t st, DevBuf& out,
              ConvertResult& res);
-    ~ConvertWorkspace();
 };
 
 }  // namespace cv

@@ -45,7 +45,7 @@ static inline void build_hier(const uint64_t* S, uint64_t n, DevBuf& buf, hipStr
     h->cnt[0] = n;
     for (int k = 1; k < nlev; ++k) {
         const uint64_t groups = ceil_div(h->cnt[k - 1], kFanout);
-        hipLaunchKernelGGL(k_bc_level, dim3((unsigned)ceil_div(groups, kLevelThreads)), dim3(kLevelThreads), 0, st, h->lev[k - 1],
+        hipLaunchKernelGGL(k_bc_level, dim3(blocks_for(groups, kLevelThreads)), dim3(kLevelThreads), 0, st, h->lev[k - 1],
                            h->cnt[k - 1], groups, hb);
         h->lev[k] = hb;
         h->cnt[k] = groups;

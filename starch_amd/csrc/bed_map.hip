@@ -31,7 +31,9 @@
 //      elements each, they are copied to LDS first and searched there
 //      (measured: DESIGN.md section 12); the runs of BASES_UNIQ are always
 //      searched in HBM.
-//   4. format: k_bm_len, an exclusive sum, k_bm_write.
+//   4. format: k_bm_len, an exclusive sum, k_bm_write (the writer and its wave
+//      copy: bed_text.hpp; the host steps between the two kernels: format_tail
+//      in common.hpp; both shared with every BED command).
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -39,6 +41,7 @@
 #include "../../include/starch_amd.h"
 #include "bed_map.hpp"
 #include "bed_search.hpp"
+#include "bed_text.hpp"
 #include "seg_max.hpp"
 
 namespace bm {
@@ -48,7 +51,8 @@ constexpr int kThreads = kBoundsThreads;
 enum : int { S_BYTES = 0, S_KEPT, S_COUNT = 4 };   // device scalars (u64)
 enum : uint32_t { W_COUNT = 1, W_BASES = 2, W_UNIQ = 4 };
 
-inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return (unsigned)ceil_div(items, per_block); }
+using bt::dec_digits;
+using bt::line_beg;
 
 // ---- 2. map arrays ------------------------------------------------------------------
 __global__ void __launch_bounds__(kThreads)
@@ -193,18 +197,6 @@ k_bm_query(const Query q)
 }
 
 // ---- 4. format ------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t dec_digits(uint64_t v)
-{
-    uint32_t d = 1;
-    while (v >= 10) { v /= 10; ++d; }
-    return d;
-}
-
-__device__ __forceinline__ void put_dec(uint8_t* o, uint64_t v, uint32_t d)
-{
-    for (uint32_t k = d; k-- > 0;) { o[k] = (uint8_t)('0' + v % 10); v /= 10; }
-}
-
 struct Format {
     const uint64_t *line_end, *start, *stop, *cnt, *bases, *uniq;
     uint64_t Lr;
@@ -234,7 +226,7 @@ k_bm_len(const Format f, uint64_t* __restrict__ len, uint32_t* __restrict__ keep
         n = (uint64_t)f.opt.delim_len * (f.opt.ncols - 1) + 1;
         for (uint32_t k = 0; k < f.opt.ncols; ++k) {
             const uint32_t c = f.opt.cols[k];
-            if (c == STARCH_MAP_ECHO) n += f.line_end[i] - 1 - (i ? f.line_end[i - 1] : 0);
+            if (c == STARCH_MAP_ECHO) n += f.line_end[i] - 1 - line_beg(f.line_end, i);
             else n += dec_digits(col_value(f, c, i));
         }
     }
@@ -250,62 +242,32 @@ k_bm_write(const uint8_t* __restrict__ bed, const Format f, const uint64_t* __re
 {
     const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    uint64_t big_src = 0, big_dst = 0, big_len = 0;
+    bt::Writer<> w{out, 0};
     if (i < f.Lr && len[i] && off[i] + len[i] <= out_bytes) {
-        uint64_t o = off[i];
+        w.o = off[i];
         for (uint32_t k = 0; k < f.opt.ncols; ++k) {
             const uint32_t c = f.opt.cols[k];
-            if (k)
-                for (uint32_t d = 0; d < f.opt.delim_len; ++d) out[o++] = f.opt.delim[d];
+            if (k) w.delim(f.opt.delim, f.opt.delim_len);
             if (c == STARCH_MAP_ECHO) {
-                const uint64_t b = i ? f.line_end[i - 1] : 0, n = f.line_end[i] - 1 - b;
-                if (n >= sb::kWaveCopyBytes) { big_src = b; big_dst = o; big_len = n; }
-                else
-                    for (uint64_t p = 0; p < n; ++p) out[o + p] = bed[b + p];
-                o += n;
-            } else {
-                const uint64_t v = col_value(f, c, i);
-                const uint32_t d = dec_digits(v);
-                put_dec(out + o, v, d);
-                o += d;
-            }
+                const uint64_t b = line_beg(f.line_end, i);
+                w.copy(0, bed + b, f.line_end[i] - 1 - b);
+            } else w.dec(col_value(f, c, i));
         }
-        out[o] = '\n';
+        out[w.o] = '\n';
     }
-    unsigned long long m = __ballot(big_len != 0);
-    while (m) {
-        const int l = __ffsll(m) - 1;
-        m &= m - 1;
-        const uint64_t src = __shfl(big_src, l, 64), dst = __shfl(big_dst, l, 64), n = __shfl(big_len, l, 64);
-        for (uint64_t p = lane; p < n; p += 64) out[dst + p] = bed[src + p];
-    }
+    bt::wave_copy_tails(w, out, lane);
 }
 
 }  // namespace
-
-MapWorkspace::~MapWorkspace()
-{
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-}
 
 void MapWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, const MapOptions& opt, const uint8_t* d_cat,
                        uint64_t n, const std::vector<uint64_t>& in_end, hipStream_t st, DevBuf& out, MapResult& res)
 {
     res = MapResult{};
     const uint64_t N = in_end.size();
-    for (auto& e : ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(STARCH_ERR_DEVICE, "hipEventCreate"); }
     (void)out.as<uint8_t>(64);
-    HIP_CHECK(hipEventRecord(ev[0], st));
-    auto finish = [&](int from) {
-        for (int k = from; k < 5; ++k) HIP_CHECK(hipEventRecord(ev[k], st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_parse, ev[0], ev[1]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_build, ev[1], ev[2]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_query, ev[2], ev[3]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_format, ev[3], ev[4]));
-    };
+    timer.start(st);
+    auto finish = [&](int from) { timer.finish(from, st, {&res.ms_parse, &res.ms_build, &res.ms_query, &res.ms_format}); };
     if (n == 0) return finish(1);   // both inputs are empty
 
     // 1. parse, ranks, checks; the reference is lines [0, Lr), the map [m0, m0 + Lm)
@@ -316,7 +278,7 @@ void MapWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, con
     res.n_ref = Lr;
     res.n_map = Lm;
     res.n_chromosomes = sorter.n_chromosomes;
-    HIP_CHECK(hipEventRecord(ev[1], st));
+    timer.mark(1, st);
     if (Lr == 0) return finish(2);
 
     uint32_t want = 0;
@@ -398,14 +360,14 @@ void MapWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, con
         q.uniq = b_uniq.as<uint64_t>(Lr);
         res.map_runs_merged = R;
     }
-    HIP_CHECK(hipEventRecord(ev[2], st));
+    timer.mark(2, st);
 
     // 3. query
     if (want) {
         hipLaunchKernelGGL(k_bm_query, dim3(blocks_for(Lr, kTileRefs)), dim3(kTileRefs), 0, st, q);
         HIP_CHECK(hipGetLastError());
     }
-    HIP_CHECK(hipEventRecord(ev[3], st));
+    timer.mark(3, st);
 
     // 4. format
     Format f{sorter.ln.line_end, start, stop, q.cnt, q.bases, q.uniq, Lr, opt};
@@ -415,17 +377,14 @@ void MapWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, con
     uint32_t* keep = opt.skip_unmapped ? b_keep.as<uint32_t>(Lr) : nullptr;
     hipLaunchKernelGGL(k_bm_len, dim3(rblocks), dim3(kThreads), 0, st, f, len, keep);
     HIP_CHECK(hipGetLastError());
-    scan::excl_sum_u64(len, off, Lr, scal + S_BYTES, b_tmp, st);
-    if (keep) scan::excl_sum_u32_to_u64(keep, b_kpos.as<uint64_t>(Lr), Lr, scal + S_KEPT, b_tmp, st);
     uint64_t tot[2] = {0, 0};
-    HIP_CHECK(hipMemcpyAsync(tot, scal + S_BYTES, (keep ? 2 : 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const uint64_t bytes = tot[0];
-    uint8_t* o = out.as<uint8_t>(bytes + 64);
-    hipLaunchKernelGGL(k_bm_write, dim3(rblocks), dim3(kThreads), 0, st, d_cat, f, len, off, bytes, o);
+    const FormatTail ft = format_tail(Lr, len, off, keep, keep ? b_kpos.as<uint64_t>(Lr) : nullptr, scal + S_BYTES, tot,
+                                      keep ? 2 : 1, b_tmp, out, st, "bedmap", false);
+    hipLaunchKernelGGL(k_bm_write, dim3(rblocks), dim3(kThreads), 0, st, d_cat, f, len, off, ft.bytes,
+                       static_cast<uint8_t*>(out.p));
     HIP_CHECK(hipGetLastError());
-    res.out_bytes = bytes;
-    res.lines_out = keep ? tot[1] : Lr;
+    res.out_bytes = ft.bytes;
+    res.lines_out = ft.lines_kept;
     finish(4);
 }
 

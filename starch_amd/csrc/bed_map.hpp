@@ -29,7 +29,7 @@ struct MapResult {
 struct MapWorkspace {
     DevBuf b_scal, b_tmp, b_mlo, b_rlo, b_B, b_PA, b_PB, b_MR, b_MS, b_ME, b_ML, b_PL, b_cnt, b_bases, b_uniq, b_len, b_off,
         b_keep, b_kpos;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    StageTimer<5> timer;
     // The inputs lie back to back in d_cat[0, n) as for so::SetopWorkspace::run:
     // in_end has one entry (the reference is mapped onto itself) or two
     // (reference, then map).  The annotated reference lines go to out
@@ -38,7 +38,6 @@ struct MapWorkspace {
     // include/starch_amd.h describes.
     void run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, const MapOptions& opt, const uint8_t* d_cat, uint64_t n,
              const std::vector<uint64_t>& in_end, hipStream_t st, DevBuf& out, MapResult& res);
-    ~MapWorkspace();
 };
 
 }  // namespace bm

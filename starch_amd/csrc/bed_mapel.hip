@@ -34,7 +34,9 @@
 //      entries).  k_me_len and the exclusive sum over the lines give the line
 //      offsets; k_me_write_line writes the per-line columns and delimiters and
 //      leaves where each list column begins; k_me_write_hit, one thread per
-//      hit, writes its pieces.
+//      hit, writes its pieces.  The writer and its wave copy are bed_text.hpp's,
+//      the host steps from the line lengths to the sized output format_tail's
+//      (common.hpp); both are shared with every BED command.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -43,6 +45,7 @@
 #include "bed_hier.hpp"
 #include "bed_mapel.hpp"
 #include "bed_search.hpp"
+#include "bed_text.hpp"
 
 namespace me {
 namespace {
@@ -56,7 +59,8 @@ constexpr uint64_t kNone = ~0ull;
 enum : int { S_BYTES = 0, S_KEPT, S_HEAVY, S_STEPS, S_BAD, S_COUNT = 8 };   // device scalars (u64)
 enum : int { L_MAP = 0, L_ID, L_SCORE, L_SIZE, L_OVR };                      // list slots: code - STARCH_MAPEL_ECHO_MAP
 
-inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return (unsigned)ceil_div(items, per_block); }
+using bt::dec_digits;
+using bt::line_beg;
 
 // ---- 3. hits --------------------------------------------------------------------------
 struct Crit {
@@ -253,18 +257,6 @@ k_me_find(const Find f)
 }
 
 // ---- 4. format ------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t dec_digits(uint64_t v)
-{
-    uint32_t d = 1;
-    while (v >= 10) { v /= 10; ++d; }
-    return d;
-}
-
-__device__ __forceinline__ void put_dec(uint8_t* o, uint64_t v, uint32_t d)
-{
-    for (uint32_t k = d; k-- > 0;) { o[k] = (uint8_t)('0' + v % 10); v /= 10; }
-}
-
 struct Format {
     const uint8_t* bed;
     const uint64_t *line_end, *start, *stop;   // of every line of the buffer; map line j is line m0 + j
@@ -280,8 +272,6 @@ struct Format {
     uint32_t slots;                            // bit k: list slot k is asked for
     unsigned long long* scal;
 };
-
-__device__ __forceinline__ uint64_t line_begin(const Format& f, uint64_t g) { return g ? f.line_end[g - 1] : 0; }
 
 // field k (from 0) of the line bed[lb, le): false when the line has k fields or fewer
 __device__ __forceinline__ bool field(const uint8_t* __restrict__ bed, uint64_t lb, uint64_t le, int k, uint64_t* fb, uint64_t* fe)
@@ -301,7 +291,7 @@ __device__ __forceinline__ bool field(const uint8_t* __restrict__ bed, uint64_t 
 // the bytes that list slot k copies for map line g (length 0 when the column is missing), or the number it prints
 __device__ __forceinline__ bool piece(const Format& f, int k, uint64_t i, uint64_t g, uint64_t* src, uint64_t* len, uint64_t* num)
 {
-    const uint64_t lb = line_begin(f, g), le = f.line_end[g] - 1;
+    const uint64_t lb = line_beg(f.line_end, g), le = f.line_end[g] - 1;
     *src = lb;
     *len = 0;
     *num = 0;
@@ -354,7 +344,7 @@ k_me_len(const Format f, uint64_t* __restrict__ len, uint32_t* __restrict__ keep
         for (uint32_t k = 0; k < f.opt.ncols; ++k) {
             const uint32_t col = f.opt.cols[k];
             switch (col) {
-                case STARCH_MAPEL_ECHO: n += f.line_end[i] - 1 - line_begin(f, i); break;
+                case STARCH_MAPEL_ECHO: n += f.line_end[i] - 1 - line_beg(f.line_end, i); break;
                 case STARCH_MAPEL_COUNT: n += dec_digits(c); break;
                 case STARCH_MAPEL_INDICATOR: n += 1; break;
                 case STARCH_MAPEL_ECHO_REF_SIZE: n += dec_digits(f.stop[i] - f.start[i]); break;
@@ -384,73 +374,53 @@ k_me_write_line(const Format f, const uint64_t* __restrict__ len, const uint64_t
 {
     const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    uint64_t big_src = 0, big_dst = 0, big_len = 0;
+    bt::Writer<> w{out, 0};
     if (i < f.Lr && len[i] && off[i] + len[i] <= out_bytes) {
         const uint64_t c = f.cnt[i];
-        uint64_t o = off[i];
-        auto number = [&](uint64_t v) {
-            const uint32_t d = dec_digits(v);
-            put_dec(out + o, v, d);
-            o += d;
-        };
-        auto chrom = [&] {
-            const uint64_t b = line_begin(f, i);
-            for (uint32_t p = 0; p < f.chr_len[i]; ++p) out[o++] = f.bed[b + p];
-        };
+        w.o = off[i];
+        auto chrom = [&] { w.bytes(f.bed + line_beg(f.line_end, i), f.chr_len[i]); };
         for (uint32_t k = 0; k < f.opt.ncols; ++k) {
             const uint32_t col = f.opt.cols[k];
-            if (k)
-                for (uint32_t d = 0; d < f.opt.delim_len; ++d) out[o++] = f.opt.delim[d];
+            if (k) w.delim(f.opt.delim, f.opt.delim_len);
             switch (col) {
                 case STARCH_MAPEL_ECHO: {
-                    const uint64_t b = line_begin(f, i), n = f.line_end[i] - 1 - b;
-                    if (n >= sb::kWaveCopyBytes) { big_src = b; big_dst = o; big_len = n; }
-                    else
-                        for (uint64_t p = 0; p < n; ++p) out[o + p] = f.bed[b + p];
-                    o += n;
+                    const uint64_t b = line_beg(f.line_end, i);
+                    w.copy(0, f.bed + b, f.line_end[i] - 1 - b);
                     break;
                 }
-                case STARCH_MAPEL_COUNT: number(c); break;
-                case STARCH_MAPEL_INDICATOR: out[o++] = c ? '1' : '0'; break;
-                case STARCH_MAPEL_ECHO_REF_SIZE: number(f.stop[i] - f.start[i]); break;
+                case STARCH_MAPEL_COUNT: w.dec(c); break;
+                case STARCH_MAPEL_INDICATOR: out[w.o++] = c ? '1' : '0'; break;
+                case STARCH_MAPEL_ECHO_REF_SIZE: w.dec(f.stop[i] - f.start[i]); break;
                 case STARCH_MAPEL_ECHO_REF_NAME:
                     chrom();
-                    out[o++] = ':';
-                    number(f.start[i]);
-                    out[o++] = '-';
-                    number(f.stop[i]);
+                    out[w.o++] = ':';
+                    w.dec(f.start[i]);
+                    out[w.o++] = '-';
+                    w.dec(f.stop[i]);
                     break;
                 case STARCH_MAPEL_ECHO_REF_ROW_ID:
-                    out[o++] = 'i';
-                    out[o++] = 'd';
-                    out[o++] = '-';
-                    number(i + 1);
+                    w.bytes(reinterpret_cast<const uint8_t*>("id-"), 3);
+                    w.dec(i + 1);
                     break;
                 case STARCH_MAPEL_ECHO_MAP_RANGE:
                     if (c) {
                         chrom();
-                        out[o++] = '\t';
-                        number(f.start[f.m0 + f.H[f.hoff[i]]]);
-                        out[o++] = '\t';
-                        number(f.rmax[i]);
+                        w.tab();
+                        w.dec(f.start[f.m0 + f.H[f.hoff[i]]]);
+                        w.tab();
+                        w.dec(f.rmax[i]);
                     }
                     break;
                 default: {   // a list column: its hits write it
                     const uint32_t slot = col - STARCH_MAPEL_ECHO_MAP;
-                    f.cs[slot][i] = o;
-                    if (c) o += f.P[slot][f.hoff[i + 1]] - f.P[slot][f.hoff[i]] + (c - 1) * f.opt.multi_len;
+                    f.cs[slot][i] = w.o;
+                    if (c) w.o += f.P[slot][f.hoff[i + 1]] - f.P[slot][f.hoff[i]] + (c - 1) * f.opt.multi_len;
                 }
             }
         }
-        out[o] = '\n';
+        out[w.o] = '\n';
     }
-    unsigned long long m = __ballot(big_len != 0);
-    while (m) {
-        const int l = __ffsll(m) - 1;
-        m &= m - 1;
-        const uint64_t src = __shfl(big_src, l, 64), dst = __shfl(big_dst, l, 64), n = __shfl(big_len, l, 64);
-        for (uint64_t p = lane; p < n; p += 64) out[dst + p] = f.bed[src + p];
-    }
+    bt::wave_copy_tails(w, out, lane);
 }
 
 // A thread writes the pieces of its hit, each after its multi-delimiter unless
@@ -461,46 +431,31 @@ k_me_write_hit(const Format f, uint64_t out_bytes, uint8_t* __restrict__ out)
 {
     const uint64_t h = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    uint64_t big_src[3] = {0, 0, 0}, big_dst[3] = {0, 0, 0}, big_len[3] = {0, 0, 0};
+    bt::Writer<3> w{out, 0};   // the cursor is set for every piece
     if (h < f.T) {
         const uint64_t i = f.R[h], g = f.m0 + f.H[h], h0 = f.hoff[i], r = h - h0;
         for (int k = 0; k < kListCols; ++k) {
             if (!((f.slots >> k) & 1)) continue;
             uint64_t src, n, num;
             (void)piece(f, k, i, g, &src, &n, &num);
-            uint64_t o = f.cs[k][i] + (f.P[k][h] - f.P[k][h0]) + r * f.opt.multi_len;
+            const uint64_t o = f.cs[k][i] + (f.P[k][h] - f.P[k][h0]) + r * f.opt.multi_len;
             if (o + n > out_bytes || o < r * f.opt.multi_len) continue;
-            if (r)
-                for (uint32_t d = 0; d < f.opt.multi_len; ++d) out[o - f.opt.multi_len + d] = f.opt.multi[d];
-            if (k >= L_SIZE) put_dec(out + o, num, (uint32_t)n);
-            else if (n >= sb::kWaveCopyBytes) { big_src[k] = src; big_dst[k] = o; big_len[k] = n; }
-            else
-                for (uint64_t p = 0; p < n; ++p) out[o + p] = f.bed[src + p];
+            if (r) {
+                w.o = o - f.opt.multi_len;
+                w.delim(f.opt.multi, f.opt.multi_len);
+            }
+            w.o = o;
+            if (k >= L_SIZE) w.dec(num, (uint32_t)n);
+            else w.copy(k, f.bed + src, n);
         }
     }
-#pragma unroll
-    for (int slot = 0; slot < 3; ++slot) {
-        unsigned long long m = __ballot(big_len[slot] != 0);
-        while (m) {
-            const int l = __ffsll(m) - 1;
-            m &= m - 1;
-            const uint64_t src = __shfl(big_src[slot], l, 64), dst = __shfl(big_dst[slot], l, 64),
-                           n = __shfl(big_len[slot], l, 64);
-            for (uint64_t p = lane; p < n; p += 64) out[dst + p] = f.bed[src + p];
-        }
-    }
+    bt::wave_copy_tails(w, out, lane);
 }
 
 }  // namespace
 
-MapelWorkspace::~MapelWorkspace()
-{
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-}
-
 int MapelWorkspace::hits(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, const char* name, const MapelOptions& opt,
-                         const uint8_t* d_cat, uint64_t n, const std::vector<uint64_t>& in_end, hipStream_t st, hipEvent_t* ev3,
+                         const uint8_t* d_cat, uint64_t n, const std::vector<uint64_t>& in_end, hipStream_t st, StageMarks tm,
                          HitList& hl)
 {
     hl = HitList{};
@@ -517,7 +472,7 @@ int MapelWorkspace::hits(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, c
     hl.Lm = Lm;
     hl.m0 = m0;
     hl.n_chromosomes = sorter.n_chromosomes;
-    HIP_CHECK(hipEventRecord(ev3[0], st));
+    tm.mark(0, st);
     if (Lr == 0) return 1;
 
     const uint64_t C = sorter.n_chromosomes;
@@ -549,7 +504,7 @@ int MapelWorkspace::hits(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, c
         q.M = lines.incl;
         bc::build_hier(q.S, Lm, b_hier, st, name, &q.h);
     }
-    HIP_CHECK(hipEventRecord(ev3[1], st));
+    tm.mark(1, st);
 
     // 3. count, scan, fill
     const unsigned qblocks = blocks_for(Lr, kTileRefs);
@@ -580,7 +535,7 @@ int MapelWorkspace::hits(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, c
         hipLaunchKernelGGL(k_me_find<true>, dim3(qblocks), dim3(kTileRefs), 0, st, q);
         HIP_CHECK(hipGetLastError());
     }
-    HIP_CHECK(hipEventRecord(ev3[2], st));
+    tm.mark(2, st);
     hl.cnt = cnt;
     hl.hoff = hoff;
     hl.H = H;
@@ -594,22 +549,13 @@ void MapelWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, c
 {
     res = MapelResult{};
     const uint64_t N = in_end.size();
-    for (auto& e : ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(STARCH_ERR_DEVICE, "hipEventCreate"); }
     (void)out.as<uint8_t>(64);
-    HIP_CHECK(hipEventRecord(ev[0], st));
-    auto finish = [&](int from) {
-        for (int k = from; k < 5; ++k) HIP_CHECK(hipEventRecord(ev[k], st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_parse, ev[0], ev[1]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_build, ev[1], ev[2]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_query, ev[2], ev[3]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_format, ev[3], ev[4]));
-    };
+    timer.start(st);
+    auto finish = [&](int from) { timer.finish(from, st, {&res.ms_parse, &res.ms_build, &res.ms_query, &res.ms_format}); };
 
     // 1 to 3. the hit list
     HitList hl;
-    const int done = hits(sorter, lines, "bedmap-elements", opt, d_cat, n, in_end, st, ev + 1, hl);
+    const int done = hits(sorter, lines, "bedmap-elements", opt, d_cat, n, in_end, st, timer.marks_from(1), hl);
     res.n_ref = hl.Lr;
     res.n_map = hl.Lm;
     res.n_chromosomes = hl.n_chromosomes;
@@ -671,19 +617,15 @@ void MapelWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, c
     uint32_t* keep = opt.skip_unmapped ? b_keep.as<uint32_t>(Lr) : nullptr;
     hipLaunchKernelGGL(k_me_len, dim3(rblocks), dim3(kThreads), 0, st, f, len, keep);
     HIP_CHECK(hipGetLastError());
-    scan::excl_sum_u64(len, off, Lr, scal + S_BYTES, b_tmp, st);
-    if (keep) scan::excl_sum_u32_to_u64(keep, b_kpos.as<uint64_t>(Lr), Lr, scal + S_KEPT, b_tmp, st);
     uint64_t tot[2] = {0, 0};
-    HIP_CHECK(hipMemcpyAsync(tot, scal + S_BYTES, (keep ? 2 : 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const uint64_t bytes = tot[0];
-    if (bytes >= (1ull << 40)) throw StarchError(STARCH_ERR_ARG, "bedmap-elements: result too large (2^40 bytes or more)");
-    uint8_t* o = out.as<uint8_t>(bytes + 64);
-    hipLaunchKernelGGL(k_me_write_line, dim3(rblocks), dim3(kThreads), 0, st, f, len, off, bytes, o);
-    if (T && f.slots) hipLaunchKernelGGL(k_me_write_hit, dim3(blocks_for(T, kThreads)), dim3(kThreads), 0, st, f, bytes, o);
+    const FormatTail ft = format_tail(Lr, len, off, keep, keep ? b_kpos.as<uint64_t>(Lr) : nullptr, scal + S_BYTES, tot,
+                                      keep ? 2 : 1, b_tmp, out, st, "bedmap-elements", true);
+    uint8_t* o = static_cast<uint8_t*>(out.p);
+    hipLaunchKernelGGL(k_me_write_line, dim3(rblocks), dim3(kThreads), 0, st, f, len, off, ft.bytes, o);
+    if (T && f.slots) hipLaunchKernelGGL(k_me_write_hit, dim3(blocks_for(T, kThreads)), dim3(kThreads), 0, st, f, ft.bytes, o);
     HIP_CHECK(hipGetLastError());
-    res.out_bytes = bytes;
-    res.lines_out = keep ? tot[1] : Lr;
+    res.out_bytes = ft.bytes;
+    res.lines_out = ft.lines_kept;
     finish(4);
 }
 

@@ -51,16 +51,16 @@ struct HitList {
 struct MapelWorkspace {
     DevBuf b_scal, b_tmp, b_mlo, b_hier, b_cnt, b_hoff, b_H, b_R, b_rmax, b_lens[kListCols], b_P[kListCols], b_cs[kListCols],
         b_len, b_off, b_keep, b_kpos;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    StageTimer<5> timer;
     // Stages 1 to 3 for run() and for bedmap-scores (bed_mapscore.hip): parse
     // and checks, the map arrays, the count pass, the scan and the fill pass.
-    // name begins the messages; of opt the criterion alone is read.  ev3[0],
-    // ev3[1] and ev3[2] are recorded after the parse, the map arrays and the
-    // fill pass.  Returns how many of them were: 0 when both inputs are empty,
+    // name begins the messages; of opt the criterion alone is read.  Marks 0,
+    // 1 and 2 of tm are recorded after the parse, the map arrays and the fill
+    // pass.  Returns how many of them were: 0 when both inputs are empty,
     // 1 when the reference has no line, else 3, and only then does hl hold the
     // arrays.
     int hits(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, const char* name, const MapelOptions& opt,
-             const uint8_t* d_cat, uint64_t n, const std::vector<uint64_t>& in_end, hipStream_t st, hipEvent_t* ev3, HitList& hl);
+             const uint8_t* d_cat, uint64_t n, const std::vector<uint64_t>& in_end, hipStream_t st, StageMarks tm, HitList& hl);
     // The inputs lie back to back in d_cat[0, n) as for bm::MapWorkspace::run:
     // in_end has one entry (the reference is its own map) or two (reference,
     // then map).  One line per reference line goes to out (res.out_bytes of
@@ -69,7 +69,6 @@ struct MapelWorkspace {
     // describes.
     void run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, const MapelOptions& opt, const uint8_t* d_cat, uint64_t n,
              const std::vector<uint64_t>& in_end, hipStream_t st, DevBuf& out, MapelResult& res);
-    ~MapelWorkspace();
 };
 
 }  // namespace me

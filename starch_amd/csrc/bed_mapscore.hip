@@ -31,13 +31,16 @@
 //       k-th smallest value of line i is then at position hoff[i] + k - 1.
 //   5. format: k_ms_len measures every line, an exclusive sum places them,
 //      k_ms_write divides, rounds and writes the digits, and copies the echoed
-//      lines (sb::kWaveCopyBytes or more: by the whole wave).
+//      lines (sb::kWaveCopyBytes or more: by the whole wave).  The writer and
+//      its wave copy are bed_text.hpp's, the host steps between the two kernels
+//      format_tail's (common.hpp); both are shared with every BED command.
 #include <algorithm>
 #include <string>
 #include <vector>
 
 #include "../../include/starch_amd.h"
 #include "bed_mapscore.hpp"
+#include "bed_text.hpp"
 
 namespace ms {
 namespace {
@@ -50,9 +53,8 @@ enum : int { S_BYTES = 0, S_KEPT, S_STRADDLE, S_BAD, S_COUNT = 8 };   // device 
 typedef unsigned __int128 u128;
 typedef __int128 i128;
 
-inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return (unsigned)ceil_div(items, per_block); }
-
-__device__ __forceinline__ uint64_t line_begin(const uint64_t* __restrict__ line_end, uint64_t g) { return g ? line_end[g - 1] : 0; }
+using bt::dec_digits;
+using bt::line_beg;
 
 // ---- 4a. scores -----------------------------------------------------------------------
 // [+-]? D{1,9} ( '.' D{0,9} )?   or   [+-]? '.' D{1,9}   over the whole of column 5
@@ -63,7 +65,7 @@ k_ms_parse(const uint8_t* __restrict__ bed, const uint64_t* __restrict__ line_en
     const uint64_t j = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     if (j >= Lm) return;
     const uint64_t g = m0 + j, le = line_end[g] - 1;
-    uint64_t p = line_begin(line_end, g);
+    uint64_t p = line_beg(line_end, g);
     bool good = true;
     for (int c = 0; c < 4 && good; ++c) {
         while (p < le && bed[p] != '\t') ++p;
@@ -244,18 +246,6 @@ struct Format {
     uint8_t delim[8];
 };
 
-__device__ __forceinline__ uint32_t dec_digits(uint64_t v)
-{
-    uint32_t d = 1;
-    while (v >= 10) { v /= 10; ++d; }
-    return d;
-}
-
-__device__ __forceinline__ void put_dec(uint8_t* o, uint64_t v, uint32_t d)
-{
-    for (uint32_t k = d; k-- > 0;) { o[k] = (uint8_t)('0' + v % 10); v /= 10; }
-}
-
 // the k-th smallest (k from 1) score of line i
 __device__ __forceinline__ int64_t kth_value(const Format& f, uint64_t i, uint64_t k)
 {
@@ -331,7 +321,7 @@ __device__ __forceinline__ void element(const Format& f, uint32_t col, uint64_t 
 {
     const uint64_t h = col == STARCH_MAPSC_MIN_ELEMENT ? f.imin[i] : f.imax[i];
     const uint64_t g = f.m0 + f.H[h];
-    *src = line_begin(f.line_end, g);
+    *src = line_beg(f.line_end, g);
     *n = f.line_end[g] - 1 - *src;
 }
 
@@ -347,7 +337,7 @@ k_ms_len(const Format f, uint64_t* __restrict__ len, uint32_t* __restrict__ keep
         n = (uint64_t)f.delim_len * (f.ncols - 1) + 1;
         for (uint32_t k = 0; k < f.ncols; ++k) {
             const uint32_t col = f.cols[k];
-            if (col == STARCH_MAPSC_ECHO) n += f.line_end[i] - 1 - line_begin(f.line_end, i);
+            if (col == STARCH_MAPSC_ECHO) n += f.line_end[i] - 1 - line_beg(f.line_end, i);
             else if (col == STARCH_MAPSC_COUNT) n += dec_digits(c);
             else if (col == STARCH_MAPSC_INDICATOR) n += 1;
             else if (c == 0) n += 3;      // NAN
@@ -370,65 +360,37 @@ k_ms_write(const Format f, const uint64_t* __restrict__ len, const uint64_t* __r
 {
     const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     const int lane = threadIdx.x & 63;
-    uint64_t big_src[3] = {0, 0, 0}, big_dst[3] = {0, 0, 0}, big_len[3] = {0, 0, 0};
+    bt::Writer<3> w{out, 0};   // slots: the echo, the min element, the max element
     if (i < f.Lr && len[i] && off[i] + len[i] <= out_bytes) {
         const uint64_t c = f.cnt[i];
-        uint64_t o = off[i];
-        auto copy = [&](int slot, uint64_t src, uint64_t n) {
-            if (n >= sb::kWaveCopyBytes) { big_src[slot] = src; big_dst[slot] = o; big_len[slot] = n; }
-            else
-                for (uint64_t p = 0; p < n; ++p) out[o + p] = f.bed[src + p];
-            o += n;
-        };
+        w.o = off[i];
         for (uint32_t k = 0; k < f.ncols; ++k) {
             const uint32_t col = f.cols[k];
-            if (k)
-                for (uint32_t d = 0; d < f.delim_len; ++d) out[o++] = f.delim[d];
+            if (k) w.delim(f.delim, f.delim_len);
             if (col == STARCH_MAPSC_ECHO) {
-                const uint64_t b = line_begin(f.line_end, i);
-                copy(0, b, f.line_end[i] - 1 - b);
-            } else if (col == STARCH_MAPSC_COUNT) {
-                const uint32_t d = dec_digits(c);
-                put_dec(out + o, c, d);
-                o += d;
-            } else if (col == STARCH_MAPSC_INDICATOR) out[o++] = c ? '1' : '0';
-            else if (c == 0) {
-                out[o++] = 'N';
-                out[o++] = 'A';
-                out[o++] = 'N';
-            } else if (col >= STARCH_MAPSC_MIN_ELEMENT) {
+                const uint64_t b = line_beg(f.line_end, i);
+                w.copy(0, f.bed + b, f.line_end[i] - 1 - b);
+            } else if (col == STARCH_MAPSC_COUNT) w.dec(c);
+            else if (col == STARCH_MAPSC_INDICATOR) out[w.o++] = c ? '1' : '0';
+            else if (c == 0) w.bytes(reinterpret_cast<const uint8_t*>("NAN"), 3);
+            else if (col >= STARCH_MAPSC_MIN_ELEMENT) {
                 uint64_t src, m;
                 element(f, col, i, &src, &m);
-                copy(col == STARCH_MAPSC_MIN_ELEMENT ? 1 : 2, src, m);
+                if (col == STARCH_MAPSC_MIN_ELEMENT) w.copy(1, f.bed + src, m);   // (a constant slot keeps w in registers)
+                else w.copy(2, f.bed + src, m);
             } else {
                 const Num x = number(f, col, i, c);
                 const uint32_t d = num_len(x, f.prec);
-                num_put(out + o, x, f.prec, d);
-                o += d;
+                num_put(out + w.o, x, f.prec, d);
+                w.o += d;
             }
         }
-        out[o] = '\n';
+        out[w.o] = '\n';
     }
-#pragma unroll
-    for (int slot = 0; slot < 3; ++slot) {
-        unsigned long long m = __ballot(big_len[slot] != 0);
-        while (m) {
-            const int l = __ffsll(m) - 1;
-            m &= m - 1;
-            const uint64_t src = __shfl(big_src[slot], l, 64), dst = __shfl(big_dst[slot], l, 64),
-                           n = __shfl(big_len[slot], l, 64);
-            for (uint64_t p = lane; p < n; p += 64) out[dst + p] = f.bed[src + p];
-        }
-    }
+    bt::wave_copy_tails(w, out, lane);
 }
 
 }  // namespace
-
-MapscWorkspace::~MapscWorkspace()
-{
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-}
 
 void MapscWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, me::MapelWorkspace& hitter,
                          const MapscOptions& opt, const uint8_t* d_cat, uint64_t n, const std::vector<uint64_t>& in_end,
@@ -436,23 +398,15 @@ void MapscWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, m
 {
     res = MapscResult{};
     const uint64_t N = in_end.size();
-    for (auto& e : ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(STARCH_ERR_DEVICE, "hipEventCreate"); }
     (void)out.as<uint8_t>(64);
-    HIP_CHECK(hipEventRecord(ev[0], st));
+    timer.start(st);
     auto finish = [&](int from) {
-        for (int k = from; k < 6; ++k) HIP_CHECK(hipEventRecord(ev[k], st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_parse, ev[0], ev[1]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_build, ev[1], ev[2]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_query, ev[2], ev[3]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_reduce, ev[3], ev[4]));
-        HIP_CHECK(hipEventElapsedTime(&res.ms_format, ev[4], ev[5]));
+        timer.finish(from, st, {&res.ms_parse, &res.ms_build, &res.ms_query, &res.ms_reduce, &res.ms_format});
     };
 
     // 1 to 3. the hit list
     me::HitList hl;
-    const int done = hitter.hits(sorter, lines, "bedmap-scores", opt.crit, d_cat, n, in_end, st, ev + 1, hl);
+    const int done = hitter.hits(sorter, lines, "bedmap-scores", opt.crit, d_cat, n, in_end, st, timer.marks_from(1), hl);
     res.n_ref = hl.Lr;
     res.n_map = hl.Lm;
     res.n_chromosomes = hl.n_chromosomes;
@@ -532,7 +486,7 @@ void MapscWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, m
             }
         }
     }
-    HIP_CHECK(hipEventRecord(ev[4], st));
+    timer.mark(4, st);
 
     // 5. format
     f.bed = d_cat;
@@ -558,20 +512,14 @@ void MapscWorkspace::run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, m
     uint32_t* keep = opt.skip_unmapped ? b_keep.as<uint32_t>(Lr) : nullptr;
     hipLaunchKernelGGL(k_ms_len, dim3(rblocks), dim3(kThreads), 0, st, f, len, keep);
     HIP_CHECK(hipGetLastError());
-    scan::excl_sum_u64(len, off, Lr, scal + S_BYTES, b_tmp, st);
-    if (keep) {   // the kept lines are counted; the lengths of the others are 0, which leaves them out
-        scan::excl_sum_u32_to_u64(keep, b_kpos.as<uint64_t>(Lr), Lr, scal + S_KEPT, b_tmp, st);
-    }
+    // (the kept lines are counted; the lengths of the others are 0, which leaves them out)
     uint64_t tot[2] = {0, 0};
-    HIP_CHECK(hipMemcpyAsync(tot, scal + S_BYTES, (keep ? 2 : 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const uint64_t bytes = tot[0];
-    if (bytes >= (1ull << 40)) throw StarchError(STARCH_ERR_ARG, "bedmap-scores: result too large (2^40 bytes or more)");
-    uint8_t* o = out.as<uint8_t>(bytes + 64);
-    hipLaunchKernelGGL(k_ms_write, dim3(rblocks), dim3(kThreads), 0, st, f, len, off, bytes, o);
+    const FormatTail ft = format_tail(Lr, len, off, keep, keep ? b_kpos.as<uint64_t>(Lr) : nullptr, scal + S_BYTES, tot,
+                                      keep ? 2 : 1, b_tmp, out, st, "bedmap-scores", true);
+    hipLaunchKernelGGL(k_ms_write, dim3(rblocks), dim3(kThreads), 0, st, f, len, off, ft.bytes, static_cast<uint8_t*>(out.p));
     HIP_CHECK(hipGetLastError());
-    res.out_bytes = bytes;
-    res.lines_out = keep ? tot[1] : Lr;
+    res.out_bytes = ft.bytes;
+    res.lines_out = ft.lines_kept;
     finish(5);
 }
 

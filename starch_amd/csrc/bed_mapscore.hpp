@@ -38,7 +38,7 @@ struct MapscResult {
 
 struct MapscWorkspace {
     DevBuf b_scal, b_tmp, b_V, b_ok, b_lo, b_hi, b_min, b_max, b_imin, b_imax, b_key, b_len, b_off, b_keep, b_kpos;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    StageTimer<6> timer;
     // The inputs lie back to back in d_cat[0, n) as for me::MapelWorkspace::run,
     // whose stages 1 to 3 (hitter.hits) find the hits.  One line per reference
     // line goes to out (res.out_bytes of it).  The sorter's radix stage orders
@@ -46,7 +46,6 @@ struct MapscWorkspace {
     // describes.
     void run(sb::SortWorkspace& sorter, so::SetopWorkspace& lines, me::MapelWorkspace& hitter, const MapscOptions& opt,
              const uint8_t* d_cat, uint64_t n, const std::vector<uint64_t>& in_end, hipStream_t st, DevBuf& out, MapscResult& res);
-    ~MapscWorkspace();
 };
 
 }  // namespace ms

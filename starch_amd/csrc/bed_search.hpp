@@ -1,5 +1,6 @@
 // starch_amd/csrc/bed_search.hpp -- the binary searches over ordered per-line
-// arrays that bed_map.hip and bed_closest.hip share: device code only.
+// arrays that bed_map.hip, bed_closest.hip and bed_mapel.hip share, and the
+// per-chromosome bounds kernel of all three: device code only.
 #pragma once
 #include "common.hpp"
 

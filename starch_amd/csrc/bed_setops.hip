@@ -20,7 +20,7 @@
 //      distinct (rank, position) with the sum at its last end as depth
 //      (k_so_gather, k_so_groups); k_so_flags marks where an output interval
 //      starts and where it ends, k_so_emit compacts both.
-//   6. format: k_so_len, an exclusive sum, k_so_write.
+//   6. format: k_so_len, an exclusive sum, k_so_write (on bed_text.hpp's writer).
 //
 // Weights are 64-bit: input 0 counts 2^32, every other input 1, so one running
 // sum holds "input 0 covers this base" in its high half and the number of
@@ -37,6 +37,7 @@
 
 #include "../../include/starch_amd.h"
 #include "bed_setops.hpp"
+#include "bed_text.hpp"
 #include "seg_max.hpp"
 
 namespace so {
@@ -44,8 +45,6 @@ namespace {
 
 constexpr int kThreads = 256;
 enum : int { S_BAD = 0, S_RUNS, S_GROUPS, S_OUT, S_OUT_END, S_BYTES, S_COUNT = 8 };   // device scalars (u64)
-
-inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return (unsigned)ceil_div(items, per_block); }
 
 // ---- 1. first line of every input ----------------------------------------------
 // first[k + 1] = lines that end at or before in_end[k] (every input ends in '\n',
@@ -277,17 +276,7 @@ k_so_emit(const uint32_t* __restrict__ grp_rank, const uint64_t* __restrict__ gr
 }
 
 // ---- 6. format ------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t dec_digits(uint64_t v)
-{
-    uint32_t d = 1;
-    while (v >= 10) { v /= 10; ++d; }
-    return d;
-}
-
-__device__ __forceinline__ void put_dec(uint8_t* o, uint64_t v, uint32_t d)
-{
-    for (uint32_t k = d; k-- > 0;) { o[k] = (uint8_t)('0' + v % 10); v /= 10; }
-}
+using bt::dec_digits;
 
 __global__ void __launch_bounds__(kThreads)
 k_so_len(const uint32_t* __restrict__ o_rank, const uint64_t* __restrict__ o_start, const uint64_t* __restrict__ o_stop,
@@ -309,17 +298,13 @@ k_so_write(const uint8_t* __restrict__ bed, const uint32_t* __restrict__ o_rank,
     const uint32_t ds = dec_digits(s), dt = dec_digits(t);
     const uint64_t off = o_off[k];
     if (off + nl + ds + dt + 3 > out_bytes) return;
-    uint8_t* o = out + off;
-    const uint8_t* nm = bed + name_off[r];
-    for (uint32_t q = 0; q < nl; ++q) o[q] = nm[q];
-    o += nl;
-    *o++ = '\t';
-    put_dec(o, s, ds);
-    o += ds;
-    *o++ = '\t';
-    put_dec(o, t, dt);
-    o += dt;
-    *o = '\n';
+    bt::Writer<> w{out, off};
+    w.bytes(bed + name_off[r], nl);
+    w.tab();
+    w.dec(s, ds);
+    w.tab();
+    w.dec(t, dt);
+    out[w.o] = '\n';
 }
 
 // ---- 7. element-of: the largest overlap of a line with one run ---------------------
@@ -631,12 +616,6 @@ k_ch_expand(const uint32_t* __restrict__ o_rank, const uint64_t* __restrict__ o_
 
 }  // namespace
 
-SetopWorkspace::~SetopWorkspace()
-{
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-}
-
 uint64_t SetopWorkspace::stage_lines(sb::SortWorkspace& sorter, const char* tool, const uint8_t* d_cat, uint64_t n,
                                      const std::vector<uint64_t>& in_end, hipStream_t st, std::vector<uint64_t>& first)
 {
@@ -706,31 +685,23 @@ uint64_t SetopWorkspace::stage_merge(const uint64_t* start, const uint64_t* stop
     return R;
 }
 
-// records ev[from ..], waits for the stream and fills the stage times
+// records the timer's events from `from` on, waits for the stream and fills the stage times
 void SetopWorkspace::finish(hipStream_t st, SetopResult& res, int from)
 {
-    for (int k = from; k < 6; ++k) HIP_CHECK(hipEventRecord(ev[k], st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    HIP_CHECK(hipEventElapsedTime(&res.ms_parse, ev[0], ev[1]));
-    HIP_CHECK(hipEventElapsedTime(&res.ms_merge, ev[1], ev[2]));
-    HIP_CHECK(hipEventElapsedTime(&res.ms_sort, ev[2], ev[3]));
-    HIP_CHECK(hipEventElapsedTime(&res.ms_sweep, ev[3], ev[4]));
-    HIP_CHECK(hipEventElapsedTime(&res.ms_format, ev[4], ev[5]));
+    timer.finish(from, st, {&res.ms_parse, &res.ms_merge, &res.ms_sort, &res.ms_sweep, &res.ms_format});
 }
 
 void SetopWorkspace::run(sb::SortWorkspace& sorter, int op, const uint8_t* d_cat, uint64_t n,
                          const std::vector<uint64_t>& in_end, hipStream_t st, DevBuf& out, SetopResult& res)
 {
     res = SetopResult{};
-    for (auto& e : ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(STARCH_ERR_DEVICE, "hipEventCreate"); }
     (void)out.as<uint8_t>(64);
-    HIP_CHECK(hipEventRecord(ev[0], st));
+    timer.start(st);
     if (n == 0) return finish(st, res, 1);   // every input is empty: nothing is covered
     const uint64_t K = stage_intervals(sorter, op, d_cat, n, in_end, st, res);
     res.lines_out = K;
     if (K == 0) return finish(st, res, 4);
-    HIP_CHECK(hipEventRecord(ev[4], st));
+    timer.mark(4, st);
     res.out_bytes = stage_format(sorter, d_cat, b_o_rank.as<uint32_t>(K), b_o_start.as<uint64_t>(K), b_o_stop.as<uint64_t>(K), K,
                                  0, st, out);
     finish(st, res, 5);
@@ -743,7 +714,7 @@ uint64_t SetopWorkspace::stage_sweep(sb::SortWorkspace& sorter, const uint32_t* 
     // 4. the ends by (rank, position)
     const sb::KeyBits kb = sorter.stage_check(e_rank, e_pos, e_pos, E, st);
     const uint32_t* idx = kb.desc == ~0ull ? nullptr : sorter.stage_radix(e_rank, e_pos, nullptr, E, kb, st, &res.radix_passes);
-    HIP_CHECK(hipEventRecord(ev[3], st));
+    timer.mark(3, st);
 
     // 5. sweep
     const unsigned eblocks = blocks_for(E, kThreads);
@@ -785,7 +756,7 @@ uint64_t SetopWorkspace::stage_intervals(sb::SortWorkspace& sorter, int op, cons
     const unsigned lblocks = blocks_for(L, kThreads);
     if (L >= (1ull << 31))
         throw StarchError(STARCH_ERR_ARG, "bedops: 2^31 lines or more over all inputs (the interval ends are indexed with 32 bits)");
-    HIP_CHECK(hipEventRecord(ev[1], st));
+    timer.mark(1, st);
 
     // 3. per-input merge
     const uint64_t R = stage_merge(start, stop, head, L, st);
@@ -798,7 +769,7 @@ uint64_t SetopWorkspace::stage_intervals(sb::SortWorkspace& sorter, int op, cons
     hipLaunchKernelGGL(k_so_ends, dim3(lblocks), dim3(kThreads), 0, st, rank, start, incl, open, pos, L, first[1], e_rank,
                        e_pos, e_w);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev[2], st));
+    timer.mark(2, st);
 
     // 4, 5. the ends by (rank, position), and their groups
     const uint64_t G = stage_sweep(sorter, e_rank, e_pos, e_w, E, st, res);
@@ -892,7 +863,7 @@ void SetopWorkspace::element_of(sb::SortWorkspace& sorter, const BedopsOptions& 
         uint8_t* q_head = b_q_head.as<uint8_t>(Lq);
         hipLaunchKernelGGL(k_eo_heads, dim3(qblocks), dim3(kThreads), 0, st, q_rank, Lq, q_head);
         HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(ev[2], st));
+        timer.mark(2, st);
         const uint64_t R = stage_merge(q_start, q_stop, q_head, Lq, st);
         if (R == 0 || R > Lq) throw StarchError(STARCH_ERR_INTERNAL, "bedops: the run count is out of range");
         res.runs_merged = R;
@@ -921,9 +892,9 @@ void SetopWorkspace::element_of(sb::SortWorkspace& sorter, const BedopsOptions& 
         q.sp = sp;
         q.NT = NT;
     } else {
-        HIP_CHECK(hipEventRecord(ev[2], st));
+        timer.mark(2, st);
     }
-    HIP_CHECK(hipEventRecord(ev[3], st));
+    timer.mark(3, st);
 
     // overlap with one run, flags, and the lines that stay
     const unsigned rblocks = blocks_for(Lr, kThreads);
@@ -938,7 +909,7 @@ void SetopWorkspace::element_of(sb::SortWorkspace& sorter, const BedopsOptions& 
     HIP_CHECK(hipStreamSynchronize(st));
     if (K > Lr) throw StarchError(STARCH_ERR_INTERNAL, "bedops: more lines kept than there are");
     res.lines_out = K;
-    HIP_CHECK(hipEventRecord(ev[4], st));
+    timer.mark(4, st);
     if (K) {
         uint32_t* order = b_order.as<uint32_t>(K);
         hipLaunchKernelGGL(k_eo_compact, dim3(rblocks), dim3(kThreads), 0, st, keep, kpos, Lr, K, order);
@@ -960,7 +931,7 @@ void SetopWorkspace::partition(sb::SortWorkspace& sorter, const uint8_t* d_cat, 
     hipLaunchKernelGGL(k_pt_ends, dim3(blocks_for(L, kThreads)), dim3(kThreads), 0, st, sorter.ln.rank, sorter.ln.start,
                        sorter.ln.stop, L, e_rank, e_pos, e_w);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev[2], st));
+    timer.mark(2, st);
     const uint64_t G = stage_sweep(sorter, e_rank, e_pos, e_w, E, st, res);
     const unsigned gblocks = blocks_for(G, kThreads);
     uint32_t* f_start = b_f_start.as<uint32_t>(G);
@@ -979,7 +950,7 @@ void SetopWorkspace::partition(sb::SortWorkspace& sorter, const uint8_t* d_cat, 
     hipLaunchKernelGGL(k_pt_emit, dim3(gblocks), dim3(kThreads), 0, st, grp_rank, grp_pos, f_start, p_start, G, K, o_rank,
                        o_start, o_stop);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev[4], st));
+    timer.mark(4, st);
     res.out_bytes = stage_format(sorter, d_cat, o_rank, o_start, o_stop, K, 0, st, out);
     finish(st, res, 5);
 }
@@ -1012,7 +983,7 @@ void SetopWorkspace::chop(sb::SortWorkspace& sorter, const BedopsOptions& opt, c
     hipLaunchKernelGGL(k_ch_expand, dim3(blocks_for(T, kExpandTile)), dim3(kExpandTile), 0, st, o_rank, o_start, o_stop, coff, K,
                        T, opt.chop, opt.stagger, c_rank, c_start, c_stop);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(ev[4], st));
+    timer.mark(4, st);
     res.out_bytes = stage_format(sorter, d_cat, c_rank, c_start, c_stop, T, 1ull << 40, st, out);
     finish(st, res, 5);
 }
@@ -1021,13 +992,13 @@ void SetopWorkspace::chop(sb::SortWorkspace& sorter, const BedopsOptions& opt, c
 void SetopWorkspace::everything(sb::SortWorkspace& sorter, const uint8_t* d_cat, uint64_t n, uint64_t L, hipStream_t st,
                                 DevBuf& out, SetopResult& res)
 {
-    HIP_CHECK(hipEventRecord(ev[2], st));
+    timer.mark(2, st);
     const sb::KeyBits kb = sorter.stage_check(sorter.ln.rank, sorter.ln.start, sorter.ln.stop, L, st);
     const uint32_t* order = kb.desc == ~0ull ? nullptr
                                              : sorter.stage_radix(sorter.ln.rank, sorter.ln.start, sorter.ln.stop, L, kb, st,
                                                                   &res.radix_passes);
-    HIP_CHECK(hipEventRecord(ev[3], st));
-    HIP_CHECK(hipEventRecord(ev[4], st));
+    timer.mark(3, st);
+    timer.mark(4, st);
     res.lines_out = L;
     if (!order) {   // the inputs one after the other are in order as they stand
         const bool open_end = sorter.ln.open_end;
@@ -1046,10 +1017,8 @@ void SetopWorkspace::run_bedops(sb::SortWorkspace& sorter, const BedopsOptions& 
 {
     if (opt.op <= STARCH_SETOP_COMPLEMENT) return run(sorter, opt.op, d_cat, n, in_end, st, out, res);
     res = SetopResult{};
-    for (auto& e : ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(STARCH_ERR_DEVICE, "hipEventCreate"); }
     (void)out.as<uint8_t>(64);
-    HIP_CHECK(hipEventRecord(ev[0], st));
+    timer.start(st);
     if (n == 0) return finish(st, res, 1);   // every input is empty
     if (opt.op == STARCH_SETOP_CHOP) {
         const uint64_t K = stage_intervals(sorter, STARCH_SETOP_MERGE, d_cat, n, in_end, st, res);
@@ -1062,7 +1031,7 @@ void SetopWorkspace::run_bedops(sb::SortWorkspace& sorter, const BedopsOptions& 
     res.n_chromosomes = sorter.n_chromosomes;
     if (L >= (1ull << 31))
         throw StarchError(STARCH_ERR_ARG, "bedops: 2^31 lines or more over all inputs (the interval ends are indexed with 32 bits)");
-    HIP_CHECK(hipEventRecord(ev[1], st));
+    timer.mark(1, st);
     if (opt.op == STARCH_SETOP_PARTITION) return partition(sorter, d_cat, L, st, out, res);
     if (opt.op == STARCH_SETOP_EVERYTHING) return everything(sorter, d_cat, n, L, st, out, res);
     element_of(sorter, opt, d_cat, L, first[1], st, out, res);

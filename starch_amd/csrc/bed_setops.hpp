@@ -36,7 +36,7 @@ struct SetopWorkspace {
     // element-of: the other inputs' lines in order, their runs and the range maximum; chop: counts and pieces
     DevBuf b_q_rank, b_q_start, b_q_stop, b_q_head, b_u_rank, b_u_start, b_u_stop, b_rmq, b_keep, b_kpos, b_order, b_cnt,
         b_coff, b_c_rank, b_c_start, b_c_stop;
-    hipEvent_t ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    StageTimer<6> timer;
     // The op (STARCH_SETOP_MERGE .. _COMPLEMENT) over the inputs that lie back to
     // back in d_cat[0, n): input k is d_cat[in_end[k-1], in_end[k]) (in_end[-1] = 0), and
     // every non-empty input ends in '\n'.  The BED3 result goes to out
@@ -64,16 +64,15 @@ struct SetopWorkspace {
     uint8_t* head = nullptr;
     uint64_t *incl = nullptr, *pos = nullptr;
     uint32_t* open = nullptr;
-    ~SetopWorkspace();
 
 private:
     // 4, 5a. E < 2^32 weighted ends ordered by (rank, position) and swept: one
     // group per distinct (rank, position) in grp_rank / grp_pos / grp_depth.
-    // Records ev[3] after the order.  Returns the number of groups.
+    // Records ev[3] of the timer after the order.  Returns the number of groups.
     uint64_t stage_sweep(sb::SortWorkspace& sorter, const uint32_t* e_rank, const uint64_t* e_pos, const uint64_t* e_w,
                          uint64_t E, hipStream_t st, SetopResult& res);
     // 1 to 5 of run(): the K result intervals in o_rank / o_start / o_stop.
-    // Records ev[1] to ev[3]; first: as stage_lines leaves it.
+    // Records ev[1] to ev[3] of the timer; first: as stage_lines leaves it.
     uint64_t stage_intervals(sb::SortWorkspace& sorter, int op, const uint8_t* d_cat, uint64_t n,
                              const std::vector<uint64_t>& in_end, hipStream_t st, SetopResult& res);
     // 6. K > 0 intervals as BED3 into out; returns the bytes.  limit: the result

@@ -1,6 +1,7 @@
-// starch_amd/csrc/bed_text.hpp -- device helpers of the per-line text converters
-// (bed_convert.hip, bed_align.hip): line bounds, decimal numbers in and out, and
-// the output cursor of a thread with the tail it leaves to its wave.
+// starch_amd/csrc/bed_text.hpp -- device helpers of every BED command that writes
+// text (bed_map, bed_mapel, bed_mapscore, bed_closest, bed_setops, bed_convert,
+// bed_align; sort_bed.hip takes line_beg): line bounds, decimal numbers in and
+// out, and the output cursor of a thread with the copies it leaves to its wave.
 #pragma once
 #include "common.hpp"
 #include "sort_bed.hpp"
@@ -48,43 +49,60 @@ __device__ __forceinline__ uint32_t parse_coord(const uint8_t* __restrict__ s, u
 
 __device__ __forceinline__ bool is_blank(uint8_t c) { return c == ' ' || c == '\t'; }
 
-struct Writer {            // one thread's output cursor, and the tail it leaves to the wave
+// One thread's output cursor, and the copies it leaves to its wave: a copy of
+// sb::kWaveCopyBytes or more is not made by the thread but noted in the slot
+// the caller names (a slot holds one copy) and made by wave_copy_tails.
+template <int kSlots = 1>
+struct Writer {
     uint8_t* out;
     uint64_t o;
-    const uint8_t* big_src = nullptr;
-    uint64_t big_dst = 0, big_len = 0;
+    const uint8_t* big_src[kSlots] = {};
+    uint64_t big_dst[kSlots] = {}, big_len[kSlots] = {};
     __device__ __forceinline__ void bytes(const uint8_t* __restrict__ s, uint64_t n)
     {
         for (uint64_t p = 0; p < n; ++p) out[o + p] = s[p];
         o += n;
     }
     __device__ __forceinline__ void tab() { out[o++] = '\t'; }
-    __device__ __forceinline__ void dec(uint64_t v)
+    __device__ __forceinline__ void delim(const uint8_t* d, uint32_t len)
     {
-        const uint32_t d = dec_digits(v);
+        for (uint32_t k = 0; k < len; ++k) out[o++] = d[k];
+    }
+    __device__ __forceinline__ void dec(uint64_t v, uint32_t d)   // d = dec_digits(v)
+    {
         put_dec(out + o, v, d);
         o += d;
+    }
+    __device__ __forceinline__ void dec(uint64_t v) { dec(v, dec_digits(v)); }
+    // n bytes at s: written here when short, left to the wave in `slot` when long
+    __device__ __forceinline__ void copy(int slot, const uint8_t* __restrict__ s, uint64_t n)
+    {
+        if (n >= sb::kWaveCopyBytes) { big_src[slot] = s; big_dst[slot] = o; big_len[slot] = n; o += n; }
+        else bytes(s, n);
     }
     // the last column and the '\n'
     __device__ __forceinline__ void tail(const uint8_t* __restrict__ s, uint64_t n)
     {
-        if (n >= sb::kWaveCopyBytes) { big_src = s; big_dst = o; big_len = n; o += n; }
-        else bytes(s, n);
+        copy(0, s, n);
         out[o++] = '\n';
     }
 };
 
-// the tails that the lanes of this wave left in w, copied lane after lane by the
-// whole wave (every lane of the wave calls this)
-__device__ __forceinline__ void wave_copy_tails(const Writer& w, uint8_t* __restrict__ out, int lane)
+// the copies that the lanes of this wave left in w, made slot after slot and
+// lane after lane by the whole wave (every lane of the wave calls this)
+template <int kSlots>
+__device__ __forceinline__ void wave_copy_tails(const Writer<kSlots>& w, uint8_t* __restrict__ out, int lane)
 {
-    unsigned long long m = __ballot(w.big_len != 0);
-    while (m) {
-        const int l = __ffsll(m) - 1;
-        m &= m - 1;
-        const uint8_t* src = reinterpret_cast<const uint8_t*>(__shfl((uint64_t)reinterpret_cast<uintptr_t>(w.big_src), l, 64));
-        const uint64_t dst = __shfl(w.big_dst, l, 64), len = __shfl(w.big_len, l, 64);
-        for (uint64_t p = lane; p < len; p += 64) out[dst + p] = src[p];
+#pragma unroll
+    for (int slot = 0; slot < kSlots; ++slot) {
+        unsigned long long m = __ballot(w.big_len[slot] != 0);
+        while (m) {
+            const int l = __ffsll(m) - 1;
+            m &= m - 1;
+            const uint8_t* src = reinterpret_cast<const uint8_t*>(__shfl((uint64_t)reinterpret_cast<uintptr_t>(w.big_src[slot]), l, 64));
+            const uint64_t dst = __shfl(w.big_dst[slot], l, 64), len = __shfl(w.big_len[slot], l, 64);
+            for (uint64_t p = lane; p < len; p += 64) out[dst + p] = src[p];
+        }
     }
 }
 

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -31,6 +32,52 @@ struct StarchError : std::runtime_error {
     } while (0)
 
 static inline uint64_t ceil_div(uint64_t a, uint64_t b) { return (a + b - 1) / b; }
+// workgroups of per_block items each that cover `items`
+static inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return (unsigned)ceil_div(items, per_block); }
+
+// Events base, base + 1, ... of a StageTimer, for a stage that two workspaces share.
+struct StageMarks {
+    hipEvent_t* ev;
+    void mark(int k, hipStream_t st) const { HIP_CHECK(hipEventRecord(ev[k], st)); }
+};
+
+// The stage timer of a workspace: N events on one stream, created on first use.
+// Stage k runs from event k to event k + 1.
+template <int N>
+struct StageTimer {
+    hipEvent_t ev[N] = {};
+    StageTimer() = default;
+    StageTimer(const StageTimer&) = delete;
+    StageTimer& operator=(const StageTimer&) = delete;
+    ~StageTimer()
+    {
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+    // creates what is missing and records event 0
+    void start(hipStream_t st)
+    {
+        for (auto& e : ev)
+            if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(-10, "hipEventCreate"); }   // (STARCH_ERR_DEVICE, as HIP_CHECK)
+        mark(0, st);
+    }
+    void mark(int k, hipStream_t st) { HIP_CHECK(hipEventRecord(ev[k], st)); }
+    StageMarks marks_from(int base) { return StageMarks{ev + base}; }
+    float elapsed(int a, int b) const   // ms from event a to event b, both complete
+    {
+        float ms = 0;
+        HIP_CHECK(hipEventElapsedTime(&ms, ev[a], ev[b]));
+        return ms;
+    }
+    // records events from .. N - 1, waits for the stream and leaves the time of stage k in *ms[k]
+    void finish(int from, hipStream_t st, std::initializer_list<float*> ms)
+    {
+        for (int k = from; k < N; ++k) mark(k, st);
+        HIP_CHECK(hipStreamSynchronize(st));
+        int k = 0;
+        for (float* m : ms) { *m = elapsed(k, k + 1); ++k; }
+    }
+};
 
 // ---------------------------------------------------------------------------
 // Device workspace: grow-only buffers owned by the context.
@@ -402,3 +449,27 @@ void excl_sum_u32_to_u64(const uint32_t* in, uint64_t* out, uint64_t n, uint64_t
 // In-place inclusive max-scan of u64 (used for "index of last valid" propagation).
 void incl_max_u64(uint64_t* data, uint64_t n, DevBuf& tmp, hipStream_t st);
 }  // namespace scan
+
+// The format tail of a BED command between its k_*_len and its k_*_write: the
+// Lr line lengths in len summed into the offsets off, the kept lines counted
+// (keep and kpos may be NULL: every line is kept), the device scalars
+// d_tot[0, n_tot) copied to tot, and out sized for the result.  d_tot[0]
+// receives the bytes and, with keep, d_tot[1] the kept lines; what lies after
+// them is the caller's and comes along.  limit: the result is refused with
+// `tool` in front when it has 2^40 bytes or more.
+struct FormatTail {
+    uint64_t bytes, lines_kept;
+};
+inline FormatTail format_tail(uint64_t Lr, const uint64_t* len, uint64_t* off, const uint32_t* keep, uint64_t* kpos,
+                              uint64_t* d_tot, uint64_t* tot, int n_tot, DevBuf& tmp, DevBuf& out, hipStream_t st,
+                              const char* tool, bool limit)
+{
+    scan::excl_sum_u64(len, off, Lr, d_tot, tmp, st);
+    if (keep) scan::excl_sum_u32_to_u64(keep, kpos, Lr, d_tot + 1, tmp, st);
+    HIP_CHECK(hipMemcpyAsync(tot, d_tot, n_tot * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (limit && tot[0] >= (1ull << 40))   // (STARCH_ERR_ARG)
+        throw StarchError(-2, std::string(tool) + ": result too large (2^40 bytes or more)");
+    (void)out.as<uint8_t>(tot[0] + 64);
+    return FormatTail{tot[0], keep ? tot[1] : Lr};
+}

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "../../include/starch_amd.h"
+#include "bed_text.hpp"
 #include "sort_bed.hpp"
 
 namespace sb {
@@ -148,10 +149,7 @@ __device__ __forceinline__ uint32_t parse_coord(const uint8_t* __restrict__ bed,
 
 // line i is bed[beg, end): end excludes its '\n' (line_end holds one past it;
 // the entry of a last line without '\n' is n + 1)
-__device__ __forceinline__ uint64_t line_beg(const uint64_t* __restrict__ line_end, uint64_t i)
-{
-    return i ? line_end[i - 1] : 0;
-}
+using bt::line_beg;
 
 __global__ void __launch_bounds__(kThreads)
 k_sb_parse(const uint8_t* __restrict__ bed, const uint64_t* __restrict__ line_end, uint64_t L,
@@ -476,8 +474,6 @@ __global__ void __launch_bounds__(kThreads) k_sb_iota(uint32_t* idx, uint64_t L)
     if (i < L) idx[i] = (uint32_t)i;
 }
 
-inline unsigned blocks_for(uint64_t items, uint64_t per_block) { return (unsigned)ceil_div(items, per_block); }
-
 }  // namespace
 
 const char* bad_text(uint32_t k)
@@ -499,12 +495,6 @@ const char* bad_text(uint32_t k)
     }
 }
 
-
-SortWorkspace::~SortWorkspace()
-{
-    for (auto& e : ev)
-        if (e) (void)hipEventDestroy(e);
-}
 
 uint64_t SortWorkspace::stage_frame(const uint8_t* d_bed, uint64_t n, hipStream_t st)
 {
@@ -725,15 +715,13 @@ void SortWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, bool c
 {
     res = SortResult{};
     if (n == 0) return;
-    for (auto& e : ev)
-        if (!e && hipEventCreate(&e) != hipSuccess) { e = nullptr; throw StarchError(STARCH_ERR_DEVICE, "hipEventCreate"); }
-    HIP_CHECK(hipEventRecord(ev[0], st));
+    timer.start(st);
 
     // 1. line index and parse
     uint64_t bad = 0;
     const uint64_t L = stage_parse(d_bed, n, st, &bad);
     res.n_lines = L;
-    HIP_CHECK(hipEventRecord(ev[1], st));
+    timer.mark(1, st);
     if (bad != ~0ull)
         throw StarchError(STARCH_ERR_DATA, "sort-bed: line " + std::to_string((bad >> 8) + 1) + ": " +
                                                bad_text((uint32_t)(bad & 255)));
@@ -741,22 +729,22 @@ void SortWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, bool c
     // 2. chromosome ranks
     stage_rank(d_bed, st);
     res.n_chromosomes = n_chromosomes;
-    HIP_CHECK(hipEventRecord(ev[2], st));
+    timer.mark(2, st);
 
     // 3. order check
     const KeyBits kb = stage_check(ln.rank, ln.start, ln.stop, L, st);
     res.already_sorted = kb.desc == ~0ull;
     res.first_unsorted_line = res.already_sorted ? 0 : kb.desc + 1;
     if (check_only) {
-        HIP_CHECK(hipEventRecord(ev[3], st));
-        HIP_CHECK(hipEventRecord(ev[4], st));
+        timer.mark(3, st);
+        timer.mark(4, st);
     } else {
         const bool open_end = ln.open_end;
         unsigned long long* uscal = reinterpret_cast<unsigned long long*>(b_scal.as<uint64_t>(S_COUNT));
         res.out_bytes = n + (open_end ? 1 : 0);
         uint8_t* o = out.as<uint8_t>(res.out_bytes + 64);
         if (res.already_sorted) {
-            HIP_CHECK(hipEventRecord(ev[3], st));
+            timer.mark(3, st);
             HIP_CHECK(hipMemcpyAsync(o, d_bed, n, hipMemcpyDeviceToDevice, st));
             if (open_end) HIP_CHECK(hipMemsetAsync(o + n, '\n', 1, st));
         } else {
@@ -772,18 +760,14 @@ void SortWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, bool c
                 spare = b_idx[1].as<uint32_t>(L);
             }
             HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipEventRecord(ev[3], st));
+            timer.mark(3, st);
             // 5. gather
             (void)stage_gather(d_bed, order, L, res.out_bytes, spare, st, out);
         }
-        HIP_CHECK(hipEventRecord(ev[4], st));
+        timer.mark(4, st);
     }
-    HIP_CHECK(hipStreamSynchronize(st));
-    HIP_CHECK(hipEventElapsedTime(&res.ms_parse, ev[0], ev[1]));
-    HIP_CHECK(hipEventElapsedTime(&res.ms_rank, ev[1], ev[2]));
-    HIP_CHECK(hipEventElapsedTime(&res.ms_sort, ev[2], ev[3]));
-    HIP_CHECK(hipEventElapsedTime(&res.ms_gather, ev[3], ev[4]));
-    HIP_CHECK(hipEventElapsedTime(&res.ms_total, ev[0], ev[4]));
+    timer.finish(5, st, {&res.ms_parse, &res.ms_rank, &res.ms_sort, &res.ms_gather});   // (every event is recorded)
+    res.ms_total = timer.elapsed(0, 4);
 }
 
 }  // namespace sb

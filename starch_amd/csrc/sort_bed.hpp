@@ -33,7 +33,7 @@ const char* bad_text(uint32_t kind);
 struct SortWorkspace {
     DevBuf b_tile_cnt, b_tile_off, b_scal, b_tmp, b_line_end, b_start, b_stop, b_chr_len, b_hash, b_rank, b_keys, b_rep,
         b_ent, b_names, b_name_dst, b_slot_rank, b_idx[2], b_digit, b_hist, b_hist_off, b_len, b_out_off;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    StageTimer<5> timer;
     // Sorts the BED bytes d_bed[0, n) into out (res.out_bytes of it); check_only
     // stops after the order check and leaves out alone.  Throws StarchError
     // (STARCH_ERR_DATA naming the first malformed line, STARCH_ERR_ARG for 2^32
@@ -76,7 +76,6 @@ struct SortWorkspace {
     uint64_t stage_gather(const uint8_t* d_bed, const uint32_t* order, uint64_t K, uint64_t bytes, uint32_t* long_list,
                           hipStream_t st, DevBuf& out);
     DevBuf b_long;
-    ~SortWorkspace();
 };
 
 }  // namespace sb

@@ -98,6 +98,17 @@ def test_shapes(ctx):
     check(ctx, a, q, dist=True, delim=b"<=delim>")                       # 8 bytes
 
 
+def test_lines_left_to_the_wave(ctx):
+    import starch_amd
+    from tests import wave_lines
+    W = starch_amd.sort_constants()[1]
+    # long reference lines and right elements at lanes 0 and 63 of the first wave and lane 0 of the
+    # third (the left elements one lane on), then no long line at all
+    for r, q in wave_lines.wave_pairs(W):
+        for kw in (dict(dist=True), dict(dist=True, delim=b"<=>"), dict(closest=True, delim=b"<=>"), dict(no_ref=True)):
+            check(ctx, r, q, **kw)
+
+
 def test_every_combination_of_the_flags(ctx):
     rng = random.Random(1)
     r = random_bed(rng, [b"chr1", b"chr2"], 400)

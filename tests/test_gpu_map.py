@@ -100,6 +100,17 @@ def test_shapes(ctx):
         ctx.bedmap(a, m, cols=("sum",))
 
 
+def test_echoes_left_to_the_wave(ctx):
+    import starch_amd
+    from tests import wave_lines
+    W = starch_amd.sort_constants()[1]
+    # long echoes at lanes 0 and 63 of the first wave and lane 0 of the third, then none at all
+    for r, m in wave_lines.wave_pairs(W):
+        check(ctx, r, m, cols=("echo", "count"))
+        check(ctx, r, m, cols=("count", "echo", "bases"), delim=b"<=>")       # the cursor after a 3-byte delimiter
+        check(ctx, r, m, cols=("echo", "bases_uniq"), delim=b"<=>", skip_unmapped=True)
+
+
 def test_stats(ctx):
     rng = random.Random(2)
     r = random_bed(rng, [b"chr1", b"chr2"], 500)

@@ -188,6 +188,25 @@ def test_heavy_lines_take_the_wave_path(ctx, K):
     assert ctx.mapel_stats()["heavy_lines"] == 3
 
 
+def test_lines_and_hits_left_to_the_wave(ctx):
+    import starch_amd
+    from tests import wave_lines
+    W = starch_amd.sort_constants()[1]
+    # reference line k has the one hit k: long echoes and long hits at lanes 0 and 63 of the first wave
+    # and lane 0 of the third, then none at all
+    for r, m in wave_lines.wave_pairs(W):
+        check(ctx, r, m, cols=("echo", "echo_map"))
+        assert ctx.mapel_stats()["hits"] == wave_lines.WAVE_LINES
+        check(ctx, r, m, cols=("echo_map", "count", "echo"), delim=b"<=>", multidelim=b", ")
+    # the id and the score of a hit long too: all three slots of one lane
+    spots = wave_lines.WAVE_SPOTS
+    m = b"".join(b"chr1\t%d\t%d\t%s\t%s\n" % (10 * k + 1, 10 * k + 3, b"i" * (W + 5 if k in spots else 4), b"7" * (W + 9 if k in spots else 2))
+                 for k in range(wave_lines.WAVE_LINES))
+    check(ctx, wave_lines.lines(wave_lines.WAVE_LINES, spots, W), m, cols=("echo", "echo_map", "echo_map_id", "echo_map_score"))
+    # two hits per reference line: every piece after the first follows its multi-delimiter
+    check(ctx, wave_lines.lines(wave_lines.WAVE_LINES // 2, (), W, width=15), m, cols=("echo_map_id", "echo_map"), multidelim=b"<;>")
+
+
 def test_long_map_lines_are_copied_by_the_wave(ctx):
     import starch_amd
     W = starch_amd.sort_constants()[1]

@@ -258,6 +258,31 @@ def test_long_element_lines_and_ties(ctx, K):
     check(ctx, mp, None, cols=("echo", "min_element", "max_element"), criterion=("range", 3))
 
 
+def test_every_mix_of_short_and_long_copies(ctx, K):
+    import itertools
+    from tests import wave_lines
+    W = K[1]
+    # the echoed line, the min element and the max element W - 1, W or W + 1 bytes long: every mix with a long one
+    mixes = [s for s in itertools.product((W - 1, W, W + 1), repeat=3) if max(s) >= W]
+    assert len(mixes) == 26
+    ref, mp = [], []
+    for k in range(8 * len(mixes)):
+        e, lo, hi = mixes[k % len(mixes)]
+        ref.append(wave_lines.line(k, e, width=9))
+        mp.append(wave_lines.line(k, lo, off=1, width=1, score=b"1"))
+        mp.append(wave_lines.line(k, hi, off=3, width=1, score=b"2"))
+    check(ctx, b"".join(ref), b"".join(mp), cols=("echo", "min_element", "max_element"))
+    check(ctx, b"".join(ref), b"".join(mp), cols=("max_element", "sum", "echo", "min_element"), delim=b"<=>")
+
+
+def test_copies_left_to_the_wave(ctx, K):
+    from tests import wave_lines
+    # the echo and both elements long at lanes 0 and 63 of the first wave and lane 0 of the third, then none at all
+    for r, m in wave_lines.wave_pairs(K[1]):
+        check(ctx, r, m, cols=("echo", "min_element", "max_element"))
+        check(ctx, r, m, cols=("count", "max_element", "echo"), skip_unmapped=True)
+
+
 # ---- 4. errors ---------------------------------------------------------------------------------------------------------------
 def _refused(ctx, ref, mp, code, *words, **kw):
     import starch_amd

@@ -218,7 +218,12 @@ def test_the_size_limits_are_decided_before_the_buffers():
     assert '": result too large (2^32 hits or more)"' in hits
     src = open(os.path.join(ROOT, "starch_amd", "csrc", "bed_mapscore.hip")).read()
     assert "hitter.hits(sorter, lines, \"bedmap-scores\"" in src
-    assert src.index("bytes >= (1ull << 40)") < src.index("out.as<uint8_t>(bytes + 64)")
+    # the 2^40 refusal is the shared format tail's: asked for here, and decided there before the output is sized
+    call = re.search(r'format_tail\([^;]*"bedmap-scores", true\);', src)
+    assert call and call.start() < src.index("hipLaunchKernelGGL(k_ms_write")
+    common = open(os.path.join(ROOT, "starch_amd", "csrc", "common.hpp")).read()
+    tail = common[common.index("inline FormatTail format_tail("):]
+    assert tail.index("limit && tot[0] >= (1ull << 40)") < tail.index("out.as<uint8_t>(tot[0] + 64)")
 
 
 def test_argument_errors_touch_no_device():
