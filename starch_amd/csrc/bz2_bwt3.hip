@@ -2555,8 +2555,20 @@ k3_sort_grp(Ctx c, const uint64_t* __restrict__ items,
     uint32_t* bst = bst_all[g];
     uint32_t* bcur = bcur_all[g];
     const int tg = wid * 64 + lane;
+    // groups per queue pop, S (E = 2) and S2 (E = 4).  With the pop waited for where it
+    // was issued, small chunks lost to the atomic's latency (8 / 16 / 32 / 64 / 128 for
+    // both: cfg2 block sort 25.0, 20.5, 19.7, 20.0, 21.8 ms) and the code sat at 32 / 16.
+    // With the pop prefetched (WaveQueue), one-lane cfg2, both macros at the same value,
+    // per step: kernel ms and fetched bytes of k3_sort_grp<1,2> | <1,4>, and ms_bwt
+    //   (waited, 32 / 16)   4.03 ms 4.65 GB | 1.88 ms  6.61 GB | 17.86
+    //   32                  3.68 ms 5.35 GB | 2.15 ms 14.56 GB | 17.83
+    //   16                  3.59 ms 2.36 GB | 1.68 ms  6.54 GB | 17.05
+    //    8                  3.62 ms 2.19 GB | 1.57 ms  1.64 GB | 17.21
+    //    4                  3.70 ms 2.14 GB | 1.57 ms  1.26 GB | 16.76
+    // (profiles/r07_queue/).  The bytes fall to a third; the time follows only a little
+    // way: with their keys in L2 these sorts wait on LDS and issue, not on HBM.
 #ifndef STARCH_GRP_CHUNK
-#define STARCH_GRP_CHUNK 32   // groups per queue pop (cfg2 block sort: 8 / 16 / 32 / 64 / 128: 25.0, 20.5, 19.7, 20.0, 21.8 ms)
+#define STARCH_GRP_CHUNK 8
 #endif
     // dynamic assignment (NW == 1): each wave pops groups, STARCH_GRP_CHUNK at a time,
     // from its XCD's queue, so the XCD's waves stay on neighbouring groups (one block's
@@ -2567,8 +2579,8 @@ k3_sort_grp(Ctx c, const uint64_t* __restrict__ items,
     const uint32_t xs = xcc_id();
     load_qsizes_binned(c, qs);
 #ifndef STARCH_GRP_CHUNK_S2
-#define STARCH_GRP_CHUNK_S2 16   // S2 (E = 4): 8 / 16 / 32 -> ms_bwt 19.17 / 18.91 / 18.97; at 32 the groups in flight
-#endif                           // span more blocks per XCD (S2 fetch 6.5 -> 14.5 GB per cfg2 step)
+#define STARCH_GRP_CHUNK_S2 8    // (table above: at 16 and 32 the groups in flight span more blocks per XCD than its L2 holds)
+#endif
     WaveQueue<E == 4 ? STARCH_GRP_CHUNK_S2 : STARCH_GRP_CHUNK> wq;
     constexpr uint32_t NONE = 0xFFFFFFFFu;
     // software pipeline, two groups deep: while group n sorts, the keys of
@@ -2606,7 +2618,9 @@ k3_sort_grp(Ctx c, const uint64_t* __restrict__ items,
     // the next group's key gathers go out now, so they are in flight during
     // this group's LDS-only sort phases (issued after the sort, the emit's
     // returning atomics and the queue pops waited for them at once: every
-    // vmcnt wait is in issue order)
+    // vmcnt wait is in issue order).  The pop of the next chunk of groups goes
+    // out ahead of them for the same reason; next() reads it chunks later
+    wq.prefetch(c.qhead, xs);
     grp_load_keys<NW, E, DBL>(c, nxt, wid, lane);
     diff = wave_reduce_or64(diff);
     if constexpr (NW > 1) {

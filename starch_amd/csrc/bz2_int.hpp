@@ -67,11 +67,12 @@ __device__ __forceinline__ uint32_t xq_pop(uint32_t* head, const uint32_t* qsize
     return 0xFFFFFFFFu;
 }
 
-// Chunked pop: up to k consecutive items; cnt = how many.  Called by one lane.
+// Chunked pop: up to k consecutive items; cnt = how many.  Queues x + t0 ..
+// x + 7 (mod 8) are tried in turn.  Called by one lane.
 __device__ __forceinline__ uint32_t xq_pop_n(uint32_t* head, const uint32_t* qsize, uint32_t x, uint32_t k,
-                                             uint32_t& cnt)
+                                             uint32_t& cnt, uint32_t t0 = 0)
 {
-    for (uint32_t t = 0; t < 8; ++t) {
+    for (uint32_t t = t0; t < 8; ++t) {
         const uint32_t y = (x + t) & 7u;
         const uint32_t sz = qsize[y];
         if (__hip_atomic_load(head + y * XQ_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= sz) continue;
@@ -89,17 +90,61 @@ __device__ __forceinline__ uint32_t xq_pop_n(uint32_t* head, const uint32_t* qsi
 // queue y in the list): items come in list order per XCD, so the waves of one
 // XCD stay on neighbouring items (one block's data in that XCD's L2) however
 // uneven the items' costs.  next() is wave-uniform; ~0u when drained.
+//
+// The smaller a pop's chunk K, the closer an XCD's waves stay together in the
+// list; but a pop is a returning atomic, and a wave that waits for it where it
+// is issued stands still for its latency and (vmcnt waits are in issue order)
+// for every load it has in flight.  So the pop of the chunk after the current
+// one is issued ahead of need: prefetch(), called once per item where the
+// caller issues its other long-latency loads, adds K to the head of the queue
+// the wave is on once the current chunk is half used, and does not read what
+// comes back.  next() reads it when the current chunk runs out: a return below
+// the queue's size is a claimed range, and it is always worked (next() is
+// called until it says drained, and says so only with nothing claimed and
+// nothing in flight); a return at or past the size means that queue is
+// drained (the head only overshoots, as it does in xq_pop_n), and the wave
+// goes on to the other queues with xq_pop_n as before.  No wave waits for
+// another anywhere.
 template <uint32_t K>
 struct WaveQueue {
-    uint32_t a = 0, r = 0;
+    uint32_t a = 0, r = 0;     // the current chunk: next list index, items left
+    uint32_t t = 0;            // the wave pops from queue (x + t) & 7; 8: all are drained
+    uint32_t pj = 0;           // lane 0: what the prefetched pop returned (the queue's head before it)
+    bool pend = false;         // a prefetched pop is issued and not yet read (wave-uniform)
+
+    __device__ __forceinline__ void prefetch(uint32_t* head, uint32_t x)
+    {
+        if (pend || t >= 8u || r > K / 2) return;
+        if ((threadIdx.x & 63) == 0) pj = atomicAdd(head + ((x + t) & 7u) * XQ_STRIDE, K);
+        pend = true;
+    }
+
     __device__ __forceinline__ uint32_t next(uint32_t* head, const uint32_t* qsize, const uint32_t* seg, uint32_t x)
     {
         if (r == 0) {
-            uint32_t j = 0, cnt = 0;
-            if ((threadIdx.x & 63) == 0) j = xq_pop_n(head, qsize, x, K, cnt);
+            if (t >= 8u) return 0xFFFFFFFFu;
+            uint32_t j = 0xFFFFFFFFu, cnt = 0;
+            if ((threadIdx.x & 63) == 0) {
+                uint32_t t0 = t;
+                if (pend) {
+                    const uint32_t y = (x + t) & 7u, sz = qsize[y];
+                    if (pj < sz) {
+                        j = (y << 28) | pj;
+                        cnt = sz - pj < K ? sz - pj : K;
+                    } else {
+                        t0 = t + 1u;               // that queue is drained
+                    }
+                }
+                if (j == 0xFFFFFFFFu) j = xq_pop_n(head, qsize, x, K, cnt, t0);
+            }
+            pend = false;
             j = (uint32_t)__shfl((int)j, 0, 64);
             cnt = (uint32_t)__shfl((int)cnt, 0, 64);
-            if (j == 0xFFFFFFFFu) return 0xFFFFFFFFu;
+            if (j == 0xFFFFFFFFu) {
+                t = 8u;
+                return 0xFFFFFFFFu;
+            }
+            t = ((j >> 28) - x) & 7u;
             a = seg[j >> 28] + (j & 0x0FFFFFFFu);
             r = cnt;
         }
