@@ -1,6 +1,7 @@
 // starch_amd/csrc/bed_align.hip -- sam2bed, psl2bed and rmsk2bed on MI355X: SAM,
 // PSL and RepeatMasker .out text into BED lines (the definitions:
-// include/starch_amd.h).  The stages are those of bed_convert.hip:
+// include/starch_amd.h).  The stages are those of bed_convert.hip, over the same
+// skeleton (bed_records.hpp):
 //   1. framing: the sort's line-end pass (sb::SortWorkspace::stage_frame).
 //   2. PSL alone, k_al_psl_head: whether line 1 begins with psLayout, and the
 //      first line that begins with ----- (an atomicMin), so that the
@@ -12,9 +13,9 @@
 //      read up to the end of its CIGAR; a PSL line to its end (a 22nd field is an
 //      error); a RepeatMasker line to its 17th token.  The lowest bad line is an
 //      atomicMin of (line << 8) | kind.
-//   4. k_al_tally: class counts, and with keep_header the bytes of the header
-//      lines from the exclusive sum of (is header).  An exclusive sum of the
-//      bytes places every line; k_al_write<format>, one thread per input line,
+//   4. br::place (k_br_tally): class counts, and with keep_header the bytes of
+//      the header lines from the exclusive sum of (is header).  An exclusive sum of
+//      the bytes places every line; k_al_write<format>, one thread per input line,
 //      writes its output lines: several in the split modes, round after round
 //      across the wave, from the same walk over the CIGAR (sam_next_run) or over
 //      blockSizes and tStarts in step (list_next) that measured them.  A copied
@@ -22,30 +23,24 @@
 //      a kept header line) of sb::kWaveCopyBytes or more is left to the whole wave.
 // All arithmetic is unsigned 64-bit integer.  A thread reads only bytes of its
 // own line and writes only its own placed range.
-#include <algorithm>
-#include <string>
-
-#include "../../include/starch_amd.h"
 #include "bed_align.hpp"
-#include "bed_text.hpp"
 
 namespace al {
 namespace {
 
-using bt::dec_digits;
-using bt::is_blank;
-using bt::is_word;
+using br::S_BAD, br::S_MARK, br::S_FLAG, br::S_OWN, br::S_HDR, br::S_REC, br::S_LINES, br::S_BYTES, br::C_BAD, br::C_HEADER, br::C_TOOL;
+using br::K_LONG, br::K_ZERO, br::K_OVER, br::K_END, br::K_STOP, br::K_TOOL;
+using br::dec_digits, br::is_blank, br::is_word, br::line_beg, br::Writer, br::parse_coord, br::token_is, br::tokens;
+using br::drop_bad, br::store_line, br::header_line, br::reset_and_bind, br::first_of, br::First, br::throw_bad, br::place, br::Placed;
 using bt::kLimit;
-using bt::line_beg;
-using bt::Writer;
 
-// device scalars (u64); the first two start as all ones
-enum : int { S_BAD = 0, S_DASH, S_PSL, S_HDR, S_REC, S_DROPPED, S_LINES, S_BYTES, S_COUNT = 8 };
+// PSL: the first line that begins with -----, whether line 1 begins with psLayout; SAM: the unmapped records left out
+enum : int { S_DASH = S_MARK, S_PSL = S_FLAG, S_DROPPED = S_OWN };
 // C_SPLIT: a SAM record written run by run; C_UNMAPPED: written as _unmapped; C_DROPPED: unmapped and left out
-enum : uint8_t { C_BAD = 0, C_HEADER, C_REC, C_SPLIT, C_UNMAPPED, C_DROPPED };
+enum : uint8_t { C_REC = C_TOOL, C_SPLIT, C_UNMAPPED, C_DROPPED };
 enum : uint32_t {
-    K_LONG = 1, K_FEW6, K_FLAG, K_RNAME, K_EMPTY, K_DIGIT, K_RANGE, K_ZERO, K_CIGAR, K_OVER, K_NODASH, K_FEW21, K_MANY21, K_FIELD,
-    K_STRAND, K_STOP, K_LIST, K_BLOCK0, K_UNDER, K_TOKENS, K_RSTRAND, K_END
+    K_FEW6 = K_TOOL, K_FLAG, K_RNAME, K_CIGAR, K_NODASH, K_FEW21, K_MANY21, K_FIELD, K_STRAND, K_LIST, K_BLOCK0, K_UNDER, K_TOKENS,
+    K_RSTRAND
 };
 // slots of a line (Rec::fo).  SAM: the starts of fields 2 to 6 (FLAG, RNAME, POS,
 // MAPQ, CIGAR), then the value of FLAG.  PSL: the starts of fields 2 to 21.
@@ -56,24 +51,14 @@ constexpr uint32_t kMaxSlots = kSlotsPsl;
 
 constexpr uint32_t slots_of(int format) { return format == STARCH_ALIGN_SAM ? kSlotsSam : (format == STARCH_ALIGN_PSL ? kSlotsPsl : 0u); }
 
-struct Rec {
-    const uint8_t* in;
-    const uint64_t* line_end;
-    uint64_t L;
-    uint8_t* cls;
-    uint32_t* fo;          // slots x L
-    uint64_t *a, *b;       // output start and stop; a split PSL record: tSize in a
-    uint32_t* cnt;         // output lines
-    uint64_t* ob;          // their bytes
-    uint32_t* hflag;       // 1: a header line
-    unsigned long long* scal;
-    uint32_t split, split_deletions, all_reads, reduced, keep_header;
+struct Rec : br::Rec {     // a of a split PSL record: tSize
+    uint32_t split, split_deletions, all_reads, reduced;
 };
 
-__device__ __forceinline__ uint32_t parse_coord(const uint8_t* __restrict__ s, uint32_t b, uint32_t e, uint64_t* v)
-{
-    return bt::parse_coord<K_EMPTY, K_DIGIT, K_RANGE>(s, b, e, v);
-}
+struct Tally {             // what k_br_tally counts
+    static constexpr uint32_t kOwn = C_DROPPED;
+    static __device__ bool record(uint32_t c) { return c == C_REC || c == C_SPLIT || c == C_UNMAPPED || c == C_DROPPED; }
+};
 
 // ---- the walks that the measuring and the writing pass share ----------------------------
 // The next piece of the CIGAR at s[p, ...), which ends at a TAB or at n: its
@@ -157,34 +142,8 @@ __device__ __forceinline__ uint32_t psl_block(uint64_t size, uint64_t t, bool re
     return 0;
 }
 
-// The first 16 tokens of s[0, n), separated by runs of blanks: [ts[k], te[k]),
-// empty past the last one.  Returns their number, 17 for more.
-__device__ __forceinline__ uint32_t tokens16(const uint8_t* __restrict__ s, uint32_t n, uint32_t (&ts)[16], uint32_t (&te)[16])
-{
-    uint32_t p = 0, nt = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 16; ++k) {
-        while (p < n && is_blank(s[p])) ++p;
-        ts[k] = p;
-        while (p < n && !is_blank(s[p])) ++p;
-        te[k] = p;
-        if (te[k] > ts[k]) nt = k + 1;
-    }
-    while (p < n && is_blank(s[p])) ++p;
-    return p < n ? 17u : nt;
-}
-
-__device__ __forceinline__ bool token_is(const uint8_t* __restrict__ s, uint32_t b, uint32_t e, const char* w, uint32_t k)
-{
-    return e - b == k && is_word(s + b, w, k);
-}
-
 // ---- 3. classify and measure -----------------------------------------------------------
-struct Line {              // what k_al_classify leaves of a line
-    uint32_t cls = C_BAD, kind = 0, cnt = 0;
-    uint64_t ob = 0, a = 0, b = 0;
-    uint32_t fo[kMaxSlots] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-};
+using Line = br::Line<kMaxSlots>;   // what k_al_classify leaves of a line
 
 __device__ __forceinline__ void sam_line(const uint8_t* __restrict__ s, uint32_t n, const Rec& r, Line& ln)
 {
@@ -289,7 +248,7 @@ __device__ __forceinline__ void psl_line(const uint8_t* __restrict__ s, uint32_t
 __device__ __forceinline__ void rmsk_line(const uint8_t* __restrict__ s, uint32_t n, Line& ln)
 {
     uint32_t ts[16], te[16];
-    const uint32_t nt = tokens16(s, n, ts, te);
+    const uint32_t nt = tokens(s, n, ts, te);   // 17: more than 16
     if (nt == 0 || token_is(s, ts[0], te[0], "SW", 2) || token_is(s, ts[0], te[0], "score", 5)) { ln.cls = C_HEADER; return; }
     if (!(nt == 15 || (nt == 16 && token_is(s, ts[15], te[15], "*", 1)))) { ln.kind = K_TOKENS; return; }
     if (!(te[8] - ts[8] == 1 && (s[ts[8]] == '+' || s[ts[8]] == 'C'))) { ln.kind = K_RSTRAND; return; }
@@ -323,7 +282,6 @@ __global__ void __launch_bounds__(kThreads) k_al_psl_head(const Rec r)
 template <int kFormat>
 __global__ void __launch_bounds__(kThreads) k_al_classify(const Rec r)
 {
-    constexpr uint32_t kSlots = slots_of(kFormat);
     const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
     if (i >= r.L) return;
     const uint64_t b = line_beg(r.line_end, i), e = r.line_end[i] - 1;
@@ -344,46 +302,11 @@ __global__ void __launch_bounds__(kThreads) k_al_classify(const Rec r)
     } else {
         rmsk_line(s, (uint32_t)(e - b), ln);
     }
-    if (ln.kind) {
-        atomicMin(&r.scal[S_BAD], (unsigned long long)((i << 8) | ln.kind));
-        ln = Line{};
-    }
-    r.cls[i] = (uint8_t)ln.cls;
-    r.hflag[i] = ln.cls == C_HEADER ? 1u : 0u;
-    r.cnt[i] = ln.cnt;
-    r.ob[i] = ln.ob;
-    r.a[i] = ln.a;
-    r.b[i] = ln.b;
-#pragma unroll
-    for (uint32_t k = 0; k < kSlots; ++k) r.fo[(uint64_t)k * r.L + i] = ln.fo[k];
+    drop_bad(r, i, ln);   // (two calls on purpose: merged into one function the kernel is other code, bed_records.hpp)
+    store_line<slots_of(kFormat)>(r, i, ln);
 }
 
 // ---- 4. output ---------------------------------------------------------------------------
-// class counts and output lines; the bytes of a kept header line
-__global__ void __launch_bounds__(kThreads) k_al_tally(const Rec r, const uint64_t* __restrict__ hord)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    const bool valid = i < r.L;
-    const uint32_t cls = valid ? r.cls[i] : (uint32_t)C_BAD;
-    uint32_t cnt = valid ? r.cnt[i] : 0u;
-    if (cls == C_HEADER && r.keep_header) {
-        const uint64_t k = hord[i];
-        cnt = 1;
-        r.cnt[i] = 1;
-        // _header K K+1 line
-        r.ob[i] = 8 + dec_digits(k) + 1 + dec_digits(k + 1) + 1 + (r.line_end[i] - 1 - line_beg(r.line_end, i)) + 1;
-    }
-    const uint32_t hdr = __popcll(__ballot(cls == C_HEADER)), dropped = __popcll(__ballot(cls == C_DROPPED));
-    const uint32_t rec = __popcll(__ballot(cls == C_REC || cls == C_SPLIT || cls == C_UNMAPPED || cls == C_DROPPED));
-    const uint32_t lines = wave_reduce_add<uint32_t>(cnt);
-    if ((threadIdx.x & 63) == 0) {
-        if (hdr) atomicAdd(&r.scal[S_HDR], (unsigned long long)hdr);
-        if (dropped) atomicAdd(&r.scal[S_DROPPED], (unsigned long long)dropped);
-        if (rec) atomicAdd(&r.scal[S_REC], (unsigned long long)rec);
-        if (lines) atomicAdd(&r.scal[S_LINES], (unsigned long long)lines);
-    }
-}
-
 // A thread writes the output lines of its input line, one per round; a tail of
 // kWaveCopyBytes or more is left to the whole wave, line after line.
 template <int kFormat>
@@ -422,19 +345,13 @@ k_al_write(const Rec r, const uint64_t* __restrict__ hord, const uint64_t* __res
         reverse = psl_split && f[P_QNAME] - 1 - f[P_STRAND] == 2 && s[f[P_STRAND] + 1] == '-';
     }
     if constexpr (kFormat == STARCH_ALIGN_RMSK) {
-        if (cls == C_REC) nt = tokens16(s, n, ts, te);
+        if (cls == C_REC) nt = tokens(s, n, ts, te);
     }
     for (uint32_t round = 0; __ballot(round < nout) != 0; ++round) {
         w.big_len[0] = 0;
         if (round < nout) {
             if (cls == C_HEADER) {
-                const uint64_t k = hord[i];
-                w.bytes(reinterpret_cast<const uint8_t*>("_header\t"), 8);
-                w.dec(k);
-                w.tab();
-                w.dec(k + 1);
-                w.tab();
-                w.tail(s, n);
+                header_line(w, hord[i], s, n);
             } else if constexpr (kFormat == STARCH_ALIGN_SAM) {
                 if (cls == C_SPLIT) (void)sam_next_run(s, n, cw, r.split_deletions != 0, &start, &stop);
                 if (cls == C_UNMAPPED) w.bytes(reinterpret_cast<const uint8_t*>("_unmapped"), 9);
@@ -521,29 +438,21 @@ void launch(uint32_t format, const Rec& r, const uint64_t* hord, const uint64_t*
 const char* bad_text(uint32_t k)
 {
     switch (k) {
-        case K_LONG: return "line of 2^32 bytes or more";
         case K_FEW6: return "fewer than six tab-separated fields";
         case K_FLAG: return "FLAG is not a decimal number from 0 to 65535";
         case K_RNAME: return "mapped record without a reference name";
-        case K_EMPTY: return "empty coordinate";
-        case K_DIGIT: return "non-digit in a coordinate";
-        case K_RANGE: return "coordinate has 20 or more digits or is above 2^63-1";
-        case K_ZERO: return "start or position below 1";
         case K_CIGAR: return "CIGAR is not * or pieces of a count of 1 to 9 digits and one of MIDNSHP=X";
-        case K_OVER: return "coordinate would exceed 2^63-1";
         case K_NODASH: return "psLayout header without a line of dashes";
         case K_FEW21: return "fewer than 21 tab-separated fields";
         case K_MANY21: return "more than 21 tab-separated fields";
         case K_FIELD: return "empty field";
         case K_STRAND: return "strand is not +, - or two of them";
-        case K_STOP: return "stop not above start";
         case K_LIST: return "blockSizes and tStarts do not hold blockCount comma-terminated numbers";
         case K_BLOCK0: return "block of size 0";
         case K_UNDER: return "block start and size exceed tSize on the reverse strand";
         case K_TOKENS: return "a record has 15 tokens, or 16 with a last *";
         case K_RSTRAND: return "strand is not + or C";
-        case K_END: return "end below start";
-        default: return "malformed line";
+        default: return br::bad_text(k);
     }
 }
 
@@ -569,22 +478,9 @@ void AlignWorkspace::run(sb::SortWorkspace& sorter, const AlignOptions& opt, con
     timer.mark(1, st);
 
     // 2, 3. the PSL header's end; classify and measure
-    const uint32_t slots = opt.format == STARCH_ALIGN_SAM ? kSlotsSam : (opt.format == STARCH_ALIGN_PSL ? kSlotsPsl : 0u);
-    uint64_t* scal = b_scal.as<uint64_t>(S_COUNT);
-    HIP_CHECK(hipMemsetAsync(scal, 0xff, 2 * sizeof(uint64_t), st));
-    HIP_CHECK(hipMemsetAsync(scal + 2, 0, (S_COUNT - 2) * sizeof(uint64_t), st));
+    const char* command = command_of(opt.format);
     Rec r{};
-    r.in = d_in;
-    r.line_end = sorter.ln.line_end;
-    r.L = L;
-    r.cls = b_cls.as<uint8_t>(L);
-    r.fo = b_fo.as<uint32_t>(std::max<uint64_t>(1, (uint64_t)slots * L));
-    r.a = b_a.as<uint64_t>(L);
-    r.b = b_b.as<uint64_t>(L);
-    r.cnt = b_cnt.as<uint32_t>(L);
-    r.ob = b_ob.as<uint64_t>(L);
-    r.hflag = b_hflag.as<uint32_t>(L);
-    r.scal = reinterpret_cast<unsigned long long*>(scal);
+    reset_and_bind(rb, r, d_in, sorter.ln.line_end, L, slots_of((int)opt.format), st);
     r.split = opt.split;
     r.split_deletions = opt.split_deletions;
     r.all_reads = opt.all_reads;
@@ -595,39 +491,21 @@ void AlignWorkspace::run(sb::SortWorkspace& sorter, const AlignOptions& opt, con
         HIP_CHECK(hipGetLastError());
     }
     launch(opt.format, r, nullptr, nullptr, 0, nullptr, false, st);
-    uint64_t first = 0;   // the lowest bad line
-    HIP_CHECK(hipMemcpyAsync(&first, scal, sizeof first, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (first != ~0ull)
-        throw StarchError(STARCH_ERR_DATA, std::string(command_of(opt.format)) + ": line " + std::to_string((first >> 8) + 1) + ": " +
-                                               bad_text((uint32_t)(first & 255)));
+    const First first = first_of(rb, st);
+    if (first.bad != ~0ull) throw_bad(command, first.bad, bad_text);
 
     // 4. header ordinals, counts, places
-    uint64_t tot[S_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const uint64_t* hord = nullptr;
-    if (opt.keep_header) {
-        uint64_t* h = b_hord.as<uint64_t>(L);
-        scan::excl_sum_u32_to_u64(r.hflag, h, L, (uint64_t*)nullptr, b_tmp, st);
-        hord = h;
-    }
-    uint64_t* off = b_off.as<uint64_t>(L);
-    hipLaunchKernelGGL(k_al_tally, dim3(blocks_for(L, kThreads)), dim3(kThreads), 0, st, r, hord);
-    HIP_CHECK(hipGetLastError());
-    scan::excl_sum_u64(r.ob, off, L, scal + S_BYTES, b_tmp, st);
-    HIP_CHECK(hipMemcpyAsync(tot, scal, sizeof tot, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    res.header_lines = tot[S_HDR];
-    res.records = tot[S_REC];
-    res.unmapped_dropped = tot[S_DROPPED];
-    if (tot[S_LINES] >= (1ull << 32))
-        throw StarchError(STARCH_ERR_ARG, std::string(command_of(opt.format)) + ": 2^32 output lines or more");
+    const Placed p = place<Tally>(rb, r, L, command, st);
+    res.header_lines = p.tot[S_HDR];
+    res.records = p.tot[S_REC];
+    res.unmapped_dropped = p.tot[S_DROPPED];
     timer.mark(2, st);
-    const uint64_t bytes = tot[S_BYTES];
+    const uint64_t bytes = p.tot[S_BYTES];
     if (bytes) {
         uint8_t* o = out.as<uint8_t>(bytes + 64);
-        launch(opt.format, r, hord, off, bytes, o, true, st);
+        launch(opt.format, r, p.hord, p.off, bytes, o, true, st);
     }
-    res.lines_out = tot[S_LINES];
+    res.lines_out = p.tot[S_LINES];
     res.out_bytes = bytes;
     finish(3);
 }

@@ -1,12 +1,11 @@
 // starch_amd/csrc/bed_align.hpp -- host interface of sam2bed, psl2bed and rmsk2bed
 // (bed_align.hip): SAM, PSL and RepeatMasker .out text into BED lines, unsorted.
 #pragma once
-#include "common.hpp"
-#include "sort_bed.hpp"
+#include "bed_records.hpp"
 
 namespace al {
 
-constexpr int kThreads = 256;           // threads per block of the per-line kernels (one line each)
+constexpr int kThreads = br::kThreads;  // threads per block of the per-line kernels (one line each)
 constexpr uint32_t kSlotsSam = 6;       // 32-bit values kept per SAM line: the starts of fields 2 to 6, FLAG
 constexpr uint32_t kSlotsPsl = 20;      // per PSL line: the starts of fields 2 to 21 (a RepeatMasker line keeps none)
 
@@ -24,7 +23,7 @@ struct AlignResult {
 const char* command_of(uint32_t format);
 
 struct AlignWorkspace {
-    DevBuf b_scal, b_tmp, b_cls, b_fo, b_a, b_b, b_cnt, b_ob, b_off, b_hflag, b_hord;
+    br::Buffers rb;
     StageTimer<4> timer;
     // The text d_in[0, n) in the format of opt, converted line by line as
     // include/starch_amd.h defines, into out (res.out_bytes of it, in input

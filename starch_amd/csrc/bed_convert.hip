@@ -19,30 +19,32 @@
 //      k; an inclusive running maximum of (line + 1 if it is a declaration)
 //      gives every data line its declaration.  k_cv_wig_resolve then computes
 //      the coordinates and bytes of the data lines.
-//   4. k_cv_tally: class counts, and with keep_header the bytes of the header
-//      lines from the exclusive sum of (is header).  An exclusive sum of the
-//      bytes places every line; k_cv_write<format>, one thread per input line,
-//      writes its output lines (several in the VCF split modes, round after
-//      round across the wave).  A copied tail (attributes, INFO and sample
+//   4. br::place (k_br_tally): class counts, and with keep_header the bytes of
+//      the header lines from the exclusive sum of (is header).  An exclusive sum
+//      of the bytes places every line; k_cv_write<format>, one thread per input
+//      line, writes its output lines (several in the VCF split modes, round
+//      after round across the wave).  A copied tail (attributes, INFO and sample
 //      columns, a kept header line) of sb::kWaveCopyBytes or more is left to
 //      the whole wave, as in k_bm_write.
-// All arithmetic is unsigned 64-bit integer.
+// The skeleton (arrays, scalars, the end of classify, tally, the host steps) is
+// bed_records.hpp's.  All arithmetic is unsigned 64-bit integer.
 #include <algorithm>
-#include <string>
 
-#include "../../include/starch_amd.h"
 #include "bed_convert.hpp"
-#include "bed_text.hpp"
 
 namespace cv {
 namespace {
 
+using br::S_BAD, br::S_MARK, br::S_OWN, br::S_HDR, br::S_REC, br::S_LINES, br::S_BYTES, br::C_BAD, br::C_HEADER, br::C_TOOL;
+using br::K_LONG, br::K_ZERO, br::K_OVER, br::K_END, br::K_STOP, br::K_TOOL;
+using br::dec_digits, br::is_blank, br::is_word, br::line_beg, br::Writer, br::parse_coord, br::token_is, br::tokens;
+using br::drop_bad, br::store_line, br::header_line, br::reset_and_bind, br::first_of, br::First, br::throw_bad, br::place, br::Placed;
 using bt::kLimit;
-enum : int { S_BAD = 0, S_FASTA, S_HDR, S_REC, S_DECL, S_LINES, S_BYTES, S_COUNT = 8 };   // device scalars (u64); the first two start as all ones
-enum : uint8_t { C_BAD = 0, C_HEADER, C_REC, C_DECL, C_DATA1, C_DATA2, C_DATA4 };
+enum : int { S_FASTA = S_MARK, S_DECL = S_OWN };   // the first ##FASTA line of GFF; the WIG declarations
+enum : uint8_t { C_REC = C_TOOL, C_DECL, C_DATA1, C_DATA2, C_DATA4 };
 enum : uint32_t {
-    K_LONG = 1, K_FEW, K_MANY, K_NONAME, K_EMPTY, K_DIGIT, K_RANGE, K_ZERO, K_END, K_STOP, K_REF, K_ALT, K_ALLELE, K_OVER,
-    K_TOKENS, K_NODECL, K_MISFIT, K_KEY, K_TWICE, K_NOCHROM, K_NOSTART, K_VALUE
+    K_FEW = K_TOOL, K_MANY, K_NONAME, K_REF, K_ALT, K_ALLELE, K_TOKENS, K_NODECL, K_MISFIT, K_KEY, K_TWICE, K_NOCHROM, K_NOSTART,
+    K_VALUE
 };
 // slots of a line (Rec::fo).  GFF, GTF: the starts of fields 1 to 8, then the
 // ID's offset and length (0: none).  VCF: the starts of fields 1 to 7.  A WIG
@@ -51,40 +53,21 @@ enum : uint32_t {
 enum : uint32_t { O_ID = 8, O_IDLEN = 9, O_CHR = 0, O_CHREND = 1, O_SCORE = 2, O_SCOREEND = 3, O_DECL = 4, O_MODE = 2 };
 enum : uint32_t { M_VARIABLE = 1, M_FIXED = 2 };
 
-struct Rec {
-    const uint8_t* in;
-    const uint64_t* line_end;
-    uint64_t L;
-    uint8_t* cls;
-    uint32_t* fo;          // kSlots x L
-    uint64_t *a, *b;       // output start and stop; a declaration's start and step
+struct Rec : br::Rec {     // a and b of a declaration: its start and step
     uint64_t* aux;         // WIG: a declaration's span
-    uint32_t* cnt;         // output lines
-    uint64_t* ob;          // their bytes
-    uint32_t* hflag;       // 1: a header line
     uint64_t* pk;          // WIG: (is data line) | (is 1-token line) << 32, then its exclusive sum
     uint64_t* dmax;        // WIG: line + 1 of a declaration, then its running maximum
-    unsigned long long* scal;
-    uint32_t vcf_class, keep_header;
+    uint32_t vcf_class;
 };
 
-using bt::dec_digits;
-using bt::is_blank;
-using bt::is_word;
-using bt::line_beg;
-using bt::Writer;
-
-// decimal field s[b, e): 0, or K_EMPTY, K_DIGIT, K_RANGE (20 digits or more, or above 2^63-1)
-__device__ __forceinline__ uint32_t parse_coord(const uint8_t* __restrict__ s, uint32_t b, uint32_t e, uint64_t* v)
-{
-    return bt::parse_coord<K_EMPTY, K_DIGIT, K_RANGE>(s, b, e, v);
-}
+struct Tally {             // what k_br_tally counts
+    static constexpr uint32_t kOwn = C_DECL;
+    static __device__ bool record(uint32_t c) { return c == C_REC || c == C_DATA1 || c == C_DATA2 || c == C_DATA4; }
+};
 
 // ---- 2. classify and measure ---------------------------------------------------------
-struct Line {              // what k_cv_classify leaves of a line
-    uint32_t cls = C_BAD, kind = 0, cnt = 0;
-    uint64_t ob = 0, a = 0, b = 0, pk = 0;
-    uint32_t fo[kSlots] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+struct Line : br::Line<kSlots> {   // what k_cv_classify leaves of a line
+    uint64_t pk = 0;
 };
 
 // a GFF (gtf == false) or GTF record s[0, n)
@@ -189,29 +172,10 @@ __device__ __forceinline__ void vcf_line(const uint8_t* __restrict__ s, uint32_t
     ln.ob = cnt * fixed + alleles;
 }
 
-// the tokens of s[0, n), at most four kept: ts, te; returns their number, 5 for more
-__device__ __forceinline__ uint32_t tokens(const uint8_t* __restrict__ s, uint32_t n, uint32_t* ts, uint32_t* te)
-{
-    uint32_t nt = 0, p = 0;
-    for (;;) {
-        while (p < n && is_blank(s[p])) ++p;
-        if (p == n) return nt;
-        if (nt == 4) return 5;
-        ts[nt] = p;
-        while (p < n && !is_blank(s[p])) ++p;
-        te[nt++] = p;
-    }
-}
-
-__device__ __forceinline__ bool token_is(const uint8_t* __restrict__ s, uint32_t b, uint32_t e, const char* w, uint32_t k)
-{
-    return e - b == k && is_word(s + b, w, k);
-}
-
 __device__ __forceinline__ void wig_line(const uint8_t* __restrict__ s, uint32_t n, Line& ln)
 {
-    uint32_t ts[4] = {0, 0, 0, 0}, te[4] = {0, 0, 0, 0};
-    const uint32_t nt = tokens(s, n, ts, te);
+    uint32_t ts[4], te[4];
+    const uint32_t nt = tokens(s, n, ts, te);   // 5: more than four
     if (nt && (token_is(s, ts[0], te[0], "track", 5) || token_is(s, ts[0], te[0], "browser", 7))) { ln.cls = C_HEADER; return; }
     if (nt && (token_is(s, ts[0], te[0], "variableStep", 12) || token_is(s, ts[0], te[0], "fixedStep", 9))) { ln.cls = C_DECL; return; }
     if (nt != 1 && nt != 2 && nt != 4) { ln.kind = K_TOKENS; return; }
@@ -251,18 +215,8 @@ __global__ void __launch_bounds__(kThreads) k_cv_classify(const Rec r)
     else if (kFormat == STARCH_CONVERT_WIG) wig_line(s, (uint32_t)(e - b), ln);
     else if (kFormat == STARCH_CONVERT_VCF) vcf_line(s, (uint32_t)(e - b), r.vcf_class, ln);
     else annotation_line<kFormat == STARCH_CONVERT_GTF>(s, (uint32_t)(e - b), ln);
-    if (ln.kind) {
-        atomicMin(&r.scal[S_BAD], (unsigned long long)((i << 8) | ln.kind));
-        ln = Line{};
-    }
-    r.cls[i] = (uint8_t)ln.cls;
-    r.hflag[i] = ln.cls == C_HEADER ? 1u : 0u;
-    r.cnt[i] = ln.cnt;
-    r.ob[i] = ln.ob;
-    r.a[i] = ln.a;
-    r.b[i] = ln.b;
-#pragma unroll
-    for (uint32_t k = 0; k < kSlots; ++k) r.fo[(uint64_t)k * r.L + i] = ln.fo[k];
+    drop_bad(r, i, ln);   // (two calls on purpose: merged into one function the kernel is other code, bed_records.hpp)
+    store_line<kSlots>(r, i, ln);
     if (kFormat == STARCH_CONVERT_WIG) {
         r.pk[i] = ln.pk;
         r.dmax[i] = ln.cls == C_DECL ? i + 1 : 0;
@@ -368,31 +322,6 @@ __global__ void __launch_bounds__(kThreads) k_cv_wig_resolve(const Rec r)
 }
 
 // ---- 4. output ---------------------------------------------------------------------------
-// class counts and output lines of the lines [0, Le); the bytes of a kept header line
-__global__ void __launch_bounds__(kThreads) k_cv_tally(const Rec r, uint64_t Le, const uint64_t* __restrict__ hord)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-    const bool valid = i < Le;
-    const uint32_t cls = valid ? r.cls[i] : (uint32_t)C_BAD;
-    uint32_t cnt = valid ? r.cnt[i] : 0u;
-    if (cls == C_HEADER && r.keep_header) {
-        const uint64_t k = hord[i];
-        cnt = 1;
-        r.cnt[i] = 1;
-        // _header K K+1 line
-        r.ob[i] = 8 + dec_digits(k) + 1 + dec_digits(k + 1) + 1 + (r.line_end[i] - 1 - line_beg(r.line_end, i)) + 1;
-    }
-    const uint32_t hdr = __popcll(__ballot(cls == C_HEADER)), dec = __popcll(__ballot(cls == C_DECL));
-    const uint32_t rec = __popcll(__ballot(cls == C_REC || cls == C_DATA1 || cls == C_DATA2 || cls == C_DATA4));
-    const uint32_t lines = wave_reduce_add<uint32_t>(cnt);
-    if ((threadIdx.x & 63) == 0) {
-        if (hdr) atomicAdd(&r.scal[S_HDR], (unsigned long long)hdr);
-        if (dec) atomicAdd(&r.scal[S_DECL], (unsigned long long)dec);
-        if (rec) atomicAdd(&r.scal[S_REC], (unsigned long long)rec);
-        if (lines) atomicAdd(&r.scal[S_LINES], (unsigned long long)lines);
-    }
-}
-
 // A thread writes the output lines of its input line, one per round; a tail of
 // kWaveCopyBytes or more is left to the whole wave, line after line.
 template <int kFormat>
@@ -419,13 +348,7 @@ k_cv_write(const Rec r, uint64_t Le, const uint64_t* __restrict__ hord, const ui
         w.big_len[0] = 0;
         if (round < nout) {
             if (cls == C_HEADER) {
-                const uint64_t k = hord[i];
-                w.bytes(reinterpret_cast<const uint8_t*>("_header\t"), 8);
-                w.dec(k);
-                w.tab();
-                w.dec(k + 1);
-                w.tab();
-                w.tail(s, n);
+                header_line(w, hord[i], s, n);
             } else if (kFormat == STARCH_CONVERT_WIG) {
                 const uint64_t from = cls == C_DATA4 ? i : (uint64_t)f[O_DECL + 1];   // the line that names the chromosome
                 const uint8_t* c = r.in + line_beg(r.line_end, from);
@@ -508,20 +431,12 @@ void launch(uint32_t format, const Rec& r, uint64_t Le, const uint64_t* hord, co
 const char* bad_text(uint32_t k)
 {
     switch (k) {
-        case K_LONG: return "line of 2^32 bytes or more";
         case K_FEW: return "fewer tab-separated fields than the format needs";
         case K_MANY: return "more than nine tab-separated fields";
         case K_NONAME: return "empty sequence name";
-        case K_EMPTY: return "empty coordinate";
-        case K_DIGIT: return "non-digit in a coordinate";
-        case K_RANGE: return "coordinate has 20 or more digits or is above 2^63-1";
-        case K_ZERO: return "start or position below 1";
-        case K_END: return "end below start";
-        case K_STOP: return "stop not above start";
         case K_REF: return "empty REF";
         case K_ALT: return "empty ALT";
         case K_ALLELE: return "empty ALT allele";
-        case K_OVER: return "coordinate would exceed 2^63-1";
         case K_TOKENS: return "a data line has 1, 2 or 4 tokens";
         case K_NODECL: return "data line before any declaration";
         case K_MISFIT: return "data line does not fit the declaration in force";
@@ -530,7 +445,7 @@ const char* bad_text(uint32_t k)
         case K_NOCHROM: return "declaration without chrom";
         case K_NOSTART: return "fixedStep declaration without start";
         case K_VALUE: return "declaration value is not a number from 1 to 2^63-1";
-        default: return "malformed line";
+        default: return br::bad_text(k);
     }
 }
 
@@ -552,26 +467,13 @@ void ConvertWorkspace::run(sb::SortWorkspace& sorter, const ConvertOptions& opt,
 
     // 2. classify and measure
     const bool wig = opt.format == STARCH_CONVERT_WIG;
-    uint64_t* scal = b_scal.as<uint64_t>(S_COUNT);
-    HIP_CHECK(hipMemsetAsync(scal, 0xff, 2 * sizeof(uint64_t), st));
-    HIP_CHECK(hipMemsetAsync(scal + 2, 0, (S_COUNT - 2) * sizeof(uint64_t), st));
     Rec r{};
-    r.in = d_in;
-    r.line_end = sorter.ln.line_end;
-    r.L = L;
-    r.cls = b_cls.as<uint8_t>(L);
-    r.fo = b_fo.as<uint32_t>((uint64_t)kSlots * L);
-    r.a = b_a.as<uint64_t>(L);
-    r.b = b_b.as<uint64_t>(L);
-    r.cnt = b_cnt.as<uint32_t>(L);
-    r.ob = b_ob.as<uint64_t>(L);
-    r.hflag = b_hflag.as<uint32_t>(L);
+    reset_and_bind(rb, r, d_in, sorter.ln.line_end, L, kSlots, st);
     if (wig) {
         r.aux = b_aux.as<uint64_t>(L);
         r.pk = b_pk.as<uint64_t>(L);
         r.dmax = b_dmax.as<uint64_t>(L);
     }
-    r.scal = reinterpret_cast<unsigned long long*>(scal);
     r.vcf_class = opt.vcf_class;
     r.keep_header = opt.keep_header;
     const unsigned lblocks = blocks_for(L, kThreads);
@@ -580,47 +482,27 @@ void ConvertWorkspace::run(sb::SortWorkspace& sorter, const ConvertOptions& opt,
     // 3. WIG state
     if (wig) {
         hipLaunchKernelGGL(k_cv_wig_decl, dim3(lblocks), dim3(kThreads), 0, st, r);
-        scan::excl_sum_u64(r.pk, r.pk, L, (uint64_t*)nullptr, b_tmp, st);
-        scan::incl_max_u64(r.dmax, L, b_tmp, st);
+        scan::excl_sum_u64(r.pk, r.pk, L, (uint64_t*)nullptr, rb.tmp, st);
+        scan::incl_max_u64(r.dmax, L, rb.tmp, st);
         hipLaunchKernelGGL(k_cv_wig_resolve, dim3(lblocks), dim3(kThreads), 0, st, r);
         HIP_CHECK(hipGetLastError());
     }
-    uint64_t first[2] = {0, 0};   // the lowest bad line, the first ##FASTA line
-    HIP_CHECK(hipMemcpyAsync(first, scal, sizeof first, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const uint64_t Le = std::min(L, first[1]);   // the lines before ##FASTA
-    if (first[0] != ~0ull && (first[0] >> 8) < Le)
-        throw StarchError(STARCH_ERR_DATA, "convert2bed: line " + std::to_string((first[0] >> 8) + 1) + ": " +
-                                               bad_text((uint32_t)(first[0] & 255)));
+    const First first = first_of(rb, st);
+    const uint64_t Le = std::min(L, first.mark);   // the lines before ##FASTA
+    if (first.bad != ~0ull && (first.bad >> 8) < Le) throw_bad("convert2bed", first.bad, bad_text);
 
     // 4. header ordinals, counts, places
-    uint64_t tot[S_COUNT] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const uint64_t* hord = nullptr;
-    uint64_t* off = nullptr;
-    if (Le) {
-        if (opt.keep_header) {
-            uint64_t* h = b_hord.as<uint64_t>(Le);
-            scan::excl_sum_u32_to_u64(r.hflag, h, Le, (uint64_t*)nullptr, b_tmp, st);
-            hord = h;
-        }
-        off = b_off.as<uint64_t>(Le);
-        hipLaunchKernelGGL(k_cv_tally, dim3(blocks_for(Le, kThreads)), dim3(kThreads), 0, st, r, Le, hord);
-        HIP_CHECK(hipGetLastError());
-        scan::excl_sum_u64(r.ob, off, Le, scal + S_BYTES, b_tmp, st);
-        HIP_CHECK(hipMemcpyAsync(tot, scal, sizeof tot, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
-    res.header_lines = tot[S_HDR];
-    res.data_lines = tot[S_REC];
-    res.declarations = tot[S_DECL];
-    if (tot[S_LINES] >= (1ull << 32)) throw StarchError(STARCH_ERR_ARG, "convert2bed: 2^32 output lines or more");
+    const Placed p = place<Tally>(rb, r, Le, "convert2bed", st);
+    res.header_lines = p.tot[S_HDR];
+    res.data_lines = p.tot[S_REC];
+    res.declarations = p.tot[S_DECL];
     timer.mark(2, st);
-    const uint64_t bytes = tot[S_BYTES];
+    const uint64_t bytes = p.tot[S_BYTES];
     if (bytes) {
         uint8_t* o = out.as<uint8_t>(bytes + 64);
-        launch(opt.format, r, Le, hord, off, bytes, o, true, st);
+        launch(opt.format, r, Le, p.hord, p.off, bytes, o, true, st);
     }
-    res.lines_out = tot[S_LINES];
+    res.lines_out = p.tot[S_LINES];
     res.out_bytes = bytes;
     finish(3);
 }

@@ -1,15 +1,14 @@
 // starch_amd/csrc/bed_convert.hpp -- host interface of convert2bed
 // (bed_convert.hip): GFF3, GTF, VCF and WIG text into BED lines, unsorted.
 #pragma once
-#include "common.hpp"
-#include "sort_bed.hpp"
+#include "bed_records.hpp"
 
 namespace cv {
 
-constexpr int kThreads = 256;           // threads per block of the per-line kernels (one line each)
+constexpr int kThreads = br::kThreads;  // threads per block of the per-line kernels (one line each)
 constexpr uint32_t kSlots = 10;         // 32-bit offsets kept per line (field starts, the ID, a declaration's record)
 
-struct ConvertOptions {                 // checked by the caller (api_convert.hip)
+struct ConvertOptions {                 // checked by the caller (api_bed.hip)
     uint32_t format = 0;                // STARCH_CONVERT_*
     uint32_t vcf_class = 0;             // STARCH_VCF_*
     uint32_t keep_header = 0;
@@ -21,7 +20,8 @@ struct ConvertResult {
 };
 
 struct ConvertWorkspace {
-    DevBuf b_scal, b_tmp, b_cls, b_fo, b_a, b_b, b_aux, b_cnt, b_ob, b_off, b_hflag, b_hord, b_pk, b_dmax;
+    br::Buffers rb;
+    DevBuf b_aux, b_pk, b_dmax;         // WIG
     StageTimer<4> timer;
     // The text d_in[0, n) in the format of opt, converted line by line as
     // include/starch_amd.h defines, into out (res.out_bytes of it, in input

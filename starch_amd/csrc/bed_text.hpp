@@ -1,7 +1,8 @@
 // starch_amd/csrc/bed_text.hpp -- device helpers of every BED command that writes
-// text (bed_map, bed_mapel, bed_mapscore, bed_closest, bed_setops, bed_convert,
-// bed_align; sort_bed.hip takes line_beg): line bounds, decimal numbers in and
-// out, and the output cursor of a thread with the copies it leaves to its wave.
+// text (bed_map, bed_mapel, bed_mapscore, bed_closest, bed_setops, and through
+// bed_records.hpp bed_convert and bed_align; sort_bed.hip takes line_beg): line
+// bounds, decimal numbers in and out, and the output cursor of a thread with the
+// copies it leaves to its wave.
 #pragma once
 #include "common.hpp"
 #include "sort_bed.hpp"

@@ -142,6 +142,21 @@ def test_line_counts_and_bad_lines_around_the_block_size(ctx, TW, fmt):
     check_error(ctx, fmt, b"\n".join(bad), 2 * T - 2, BAD[fmt][1])
 
 
+@pytest.mark.parametrize("fmt", ("sam", "rmsk"))
+def test_kept_headers_at_the_block_edges(ctx, TW, fmt):
+    """Header ordinals and the tally's per-wave counts across a block boundary, beside records of two lines."""
+    T, _ = TW
+    rows = rows_of(fmt, 2 * T + 1)
+    for at in (0, T - 1, T, 2 * T):
+        rows[at] = b"@CO\tline %d" % at if fmt == "sam" else b""
+    data = b"\n".join(rows) + b"\n"
+    modes = [dict(keep_header=True), dict(keep_header=False)] + ([dict(split=True, keep_header=True)] if fmt == "sam" else [])
+    for kw in modes:
+        got = check(ctx, fmt, data, **kw)
+        assert ctx.align_stats()["header_lines"] == 4
+        assert (b"_header\t3\t4\t" in got) == kw["keep_header"]
+
+
 # ---- long tails -------------------------------------------------------------------------
 def test_tails_around_the_wave_copy_threshold(ctx, TW):
     T, W = TW

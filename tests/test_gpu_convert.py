@@ -115,6 +115,20 @@ def test_line_counts_around_the_block_size(ctx, TW):
         assert wig.count(b"\n") == n and check(ctx, "wig", wig).count(b"\n") == n - 1
 
 
+@pytest.mark.parametrize("fmt", ("gff", "vcf"))
+def test_kept_headers_at_the_block_edges(ctx, TW, fmt):
+    """Header ordinals and the tally's per-wave counts across a block boundary."""
+    T, _ = TW
+    rows = gff_rows(2 * T + 1) if fmt == "gff" else vcf_rows(2 * T + 1)
+    for at in (0, T - 1, T, 2 * T):
+        rows[at] = b"#comment %d" % at
+    data = b"\n".join(rows) + b"\n"
+    for keep in (True, False):
+        got = check(ctx, fmt, data, keep_header=keep)
+        assert ctx.convert_stats()["header_lines"] == 4
+        assert (b"_header\t3\t4\t" in got) == keep
+
+
 # ---- long tails -------------------------------------------------------------------------
 def test_tails_around_the_wave_copy_threshold(ctx, TW):
     T, W = TW
