@@ -660,9 +660,7 @@ class Starch:
         return out
 
     def stats(self):
-        s = Stats()
-        _check(self._L.starch_get_stats(self._h, ctypes.byref(s)), self._h)
-        return {k: getattr(s, k) for k, _ in Stats._fields_}
+        return self._stats(Stats, self._L.starch_get_stats)
 
     def transform(self, bed: bytes):
         """Transform stage only -> (text, [(chr, line_count, segment text)])."""
@@ -703,12 +701,21 @@ class Starch:
 
 
     # ---- decompression / unstarch ----
+    def _output_size(self) -> int:
+        k = ctypes.c_uint64()
+        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
+        return k.value
+
     def _output(self) -> bytes:
-        n = ctypes.c_uint64()
-        _check(self._L.starch_output_size(self._h, ctypes.byref(n)), self._h)
-        buf = ctypes.create_string_buffer(max(1, n.value))
-        _check(self._L.starch_output_copy(self._h, buf, n.value), self._h)
-        return buf.raw[:n.value]
+        n = self._output_size()
+        buf = ctypes.create_string_buffer(max(1, n))
+        _check(self._L.starch_output_copy(self._h, buf, n), self._h)
+        return buf.raw[:n]
+
+    def _stats(self, S, fn) -> dict:
+        s = S()
+        _check(fn(self._h, ctypes.byref(s)), self._h)
+        return _as_dict(s)
 
     def bz2_decompress(self, data: bytes) -> bytes:
         """Concatenated bzip2 streams -> their bytes (GPU decode, CRCs checked)."""
@@ -718,9 +725,7 @@ class Starch:
     def bz2_decompress_device(self, d_ptr: int, n: int) -> int:
         """Device-resident streams; returns the output size (output_device_ptr())."""
         _check(self._L.starch_bz2_decompress_device(self._h, ctypes.c_void_p(d_ptr), n), self._h)
-        k = ctypes.c_uint64()
-        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
-        return k.value
+        return self._output_size()
 
     def output_device_ptr(self) -> int:
         p = ctypes.c_void_p()
@@ -732,7 +737,7 @@ class Starch:
         _check(self._L.starch_bz2_stream_count(self._h, ctypes.byref(n)), self._h)
         arr = (DecStream * max(1, n.value))()
         _check(self._L.starch_bz2_streams(self._h, arr, n.value), self._h)
-        return [{f: getattr(arr[i], f) for f, _ in DecStream._fields_} for i in range(n.value)]
+        return [_as_dict(arr[i]) for i in range(n.value)]
 
     def untransform(self, text: bytes, chromosome: bytes) -> bytes:
         """One segment's transformed text -> its BED lines (inverse of hpp:428-504)."""
@@ -766,9 +771,7 @@ class Starch:
     def extract_stats(self) -> dict:
         """Of the last extract(): streams_total / streams_decoded /
         compressed_bytes_decoded / lines_scanned / lines_out."""
-        s = ExtractStats()
-        _check(self._L.starch_extract_get_stats(self._h, ctypes.byref(s)), self._h)
-        return {k: getattr(s, k) for k, _ in ExtractStats._fields_}
+        return self._stats(ExtractStats, self._L.starch_extract_get_stats)
 
     # ---- sort-bed ----
     def sort_bed(self, bed: bytes) -> bytes:
@@ -781,9 +784,7 @@ class Starch:
     def sort_bed_device(self, d_ptr: int, n: int) -> int:
         """The same for BED bytes in HBM; returns the output size (output_device_ptr())."""
         _check(self._L.starch_sort_device(self._h, ctypes.c_void_p(d_ptr), n), self._h)
-        k = ctypes.c_uint64()
-        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
-        return k.value
+        return self._output_size()
 
     def sort_check(self, bed: bytes) -> int:
         """0 if bed is sorted, else the number (from 1) of the first line that
@@ -795,9 +796,7 @@ class Starch:
     def sort_stats(self) -> dict:
         """Of the last sort call: input_bytes / n_lines / n_chromosomes /
         already_sorted / first_unsorted_line / radix_passes / ms_*."""
-        s = SortStats()
-        _check(self._L.starch_sort_get_stats(self._h, ctypes.byref(s)), self._h)
-        return {k: getattr(s, k) for k, _ in SortStats._fields_}
+        return self._stats(SortStats, self._L.starch_sort_get_stats)
 
     def compress_sorted(self, bed: bytes, emit_index=True) -> bytes:
         """sort_bed, then compress from the sorted bytes while they are in HBM:
@@ -815,23 +814,16 @@ class Starch:
         malformed or unsorted line is StarchError -12 naming input and line."""
         if op not in SETOPS:
             raise ValueError("setop: op must be one of %s" % ", ".join(SETOPS))
-        inputs = [bytes(b) for b in inputs]
-        arr = (SetopInput * max(1, len(inputs)))()
-        for k, b in enumerate(inputs):
-            arr[k].data = b
-            arr[k].len = len(b)
-        _check(self._L.starch_setop_host(self._h, SETOPS[op], arr, len(inputs)), self._h)
+        arr, n = _inputs(inputs)
+        _check(self._L.starch_setop_host(self._h, SETOPS[op], arr, n), self._h)
         return self._output()
 
     def setop_device(self, op: str, d_ptr: int, offs) -> int:
         """The same for BED text in HBM, input k at d_ptr + [offs[k], offs[k+1]);
         returns the output size (output_device_ptr())."""
-        offs = [int(o) for o in offs]
-        a = (ctypes.c_uint64 * len(offs))(*offs)
-        _check(self._L.starch_setop_device(self._h, SETOPS[op], ctypes.c_void_p(d_ptr), a, len(offs) - 1), self._h)
-        k = ctypes.c_uint64()
-        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
-        return k.value
+        a, k = _offs(offs)
+        _check(self._L.starch_setop_device(self._h, SETOPS[op], ctypes.c_void_p(d_ptr), a, k), self._h)
+        return self._output_size()
 
     def merge(self, *inputs) -> bytes: return self.setop("merge", inputs)
     def intersect(self, *inputs) -> bytes: return self.setop("intersect", inputs)
@@ -852,24 +844,17 @@ class Starch:
         "everything" gives every line of every input in sort-bed's order.
         The definitions are in include/starch_amd.h."""
         o = _bedops_options(op, threshold, chop, stagger, exclude_short)
-        inputs = [bytes(b) for b in inputs]
-        arr = (SetopInput * max(1, len(inputs)))()
-        for k, b in enumerate(inputs):
-            arr[k].data = b
-            arr[k].len = len(b)
-        _check(self._L.starch_bedops_host(self._h, ctypes.byref(o), arr, len(inputs)), self._h)
+        arr, n = _inputs(inputs)
+        _check(self._L.starch_bedops_host(self._h, ctypes.byref(o), arr, n), self._h)
         return self._output()
 
     def bedops_device(self, op: str, d_ptr: int, offs, threshold="100%", chop=1, stagger=None, exclude_short=False) -> int:
         """The same for BED text in HBM, input k at d_ptr + [offs[k], offs[k+1]);
         returns the output size (output_device_ptr())."""
         o = _bedops_options(op, threshold, chop, stagger, exclude_short)
-        offs = [int(x) for x in offs]
-        a = (ctypes.c_uint64 * len(offs))(*offs)
-        _check(self._L.starch_bedops_device(self._h, ctypes.byref(o), ctypes.c_void_p(d_ptr), a, len(offs) - 1), self._h)
-        k = ctypes.c_uint64()
-        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
-        return k.value
+        a, k = _offs(offs)
+        _check(self._L.starch_bedops_device(self._h, ctypes.byref(o), ctypes.c_void_p(d_ptr), a, k), self._h)
+        return self._output_size()
 
     def element_of(self, ref, *others, threshold="100%") -> bytes:
         return self.bedops("element_of", (ref,) + others, threshold=threshold)
@@ -888,9 +873,7 @@ class Starch:
         """Of the last setop() or bedops(): n_inputs / input_bytes / n_lines / n_chromosomes /
         runs_merged / groups / lines_out / output_bytes / archives_decoded /
         radix_passes / ms_*."""
-        s = SetopStats()
-        _check(self._L.starch_setop_get_stats(self._h, ctypes.byref(s)), self._h)
-        return {k: getattr(s, k) for k, _ in SetopStats._fields_}
+        return self._stats(SetopStats, self._L.starch_setop_get_stats)
 
     # ---- bedmap ----
     def bedmap(self, ref, map=None, cols=("echo", "count"), range=0, skip_unmapped=False, delim=b"|") -> bytes:
@@ -903,9 +886,7 @@ class Starch:
         include/starch_amd.h.  A malformed or unsorted line is StarchError -12
         naming input (ref 0, map 1) and line; a bad argument is -2."""
         o = _map_options(cols, range, skip_unmapped, delim)
-        r = SetopInput(bytes(ref), len(ref))
-        m = None if map is None else ctypes.byref(SetopInput(bytes(map), len(map)))
-        _check(self._L.starch_map_host(self._h, ctypes.byref(r), m, ctypes.byref(o)), self._h)
+        _check(self._L.starch_map_host(self._h, *_pair(ref, map), ctypes.byref(o)), self._h)
         return self._output()
 
     def bedmap_device(self, d_ptr: int, offs, cols=("echo", "count"), range=0, skip_unmapped=False, delim=b"|") -> int:
@@ -913,19 +894,14 @@ class Starch:
         offs[1]), the map (if offs has a third entry) at d_ptr + [offs[1],
         offs[2]); returns the output size (output_device_ptr())."""
         o = _map_options(cols, range, skip_unmapped, delim)
-        offs = [int(x) for x in offs]
-        a = (ctypes.c_uint64 * len(offs))(*offs)
-        _check(self._L.starch_map_device(self._h, ctypes.c_void_p(d_ptr), a, len(offs) - 1, ctypes.byref(o)), self._h)
-        k = ctypes.c_uint64()
-        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
-        return k.value
+        a, k = _offs(offs)
+        _check(self._L.starch_map_device(self._h, ctypes.c_void_p(d_ptr), a, k, ctypes.byref(o)), self._h)
+        return self._output_size()
 
     def map_stats(self) -> dict:
         """Of the last bedmap(): n_ref / n_map / n_chromosomes / map_runs_merged /
         stops_sorted / lines_out / output_bytes / ms_*."""
-        s = MapStats()
-        _check(self._L.starch_map_get_stats(self._h, ctypes.byref(s)), self._h)
-        return {k: getattr(s, k) for k, _ in MapStats._fields_}
+        return self._stats(MapStats, self._L.starch_map_get_stats)
 
     # ---- closest-features ----
     def closest_features(self, ref, query, closest=False, dist=False, no_overlaps=False, no_ref=False, delim=b"|") -> bytes:
@@ -940,9 +916,7 @@ class Starch:
         malformed or unsorted line is StarchError -12 naming input (ref 0,
         query 1) and line; a bad argument is -2."""
         o = _closest_options(closest, dist, no_overlaps, no_ref, delim)
-        r = SetopInput(bytes(ref), len(ref))
-        q = SetopInput(bytes(query), len(query))
-        _check(self._L.starch_closest_host(self._h, ctypes.byref(r), ctypes.byref(q), ctypes.byref(o)), self._h)
+        _check(self._L.starch_closest_host(self._h, *_pair(ref, query), ctypes.byref(o)), self._h)
         return self._output()
 
     def closest_device(self, d_ptr: int, offs, closest=False, dist=False, no_overlaps=False, no_ref=False, delim=b"|") -> int:
@@ -950,21 +924,14 @@ class Starch:
         offs[1]), the query at d_ptr + [offs[1], offs[2]); returns the output
         size (output_device_ptr())."""
         o = _closest_options(closest, dist, no_overlaps, no_ref, delim)
-        offs = [int(x) for x in offs]
-        if len(offs) != 3:
-            raise ValueError("closest_device: offs holds three values")
-        a = (ctypes.c_uint64 * 3)(*offs)
+        a, _ = _offs(offs, 3, "closest_device: offs holds three values")
         _check(self._L.starch_closest_device(self._h, ctypes.c_void_p(d_ptr), a, ctypes.byref(o)), self._h)
-        k = ctypes.c_uint64()
-        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
-        return k.value
+        return self._output_size()
 
     def closest_stats(self) -> dict:
         """Of the last closest_features(): n_ref / n_query / n_chromosomes /
         stops_sorted / left_na / right_na / lines_out / output_bytes / ms_*."""
-        s = ClosestStats()
-        _check(self._L.starch_closest_get_stats(self._h, ctypes.byref(s)), self._h)
-        return {k: getattr(s, k) for k, _ in ClosestStats._fields_}
+        return self._stats(ClosestStats, self._L.starch_closest_get_stats)
 
     # ---- bedmap-elements ----
     def map_elements(self, ref, map=None, cols=("echo", "echo_map"), criterion=("bp_ovr", 1), skip_unmapped=False,
@@ -983,9 +950,7 @@ class Starch:
         echo_map_score asks for, is StarchError -12 naming input (ref 0, map
         1) and line; a bad argument is -2."""
         o = _mapel_options(cols, criterion, skip_unmapped, delim, multidelim)
-        r = SetopInput(bytes(ref), len(ref))
-        m = None if map is None else ctypes.byref(SetopInput(bytes(map), len(map)))
-        _check(self._L.starch_mapel_host(self._h, ctypes.byref(r), m, ctypes.byref(o)), self._h)
+        _check(self._L.starch_mapel_host(self._h, *_pair(ref, map), ctypes.byref(o)), self._h)
         return self._output()
 
     def map_elements_device(self, d_ptr: int, offs, cols=("echo", "echo_map"), criterion=("bp_ovr", 1), skip_unmapped=False,
@@ -994,20 +959,15 @@ class Starch:
         offs[1]), the map (if offs has a third entry) at d_ptr + [offs[1],
         offs[2]); returns the output size (output_device_ptr())."""
         o = _mapel_options(cols, criterion, skip_unmapped, delim, multidelim)
-        offs = [int(x) for x in offs]
-        a = (ctypes.c_uint64 * len(offs))(*offs)
-        _check(self._L.starch_mapel_device(self._h, ctypes.c_void_p(d_ptr), a, len(offs) - 1, ctypes.byref(o)), self._h)
-        k = ctypes.c_uint64()
-        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
-        return k.value
+        a, k = _offs(offs)
+        _check(self._L.starch_mapel_device(self._h, ctypes.c_void_p(d_ptr), a, k, ctypes.byref(o)), self._h)
+        return self._output_size()
 
     def mapel_stats(self) -> dict:
         """Of the last map_elements(): n_ref / n_map / n_chromosomes / hits /
         heavy_lines / walk_steps / lines_out / output_bytes (also under the
         name out_bytes) / ms_*."""
-        s = MapelStats()
-        _check(self._L.starch_mapel_get_stats(self._h, ctypes.byref(s)), self._h)
-        d = {k: getattr(s, k) for k, _ in MapelStats._fields_}
+        d = self._stats(MapelStats, self._L.starch_mapel_get_stats)
         d["out_bytes"] = d["output_bytes"]
         return d
 
@@ -1028,9 +988,7 @@ class Starch:
         sum on is asked for, is StarchError -12 naming input (ref 0, map 1)
         and line; a bad argument is -2."""
         o = _mapsc_options(cols, criterion, prec, kth, skip_unmapped, delim)
-        r = SetopInput(bytes(ref), len(ref))
-        m = None if map is None else ctypes.byref(SetopInput(bytes(map), len(map)))
-        _check(self._L.starch_mapsc_host(self._h, ctypes.byref(r), m, ctypes.byref(o)), self._h)
+        _check(self._L.starch_mapsc_host(self._h, *_pair(ref, map), ctypes.byref(o)), self._h)
         return self._output()
 
     def map_scores_device(self, d_ptr: int, offs, cols=("echo", "mean"), criterion=("bp_ovr", 1), prec=6, kth=None,
@@ -1039,20 +997,15 @@ class Starch:
         offs[1]), the map (if offs has a third entry) at d_ptr + [offs[1],
         offs[2]); returns the output size (output_device_ptr())."""
         o = _mapsc_options(cols, criterion, prec, kth, skip_unmapped, delim)
-        offs = [int(x) for x in offs]
-        a = (ctypes.c_uint64 * len(offs))(*offs)
-        _check(self._L.starch_mapsc_device(self._h, ctypes.c_void_p(d_ptr), a, len(offs) - 1, ctypes.byref(o)), self._h)
-        k = ctypes.c_uint64()
-        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
-        return k.value
+        a, k = _offs(offs)
+        _check(self._L.starch_mapsc_device(self._h, ctypes.c_void_p(d_ptr), a, k, ctypes.byref(o)), self._h)
+        return self._output_size()
 
     def mapsc_stats(self) -> dict:
         """Of the last map_scores(): n_ref / n_map / n_chromosomes / hits /
         straddling / sorted_hits / radix_passes / lines_out / output_bytes /
         ms_*."""
-        s = MapscStats()
-        _check(self._L.starch_mapsc_get_stats(self._h, ctypes.byref(s)), self._h)
-        return {k: getattr(s, k) for k, _ in MapscStats._fields_}
+        return self._stats(MapscStats, self._L.starch_mapsc_get_stats)
 
     # ---- convert2bed ----
     def convert(self, data: bytes, fmt: str, vcf_class="all", keep_header=False, sort=True) -> bytes:
@@ -1071,9 +1024,7 @@ class Starch:
         """The same for text in HBM; returns the output size (output_device_ptr())."""
         o = _convert_options(fmt, vcf_class, keep_header, sort)
         _check(self._L.starch_convert_device(self._h, ctypes.c_void_p(d_ptr), n, ctypes.byref(o)), self._h)
-        k = ctypes.c_uint64()
-        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
-        return k.value
+        return self._output_size()
 
     def compress_converted(self, data: bytes, fmt: str, vcf_class="all", keep_header=False, emit_index=True) -> bytes:
         """convert, sort and compress without leaving HBM: the archive
@@ -1086,9 +1037,7 @@ class Starch:
     def convert_stats(self) -> dict:
         """Of the last convert(): input_bytes / input_lines / header_lines /
         data_lines / declarations / lines_out / output_bytes / sorted / ms_*."""
-        s = ConvertStats()
-        _check(self._L.starch_convert_get_stats(self._h, ctypes.byref(s)), self._h)
-        return {k: getattr(s, k) for k, _ in ConvertStats._fields_}
+        return self._stats(ConvertStats, self._L.starch_convert_get_stats)
 
     # ---- sam2bed, psl2bed, rmsk2bed ----
     def align2bed(self, data: bytes, fmt: str, split=False, split_deletions=False, all_reads=False, reduced=False,
@@ -1111,9 +1060,7 @@ class Starch:
         """The same for text in HBM; returns the output size (output_device_ptr())."""
         o = _align_options(fmt, split, split_deletions, all_reads, reduced, keep_header, sort)
         _check(self._L.starch_align_device(self._h, ctypes.c_void_p(d_ptr), n, ctypes.byref(o)), self._h)
-        k = ctypes.c_uint64()
-        _check(self._L.starch_output_size(self._h, ctypes.byref(k)), self._h)
-        return k.value
+        return self._output_size()
 
     def compress_aligned(self, data: bytes, fmt: str, split=False, split_deletions=False, all_reads=False, reduced=False,
                          keep_header=False, emit_index=True) -> bytes:
@@ -1127,9 +1074,7 @@ class Starch:
     def align_stats(self) -> dict:
         """Of the last align2bed(): input_bytes / input_lines / header_lines /
         records / unmapped_dropped / lines_out / output_bytes / sorted / ms_*."""
-        s = AlignStats()
-        _check(self._L.starch_align_get_stats(self._h, ctypes.byref(s)), self._h)
-        return {k: getattr(s, k) for k, _ in AlignStats._fields_}
+        return self._stats(AlignStats, self._L.starch_align_get_stats)
 
     def cat(self, archives) -> bytes:
         """starchcat: the archives (bytes, in order) merged into one, with this
@@ -1142,32 +1087,97 @@ class Starch:
     def cat_stats(self) -> dict:
         """Of the last cat(): streams_in / streams_copied / groups_merged /
         runs_decoded / lines_merged / bytes_copied / bytes_decoded."""
-        s = CatStats()
-        _check(self._L.starch_cat_get_stats(self._h, ctypes.byref(s)), self._h)
-        return {k: getattr(s, k) for k, _ in CatStats._fields_}
+        return self._stats(CatStats, self._L.starch_cat_get_stats)
+
+
+def _as_dict(s) -> dict:
+    """A ctypes structure's fields by name."""
+    return {k: getattr(s, k) for k, _ in s._fields_}
+
+
+def _offs(offs, exact=None, why=None):
+    """(uint64 array of the offsets, number of inputs they bound); exact: the only length allowed, else ValueError(why)."""
+    offs = [int(x) for x in offs]
+    if exact is not None and len(offs) != exact:
+        raise ValueError(why)
+    return (ctypes.c_uint64 * len(offs))(*offs), len(offs) - 1
+
+
+def _inputs(inputs):
+    """(SetopInput array, its length) of a list of bytes; the array keeps the bytes alive."""
+    inputs = [bytes(b) for b in inputs]
+    arr = (SetopInput * max(1, len(inputs)))()
+    for k, b in enumerate(inputs):
+        arr[k].data = b
+        arr[k].len = len(b)
+    return arr, len(inputs)
+
+
+def _pair(ref, other):
+    """The two SetopInput arguments of a call that takes a reference and a second input, which may be None."""
+    return (ctypes.byref(SetopInput(bytes(ref), len(ref))),
+            None if other is None else ctypes.byref(SetopInput(bytes(other), len(other))))
+
+
+def _constants(fn, n):
+    """The n uint32 values fn writes: the value for one, a tuple for several."""
+    v = [ctypes.c_uint32() for _ in range(n)]
+    _check(fn(*[ctypes.byref(x) for x in v]))
+    return v[0].value if n == 1 else tuple(x.value for x in v)
+
+
+def _named(cols, table, tool):
+    """cols as a list, every one a name of table, else ValueError."""
+    cols = list(cols)
+    for c in cols:
+        if c not in table:
+            raise ValueError("%s: a column must be one of %s" % (tool, ", ".join(table)))
+    return cols
+
+
+def _fill_cols(o, cols, table):
+    """ncols and as many of cols as the structure holds; too many are left to the library."""
+    o.ncols = len(cols)
+    for k, c in enumerate(cols[:len(o.cols)]):
+        o.cols[k] = table[c]
+
+
+def _put_delim(o, field, delim):
+    """The delimiter field and its length; an over-long one is left to the library."""
+    delim = bytes(delim)
+    setattr(o, field + "_len", len(delim))
+    ctypes.memmove(ctypes.addressof(o) + getattr(type(o), field).offset, delim, min(len(delim), 8))
+
+
+def _criterion(o, criterion):
+    """The five criterion fields of MapelOptions or MapscOptions; the messages name bedmap-elements for both."""
+    criterion = (criterion,) if isinstance(criterion, str) else tuple(criterion)
+    if not criterion or criterion[0] not in MAPEL_CRITERIA or len(criterion) != (1 if criterion[0] == "exact" else 2):
+        raise ValueError("bedmap-elements: criterion is ('exact',) or (name, value) with a name of %s" % ", ".join(MAPEL_CRITERIA))
+    o.criterion = MAPEL_CRITERIA[criterion[0]]
+    if criterion[0] == "bp_ovr":
+        o.n = int(criterion[1])
+    elif criterion[0] == "range":
+        o.range = int(criterion[1])
+    elif criterion[0] != "exact":
+        o.frac_num, o.frac_digits = mapel_fraction(criterion[1])
 
 
 def sort_constants():
     """(lines per radix tile, bytes from which an output line is copied by a
     whole wave) of the sort's kernels; no GPU needed."""
-    a, b = ctypes.c_uint32(), ctypes.c_uint32()
-    _check(load().starch_sort_constants(ctypes.byref(a), ctypes.byref(b)))
-    return a.value, b.value
+    return _constants(load().starch_sort_constants, 2)
 
 
 def setop_constants():
     """Lines per tile of the set operations' segmented max-scan; no GPU needed."""
-    a = ctypes.c_uint32()
-    _check(load().starch_setop_constants(ctypes.byref(a)))
-    return a.value
+    return _constants(load().starch_setop_constants, 1)
 
 
 def bedops_constants():
     """(runs per tile of element-of's range maximum, pieces per workgroup of
     chop's expansion); no GPU needed."""
-    a, b = ctypes.c_uint32(), ctypes.c_uint32()
-    _check(load().starch_bedops_constants(ctypes.byref(a), ctypes.byref(b)))
-    return a.value, b.value
+    return _constants(load().starch_bedops_constants, 2)
 
 
 def _bedops_options(op, threshold, chop, stagger, exclude_short):
@@ -1188,7 +1198,7 @@ def _bedops_options(op, threshold, chop, stagger, exclude_short):
         o.threshold, o.threshold_is_percent = int(t), 0
     o.chop = int(chop)
     o.stagger = 0 if stagger is None else int(stagger)
-    o.exclude_short = 1 if exclude_short else 0
+    o.exclude_short = bool(exclude_short)
     return o
 
 
@@ -1196,47 +1206,30 @@ def map_constants():
     """(reference lines per query workgroup, largest map window in elements
     that is staged in LDS, 0 when there is no such path) of bedmap's query
     kernel; no GPU needed."""
-    a, b = ctypes.c_uint32(), ctypes.c_uint32()
-    _check(load().starch_map_constants(ctypes.byref(a), ctypes.byref(b)))
-    return a.value, b.value
+    return _constants(load().starch_map_constants, 2)
 
 
 def _map_options(cols, range_, skip_unmapped, delim):
     """starch_map_options; unknown names are ValueError, everything else is left to the library."""
-    cols = list(cols)
-    for c in cols:
-        if c not in MAPCOLS:
-            raise ValueError("bedmap: a column must be one of %s" % ", ".join(MAPCOLS))
-    delim = bytes(delim)
+    cols = _named(cols, MAPCOLS, "bedmap")
     o = MapOptions()
-    o.ncols = len(cols)
-    for k, c in enumerate(cols[:8]):
-        o.cols[k] = MAPCOLS[c]
+    _put_delim(o, "delim", delim)
+    _fill_cols(o, cols, MAPCOLS)
     o.range = int(range_)
-    o.skip_unmapped = 1 if skip_unmapped else 0
-    o.delim_len = len(delim)
-    ctypes.memmove(ctypes.addressof(o) + MapOptions.delim.offset, delim, min(len(delim), 8))
+    o.skip_unmapped = bool(skip_unmapped)
     return o
 
 
 def closest_constants():
     """(reference lines per query workgroup, fan-out of the hierarchy of maxima
     over the query stops) of closest-features' kernels; no GPU needed."""
-    a, b = ctypes.c_uint32(), ctypes.c_uint32()
-    _check(load().starch_closest_constants(ctypes.byref(a), ctypes.byref(b)))
-    return a.value, b.value
+    return _constants(load().starch_closest_constants, 2)
 
 
 def _closest_options(closest, dist, no_overlaps, no_ref, delim):
     """starch_closest_options; the delimiter's length is left to the library."""
-    delim = bytes(delim)
-    o = ClosestOptions()
-    o.closest = 1 if closest else 0
-    o.dist = 1 if dist else 0
-    o.no_overlaps = 1 if no_overlaps else 0
-    o.no_ref = 1 if no_ref else 0
-    o.delim_len = len(delim)
-    ctypes.memmove(ctypes.addressof(o) + ClosestOptions.delim.offset, delim, min(len(delim), 8))
+    o = ClosestOptions(bool(closest), bool(dist), bool(no_overlaps), bool(no_ref))
+    _put_delim(o, "delim", delim)
     return o
 
 
@@ -1245,9 +1238,7 @@ def mapel_constants():
     the map stops, candidates from which a reference line's run is tested by a
     whole wave, bound on walk_steps per reference line and per hit) of
     bedmap-elements' kernels; no GPU needed."""
-    v = [ctypes.c_uint32() for _ in range(4)]
-    _check(load().starch_mapel_constants(*[ctypes.byref(x) for x in v]))
-    return tuple(x.value for x in v)
+    return _constants(load().starch_mapel_constants, 4)
 
 
 def mapel_fraction(f):
@@ -1280,30 +1271,13 @@ def mapel_fraction(f):
 def _mapel_options(cols, criterion, skip_unmapped, delim, multidelim):
     """starch_mapel_options; unknown names and a fraction that is no exact
     decimal in (0, 1] are ValueError, everything else is left to the library."""
-    cols = list(cols)
-    for c in cols:
-        if c not in MAPEL_COLS:
-            raise ValueError("bedmap-elements: a column must be one of %s" % ", ".join(MAPEL_COLS))
-    criterion = (criterion,) if isinstance(criterion, str) else tuple(criterion)
-    if not criterion or criterion[0] not in MAPEL_CRITERIA or len(criterion) != (1 if criterion[0] == "exact" else 2):
-        raise ValueError("bedmap-elements: criterion is ('exact',) or (name, value) with a name of %s" % ", ".join(MAPEL_CRITERIA))
-    delim, multidelim = bytes(delim), bytes(multidelim)
+    cols = _named(cols, MAPEL_COLS, "bedmap-elements")
     o = MapelOptions()
-    o.ncols = len(cols)
-    for k, c in enumerate(cols[:12]):
-        o.cols[k] = MAPEL_COLS[c]
-    o.criterion = MAPEL_CRITERIA[criterion[0]]
-    if criterion[0] == "bp_ovr":
-        o.n = int(criterion[1])
-    elif criterion[0] == "range":
-        o.range = int(criterion[1])
-    elif criterion[0] != "exact":
-        o.frac_num, o.frac_digits = mapel_fraction(criterion[1])
-    o.skip_unmapped = 1 if skip_unmapped else 0
-    o.delim_len = len(delim)
-    o.multidelim_len = len(multidelim)
-    ctypes.memmove(ctypes.addressof(o) + MapelOptions.delim.offset, delim, min(len(delim), 8))
-    ctypes.memmove(ctypes.addressof(o) + MapelOptions.multidelim.offset, multidelim, min(len(multidelim), 8))
+    _criterion(o, criterion)
+    _put_delim(o, "delim", delim)
+    _put_delim(o, "multidelim", multidelim)
+    _fill_cols(o, cols, MAPEL_COLS)
+    o.skip_unmapped = bool(skip_unmapped)
     return o
 
 
@@ -1311,43 +1285,31 @@ def mapsc_constants():
     """(contiguous hits per workgroup of bedmap-scores' segmented reduction,
     bytes from which an echoed line is copied by a whole wave); no GPU
     needed."""
-    a, b = ctypes.c_uint32(), ctypes.c_uint32()
-    _check(load().starch_mapsc_constants(ctypes.byref(a), ctypes.byref(b)))
-    return a.value, b.value
+    return _constants(load().starch_mapsc_constants, 2)
 
 
 def _mapsc_options(cols, criterion, prec, kth, skip_unmapped, delim):
     """starch_mapsc_options; unknown names, a criterion fraction or a kth that
     is no exact decimal in (0, 1], and a prec that is no integer are
     ValueError, everything else is left to the library."""
-    cols = list(cols)
-    for c in cols:
-        if c not in MAPSC_COLS:
-            raise ValueError("bedmap-scores: a column must be one of %s" % ", ".join(MAPSC_COLS))
+    cols = _named(cols, MAPSC_COLS, "bedmap-scores")
     if isinstance(prec, bool) or not isinstance(prec, int) or prec < 0:
         raise ValueError("bedmap-scores: prec is an integer from 0 to 9")
-    e = _mapel_options(("echo",), criterion, skip_unmapped, delim, b";")
     o = MapscOptions()
-    o.ncols = len(cols)
-    for k, c in enumerate(cols[:12]):
-        o.cols[k] = MAPSC_COLS[c]
-    o.criterion, o.n, o.range, o.frac_num, o.frac_digits = e.criterion, e.n, e.range, e.frac_num, e.frac_digits
+    _criterion(o, criterion)
+    _put_delim(o, "delim", delim)
+    _fill_cols(o, cols, MAPSC_COLS)
     if kth is not None:
         o.kth_num, o.kth_digits = mapel_fraction(kth)
     o.prec = min(prec, 2 ** 32 - 1)
-    o.skip_unmapped = e.skip_unmapped
-    o.delim_len = e.delim_len
-    delim = bytes(delim)
-    ctypes.memmove(ctypes.addressof(o) + MapscOptions.delim.offset, delim, min(len(delim), 8))
+    o.skip_unmapped = bool(skip_unmapped)
     return o
 
 
 def convert_constants():
     """(threads per block of convert2bed's per-line kernels, bytes from which a
     copied tail is left to a whole wave); no GPU needed."""
-    a, b = ctypes.c_uint32(), ctypes.c_uint32()
-    _check(load().starch_convert_constants(ctypes.byref(a), ctypes.byref(b)))
-    return a.value, b.value
+    return _constants(load().starch_convert_constants, 2)
 
 
 def _convert_options(fmt, vcf_class, keep_header, sort):
@@ -1357,21 +1319,14 @@ def _convert_options(fmt, vcf_class, keep_header, sort):
         raise ValueError("convert: fmt must be one of %s" % ", ".join(CONVERT_FORMATS))
     if vcf_class not in VCF_CLASSES:
         raise ValueError("convert: vcf_class must be one of %s" % ", ".join(VCF_CLASSES))
-    o = ConvertOptions()
-    o.format = CONVERT_FORMATS[fmt]
-    o.vcf_class = VCF_CLASSES[vcf_class]
-    o.keep_header = 1 if keep_header else 0
-    o.no_sort = 0 if sort else 1
-    return o
+    return ConvertOptions(CONVERT_FORMATS[fmt], VCF_CLASSES[vcf_class], bool(keep_header), not sort)
 
 
 def align_constants():
     """(threads per block of the per-line kernels of sam2bed, psl2bed and
     rmsk2bed, bytes from which a copied tail is left to a whole wave); no GPU
     needed."""
-    a, b = ctypes.c_uint32(), ctypes.c_uint32()
-    _check(load().starch_align_constants(ctypes.byref(a), ctypes.byref(b)))
-    return a.value, b.value
+    return _constants(load().starch_align_constants, 2)
 
 
 def _align_options(fmt, split, split_deletions, all_reads, reduced, keep_header, sort):
@@ -1379,15 +1334,8 @@ def _align_options(fmt, split, split_deletions, all_reads, reduced, keep_header,
     fmt = fmt.lower() if isinstance(fmt, str) else fmt
     if fmt not in ALIGN_FORMATS:
         raise ValueError("align2bed: fmt must be one of %s" % ", ".join(ALIGN_FORMATS))
-    o = AlignOptions()
-    o.format = ALIGN_FORMATS[fmt]
-    o.split = 1 if split else 0
-    o.split_deletions = 1 if split_deletions else 0
-    o.all_reads = 1 if all_reads else 0
-    o.reduced = 1 if reduced else 0
-    o.keep_header = 1 if keep_header else 0
-    o.no_sort = 0 if sort else 1
-    return o
+    return AlignOptions(ALIGN_FORMATS[fmt], bool(split), bool(split_deletions), bool(all_reads), bool(reduced),
+                        bool(keep_header), not sort)
 
 
 def _cat_args(archives):

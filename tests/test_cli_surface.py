@@ -1,13 +1,18 @@
-"""What the six commands show before any GPU work: the help text byte for
+"""What the thirteen commands show before any GPU work: the help text byte for
 byte, the version line, and the exit codes and messages for a missing input,
-an unknown option and stdin named twice.  None of this opens a device.
+an unknown option, stdin named twice and every other bad command line of the
+commands whose option parsers are built from tools/cli_common.hpp.  None of
+this opens a device.
 
 tests/golden/cli_help/<command>.txt is the --help output of the commands as
-they were before their shared code moved into tools/cli_common.hpp.  Checks
+they were before their shared code moved into tools/cli_common.hpp, and
+tests/golden/cli_usage.json (command, arguments, exit status, first line of
+stderr) what they answered then; {bed} in it stands for a small BED file.  Checks
 that test_sortbed_cli.py, test_setops_cpu.py, test_bedops2_cpu.py and
 test_map_cpu.py already make (sort-bed, bedops and bedmap: missing input,
 unknown option) are not repeated here."""
 import errno
+import json
 import os
 import subprocess
 
@@ -16,7 +21,10 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "starch_amd", "_build")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "cli_help")
-COMMANDS = ("starch3", "unstarch", "starchcat", "sort-bed", "bedops", "bedmap")
+COMMANDS = ("starch3", "unstarch", "starchcat", "sort-bed", "bedops", "bedmap", "closest-features", "convert2bed",
+            "bedmap-elements", "bedmap-scores", "sam2bed", "psl2bed", "rmsk2bed")
+with open(os.path.join(ROOT, "tests", "golden", "cli_usage.json")) as _f:
+    USAGE_TABLE = json.load(_f)
 NO_GPU = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1")
 MISSING = os.path.join(ROOT, "no", "such", "file")
 
@@ -33,6 +41,24 @@ def test_help_text(cmd):
     assert r.returncode == 0 and r.stderr == b""
     with open(os.path.join(GOLDEN, cmd + ".txt"), "rb") as f:
         assert r.stdout == f.read()
+
+
+# A bad command line: its message, then the usage text, and exit 2.  An accepted one gets as far as
+# asking for a device, and with none visible that is EINVAL after one line.
+@pytest.mark.parametrize("cmd", sorted(set(e["cmd"] for e in USAGE_TABLE)))
+def test_bad_command_lines(cmd, tmp_path):
+    bed = tmp_path / "in.bed"
+    bed.write_bytes(b"chr1\t1\t2\n")
+    with open(os.path.join(GOLDEN, cmd + ".txt"), "rb") as f:
+        usage = f.read()
+    entries = [e for e in USAGE_TABLE if e["cmd"] == cmd]
+    assert entries and {e["status"] for e in entries} == {2, errno.EINVAL}
+    for e in entries:
+        r = _run(cmd, *[a.replace("{bed}", str(bed)) for a in e["argv"]], env=NO_GPU)
+        first, _, rest = r.stderr.partition(b"\n")
+        assert r.returncode == e["status"] and r.stdout == b"", e
+        assert first == e["stderr_first_line"].replace("{bed}", str(bed)).encode(), e
+        assert rest == (usage if e["status"] == 2 else b""), e
 
 
 @pytest.mark.parametrize("cmd", ("starch3", "unstarch", "starchcat"))

@@ -8,73 +8,47 @@
 // not have (answered before a GPU is opened), otherwise as bedmap
 // (tools/bedmap_cli.cpp): ENODATA for a missing input, EINVAL for a data error
 // (the library's text names the input and the line), ENOMEM, EIO.
-#include <errno.h>
-#include <getopt.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <string>
-#include <vector>
-
 #include "cli_common.hpp"
 
-static const char* kName = "closest-features";
-static const char* kVersion = "0.1 (mi355x)";
-static const int kUsageError = 2;
-
-static void usage(FILE* f)
-{
-    fprintf(f,
-            "%s\n  version: %s\n\n"
-            "USAGE: closest-features [--closest|--shortest] [--dist] [--no-overlaps] [--no-ref] [--delim S]\n"
-            "                        [--device N] input-file query-file\n\n"
-            "  input-file and query-file are sorted BED (see sort-bed) or .starch archives, which\n"
-            "  are recognised by their first four bytes and not by their names; - is stdin and may\n"
-            "  be named once.  Every line needs stop > start.\n"
-            "  One line is written per line of input-file, in its order: the line itself, the\n"
-            "  nearest query line on its left and the nearest on its right, joined by the\n"
-            "  delimiter; NA where a side has none.  Only lines of one chromosome are compared.\n"
-            "  A query line that sorts below the input line (by start, then stop) counts as left,\n"
-            "  any other as right; one that overlaps the input line is at distance 0.  Among\n"
-            "  equally near lines the left side takes the last, the right side the first.\n\n"
-            "  --closest         write the nearer of the two alone; a tie goes to the left one\n"
-            "  --shortest        the same as --closest\n"
-            "  --dist            after every query line its signed distance in bases: 0 when it\n"
-            "                    overlaps, -1 or 1 when it abuts on the left or right; NA for NA\n"
-            "  --no-overlaps     query lines that overlap the input line are not considered\n"
-            "  --no-ref          do not write the input line\n"
-            "  --delim S         the field delimiter, 1 to 8 bytes (default |)\n"
-            "  --device N        GPU to compute on (default 0)\n"
-            "  --help, --version\n\n"
-            "  Not supported: --center, --chrom, --ec, --header.\n\n"
-            "  This is modelled on BEDOPS' closest-features for the options above, but it is\n"
-            "  unverified against a BEDOPS binary.\n\n"
-            "  An unsorted input, a line with stop <= start or a malformed line is reported\n"
-            "  with its input number (input-file is 0, query-file is 1) and line number\n"
-            "  (from 1); nothing is written.\n",
-            kName, kVersion);
-}
-
-static int bad_usage(const char* why, const char* what)
-{
-    fprintf(stderr, "Error: %s%s%s\n", why, what ? ": " : "", what ? what : "");
-    usage(stderr);
-    return kUsageError;
-}
+static const char* kHelp =
+    "USAGE: closest-features [--closest|--shortest] [--dist] [--no-overlaps] [--no-ref] [--delim S]\n"
+    "                        [--device N] input-file query-file\n\n"
+    "  input-file and query-file are sorted BED (see sort-bed) or .starch archives, which\n"
+    "  are recognised by their first four bytes and not by their names; - is stdin and may\n"
+    "  be named once.  Every line needs stop > start.\n"
+    "  One line is written per line of input-file, in its order: the line itself, the\n"
+    "  nearest query line on its left and the nearest on its right, joined by the\n"
+    "  delimiter; NA where a side has none.  Only lines of one chromosome are compared.\n"
+    "  A query line that sorts below the input line (by start, then stop) counts as left,\n"
+    "  any other as right; one that overlaps the input line is at distance 0.  Among\n"
+    "  equally near lines the left side takes the last, the right side the first.\n\n"
+    "  --closest         write the nearer of the two alone; a tie goes to the left one\n"
+    "  --shortest        the same as --closest\n"
+    "  --dist            after every query line its signed distance in bases: 0 when it\n"
+    "                    overlaps, -1 or 1 when it abuts on the left or right; NA for NA\n"
+    "  --no-overlaps     query lines that overlap the input line are not considered\n"
+    "  --no-ref          do not write the input line\n"
+    "  --delim S         the field delimiter, 1 to 8 bytes (default |)\n"
+    "  --device N        GPU to compute on (default 0)\n"
+    "  --help, --version\n\n"
+    "  Not supported: --center, --chrom, --ec, --header.\n\n"
+    "  This is modelled on BEDOPS' closest-features for the options above, but it is\n"
+    "  unverified against a BEDOPS binary.\n\n"
+    "  An unsorted input, a line with stop <= start or a malformed line is reported\n"
+    "  with its input number (input-file is 0, query-file is 1) and line number\n"
+    "  (from 1); nothing is written.\n";
+static const cli::Command kCmd = {"closest-features", "0.1 (mi355x)", kHelp, 2};   // 2: the exit code for a bad command line
 
 int main(int argc, char** argv)
 {
-    enum { O_CLOSEST = 256, O_DIST, O_NOOVR, O_NOREF, O_DELIM, O_DEVICE, O_HELP, O_VERSION };
+    enum { O_CLOSEST = 256, O_DIST, O_NOOVR, O_NOREF, O_DELIM };
     static struct option longs[] = {{"closest", no_argument, nullptr, O_CLOSEST},
                                     {"shortest", no_argument, nullptr, O_CLOSEST},
                                     {"dist", no_argument, nullptr, O_DIST},
                                     {"no-overlaps", no_argument, nullptr, O_NOOVR},
                                     {"no-ref", no_argument, nullptr, O_NOREF},
                                     {"delim", required_argument, nullptr, O_DELIM},
-                                    {"device", required_argument, nullptr, O_DEVICE},
-                                    {"help", no_argument, nullptr, O_HELP},
-                                    {"version", no_argument, nullptr, O_VERSION},
+                                    CLI_COMMON_OPTIONS,
                                     {nullptr, 0, nullptr, 0}};
     starch_closest_options opt;
     memset(&opt, 0, sizeof opt);
@@ -85,37 +59,16 @@ int main(int argc, char** argv)
     opterr = 0;
     int c;
     while ((c = getopt_long(argc, argv, "", longs, nullptr)) != -1) {
+        int e = cli::GO_ON;
         switch (c) {
             case O_CLOSEST: opt.closest = 1; break;
             case O_DIST: opt.dist = 1; break;
             case O_NOOVR: opt.no_overlaps = 1; break;
             case O_NOREF: opt.no_ref = 1; break;
-            case O_DELIM: {
-                if (have_delim) return bad_usage("an option is given twice", "--delim");
-                const size_t n = strlen(optarg);
-                if (n < 1 || n > sizeof opt.delim) return bad_usage("--delim needs 1 to 8 bytes", optarg);
-                memcpy(opt.delim, optarg, n);
-                opt.delim_len = (uint32_t)n;
-                have_delim = true;
-                break;
-            }
-            case O_DEVICE: device = atoi(optarg); break;
-            case O_HELP: usage(stdout); return 0;
-            case O_VERSION: cli::print_version(kName, kVersion); return 0;
-            default: return bad_usage("unsupported or unknown option", argv[optind - 1]);
+            case O_DELIM: e = cli::take_delim(kCmd, opt.delim, &opt.delim_len, &have_delim, "--delim", "--delim needs 1 to 8 bytes"); break;
+            default: e = cli::take_common(kCmd, c, argv, &device);
         }
+        if (e != cli::GO_ON) return e;
     }
-    std::vector<std::string> paths;
-    for (int i = optind; i < argc; ++i) paths.push_back(argv[i]);
-    if (paths.size() != 2) return bad_usage("one input file and one query file are needed", nullptr);
-    if (paths[0] == "-" && paths[1] == "-") return bad_usage("stdin (-) may be named once", nullptr);
-
-    std::vector<std::vector<char>> data;
-    if (const int e = cli::load_inputs(paths, &data)) return e;
-    starch_setop_input in[2];
-    for (size_t k = 0; k < 2; ++k) in[k] = starch_setop_input{data[k].data(), (uint64_t)data[k].size()};
-
-    starch_ctx* ctx = nullptr;
-    if (const int e = cli::open_ctx(device, &ctx)) return e;
-    return cli::finish_output(ctx, starch_closest_host(ctx, &in[0], &in[1], &opt), "Error: %s (%s)\n");
+    return cli::run_two_inputs(kCmd, argc, argv, 2, "one input file and one query file are needed", device, starch_closest_host, &opt);
 }
