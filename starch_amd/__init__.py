@@ -510,7 +510,8 @@ class Starch:
         o.emit_index = 1 if emit_index else 0
         o.reference_compat = 1 if reference_compat else 0
         o.base_counts = 1 if self.base_counts else 0
-        # gzip (-g): one gzip member per segment (fixed-Huffman deflate on the GPU);
+        # gzip (-g): one gzip member per segment (deflate on the GPU: a block per 4 KiB,
+        # fixed or dynamic Huffman codes, whichever is shorter);
         # the reference itself stops with ENOSYS (kept under reference_compat)
         o.compression_method = 1 if self._method == K_GZIP else 0
         self._note_b = self._note.encode() if self._note else None

@@ -5,7 +5,10 @@ unpinned, and the contract tested here is that every segment's member is a
 valid RFC 1952 gzip member (any zlib inflates it, CRC-32 and ISIZE included)
 whose content is exactly the segment's transformed text as the oracle
 restates it, that the index names the method, and that the archive does not
-depend on the entry point (one call, streaming, virtual shards, the CLI)."""
+depend on the entry point (one call, streaming, virtual shards, the CLI).
+Each 4 KiB sub-chunk is one deflate block, fixed-Huffman or with the block's
+own dynamic codes, whichever is shorter; the small cases here also go through
+the block-level checks of tests/test_gpu_gzip_blocks.py."""
 import gzip
 import os
 import random
@@ -14,7 +17,7 @@ import zlib
 
 import pytest
 
-from tests import corpus, oracle_lib
+from tests import corpus, gz_model, oracle_lib
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +32,7 @@ def ctx():
     c.close()
 
 
-def _check(arch, data):
+def _check(arch, data, blocks=False):
     import starch_amd
     idx, members = starch_amd.parse_archive(arch)
     assert idx["archive"]["compressionFormat"] == "gzip"
@@ -40,6 +43,8 @@ def _check(arch, data):
         assert m[:3] == b"\x1f\x8b\x08"
         assert gzip.decompress(m) == text
         assert meta["combinedCRC"] == zlib.crc32(text)
+        if blocks:                                 # every block against the token-level model
+            gz_model.check_member(m, text)
     return members
 
 
@@ -58,7 +63,7 @@ def _cases():
 
 @pytest.mark.parametrize("name,data", list(_cases()), ids=lambda x: x if isinstance(x, str) else "")
 def test_gzip_members_inflate_to_transform(ctx, name, data):
-    _check(ctx.compress(data), data)
+    _check(ctx.compress(data), data, blocks=len(data) < 400_000)
 
 
 def test_gzip_generated_hg38(ctx):
@@ -66,7 +71,7 @@ def test_gzip_generated_hg38(ctx):
     data = bytes(starch_amd.gen_bed(0, 600_000))
     arch = ctx.compress(data)
     members = _check(arch, data)
-    # fixed-Huffman LZ77 over 4 KiB blocks: BED text compresses to well under half
+    # LZ77 over 4 KiB blocks, fixed or dynamic Huffman codes: BED text compresses to well under half
     assert sum(len(m) for m in members) < 0.5 * sum(len(t) for _, _, t in oracle_lib.transform(data)[1])
 
 
@@ -91,4 +96,4 @@ def test_cli_gzip(tmp_path):
     c.set_compression_method(starch_amd.K_GZIP)
     assert r.stdout == c.compress(data)
     c.close()
-    _check(r.stdout, data)
+    _check(r.stdout, data, blocks=True)
