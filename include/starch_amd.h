@@ -1244,6 +1244,67 @@ int starch_align_get_stats(starch_ctx* ctx, starch_align_stats* out);
  * whole wave. */
 int starch_align_constants(uint32_t* block_lines, uint32_t* wave_copy_bytes);
 
+/* ---- gzip and BGZF inputs: inflate on the GPU (gz_inflate.hip) ----
+ * An input of at least 18 bytes that begins 1f 8b 08 is gzip: one or more
+ * RFC 1952 members back to back.  When every member carries the BC extra
+ * subfield (bgzip's BGZF: the member's compressed size is in its header and it
+ * inflates to at most 65536 bytes) the member table is made on the host from
+ * the headers alone and every member is inflated by a wave of its own, all in
+ * one launch.  Any other gzip file (gzip, pigz, zlib's gzip framing) is generic:
+ * its members are found by a sizing launch that walks the Huffman symbols of the
+ * whole chain, so a one-member file is decoded by one wave -- correct and serial.
+ * CRC-32 and ISIZE of every member are checked on the GPU.  FHCRC is skipped,
+ * not verified.
+ *
+ * Errors.  A malformed header or deflate stream, a wrong CRC-32 or ISIZE, a
+ * truncated member, a BGZF member that claims more than 65536 bytes or whose
+ * BSIZE reaches past the input, and bytes after the last member that do not
+ * begin a member are STARCH_ERR_DATA: starch_last_error names the member's
+ * number (from 0), its byte offset in the input and the reason.  Nothing is
+ * published from a failed call.
+ *
+ * The host entry points of sort-bed, bedops, bedmap, bedmap-elements,
+ * bedmap-scores, closest-features, convert2bed and sam2bed / psl2bed / rmsk2bed
+ * (starch_sort_host, starch_sort_check_host, starch_sort_encode_host, every
+ * starch_setop_input of the two-input calls, starch_convert_host,
+ * starch_convert_encode_host, starch_align_host, starch_align_encode_host)
+ * recognise a gzip input in the same way and inflate it in HBM where the text is
+ * wanted; the inflated bytes are then taken as text (a gzip of an archive is
+ * not unwrapped).  starch_encode_host and the stream API take their bytes as
+ * they are. */
+typedef struct {
+    uint64_t in_off, in_len;    /* the member: header, deflate data and trailer */
+    uint64_t out_off;           /* exclusive sum of isize */
+    uint32_t isize, crc;        /* the trailer */
+} starch_gunzip_member;
+int starch_gunzip_host(starch_ctx* ctx, const void* gz, uint64_t n);
+/* The same for bytes in HBM.  The whole input is read back to the host, where
+ * the headers are walked, and copied again into the context's padded, aligned
+ * input buffer: two trips over the host link that starch_gunzip_host does not
+ * make.  For a caller whose bytes are in HBM already and small beside the text. */
+int starch_gunzip_device(starch_ctx* ctx, const void* d_gz, uint64_t n);
+/* The plan of a BGZF input: host only, no GPU is opened.  *n_members members,
+ * the first cap of them in out (out may be NULL with cap 0); generic gzip gives
+ * *is_bgzf = 0 and *n_members = 0.  STARCH_ERR_DATA as above, for what the
+ * headers show; STARCH_ERR_MEM when cap is short (the count is still set). */
+int starch_gunzip_plan(const void* gz, uint64_t n, starch_gunzip_member* out, uint64_t cap, uint64_t* n_members,
+                       int* is_bgzf);
+typedef struct {
+    uint64_t members, is_bgzf;
+    uint64_t stored_blocks, fixed_blocks, dynamic_blocks;
+    uint64_t bytes_in, bytes_out;
+    /* ms_plan is host clock; the others are GPU events (ms_size: the sizing
+     * launch of generic gzip, 0 for BGZF) */
+    float ms_plan, ms_upload, ms_size, ms_inflate, ms_crc;
+} starch_gunzip_stats;
+/* Of the last inflate on this context (the last gzip input of a BED command counts). */
+int starch_gunzip_get_stats(starch_ctx* ctx, starch_gunzip_stats* out);
+/* The bytes of the LDS output window, the bits of the primary decode table,
+ * the bytes of a match copied per round and the most a BGZF member inflates to. */
+int starch_gunzip_constants(uint32_t* window_bytes, uint32_t* primary_bits, uint32_t* copy_width, uint32_t* bgzf_max);
+/* 1 for an input that the commands above take as gzip */
+int starch_is_gzip(const void* data, uint64_t n);
+
 int starch_output_size(starch_ctx* ctx, uint64_t* n);
 int starch_output_copy(starch_ctx* ctx, void* dst, uint64_t cap);
 int starch_output_device(starch_ctx* ctx, const void** d_ptr);

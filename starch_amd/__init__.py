@@ -262,6 +262,19 @@ class SortStats(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("ms_parse", "ms_rank", "ms_sort", "ms_gather", "ms_total")]
 
 
+class GunzipMember(ctypes.Structure):
+    """starch_gunzip_member: one member of a BGZF input's plan."""
+    _fields_ = [("in_off", ctypes.c_uint64), ("in_len", ctypes.c_uint64), ("out_off", ctypes.c_uint64),
+                ("isize", ctypes.c_uint32), ("crc", ctypes.c_uint32)]
+
+
+class GunzipStats(ctypes.Structure):
+    """starch_gunzip_stats: the last inflate on a context."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("members", "is_bgzf", "stored_blocks", "fixed_blocks", "dynamic_blocks",
+                                               "bytes_in", "bytes_out")] + \
+               [(n, ctypes.c_float) for n in ("ms_plan", "ms_upload", "ms_size", "ms_inflate", "ms_crc")]
+
+
 class IndexEntry(ctypes.Structure):
     """starch_index_entry: one stream of an archive's index."""
     _fields_ = [("name_off", ctypes.c_uint64), ("name_len", ctypes.c_uint64), ("offset", ctypes.c_uint64),
@@ -406,6 +419,13 @@ def load():
                                      ctypes.c_int),
         "starch_align_get_stats": ([vp, ctypes.POINTER(AlignStats)], ctypes.c_int),
         "starch_align_constants": ([ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+        "starch_gunzip_host": ([vp, ctypes.c_char_p, u64], ctypes.c_int),
+        "starch_gunzip_device": ([vp, vp, u64], ctypes.c_int),
+        "starch_gunzip_plan": ([ctypes.c_char_p, u64, ctypes.POINTER(GunzipMember), u64, pu64,
+                                ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
+        "starch_gunzip_get_stats": ([vp, ctypes.POINTER(GunzipStats)], ctypes.c_int),
+        "starch_gunzip_constants": ([ctypes.POINTER(ctypes.c_uint32)] * 4, ctypes.c_int),
+        "starch_is_gzip": ([ctypes.c_char_p, u64], ctypes.c_int),
         "starch_output_size": ([vp, pu64], ctypes.c_int),
         "starch_output_copy": ([vp, vp, u64], ctypes.c_int),
         "starch_output_device": ([vp, ctypes.POINTER(vp)], ctypes.c_int),
@@ -773,6 +793,26 @@ class Starch:
         """Of the last extract(): streams_total / streams_decoded /
         compressed_bytes_decoded / lines_scanned / lines_out."""
         return self._stats(ExtractStats, self._L.starch_extract_get_stats)
+
+    # ---- gzip and BGZF inputs ----
+    def gunzip(self, data: bytes) -> bytes:
+        """A gzip or BGZF file -> its bytes, inflated on the GPU with every
+        member's CRC-32 and ISIZE checked.  BGZF members are decoded all at
+        once, a wave each; a generic gzip member is decoded by one wave.  A bad
+        member is StarchError -12 naming its number, byte offset and the reason."""
+        _check(self._L.starch_gunzip_host(self._h, data, len(data)), self._h)
+        return self._output()
+
+    def gunzip_device(self, d_ptr: int, n: int) -> int:
+        """The same for bytes in HBM; returns the output size (output_device_ptr())."""
+        _check(self._L.starch_gunzip_device(self._h, ctypes.c_void_p(d_ptr), n), self._h)
+        return self._output_size()
+
+    def gunzip_stats(self) -> dict:
+        """Of the last inflate (gunzip(), or a gzip input of a BED method):
+        members / is_bgzf / stored_blocks / fixed_blocks / dynamic_blocks /
+        bytes_in / bytes_out / ms_plan / ms_upload / ms_size / ms_inflate / ms_crc."""
+        return self._stats(GunzipStats, self._L.starch_gunzip_get_stats)
 
     # ---- sort-bed ----
     def sort_bed(self, bed: bytes) -> bytes:
@@ -1162,6 +1202,31 @@ def _criterion(o, criterion):
         o.range = int(criterion[1])
     elif criterion[0] != "exact":
         o.frac_num, o.frac_digits = mapel_fraction(criterion[1])
+
+
+def is_gzip(data: bytes) -> bool:
+    """True for an input the BED methods take as gzip: at least 18 bytes that begin 1f 8b 08."""
+    return bool(load().starch_is_gzip(data, len(data)))
+
+
+def gunzip_plan(data: bytes):
+    """The plan of a gzip input from its headers; opens no GPU.  Returns
+    (is_bgzf, members): for BGZF the member table as dicts (in_off, in_len,
+    out_off, isize, crc), for generic gzip (False, [])."""
+    L = load()
+    n, bg = ctypes.c_uint64(), ctypes.c_int()
+    _check(L.starch_gunzip_plan(data, len(data), None, 0, ctypes.byref(n), ctypes.byref(bg)))
+    arr = (GunzipMember * max(1, n.value))()
+    if n.value:
+        _check(L.starch_gunzip_plan(data, len(data), arr, n.value, ctypes.byref(n), ctypes.byref(bg)))
+    return bool(bg.value), [_as_dict(arr[i]) for i in range(n.value)]
+
+
+def gunzip_constants():
+    """window_bytes (the LDS output ring), primary_bits (codes decoded by one
+    table lookup), copy_width (bytes of a match per round), bgzf_max."""
+    return dict(zip(("window_bytes", "primary_bits", "copy_width", "bgzf_max"),
+                    _constants(load().starch_gunzip_constants, 4)))
 
 
 def sort_constants():

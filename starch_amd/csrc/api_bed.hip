@@ -47,8 +47,15 @@ void sort_run(starch_ctx* c, const uint8_t* d, uint64_t n, bool check_only)
     if (check_only) return;
     publish(c, c->sort_out, r.out_bytes);
 }
-const uint8_t* sort_upload(starch_ctx* c, const void* bed, uint64_t n)
+// bed[0, n) into c->input; a gzip input is inflated there, and n becomes its inflated size
+const uint8_t* sort_upload(starch_ctx* c, const void* bed, uint64_t& n)
 {
+    if (gz::is_gzip(bed, n)) {
+        n = gunzip_plan(c, static_cast<const uint8_t*>(bed), n);
+        uint8_t* t = c->input.as<uint8_t>(n + 64);
+        gunzip_into(c, t);
+        return t;
+    }
     uint8_t* d = c->input.as<uint8_t>(n + 64);
     HostRegistration reg(bed, n, 256ull << 20);
     reg.h2d(d, bed, n, c->st);
@@ -72,7 +79,8 @@ int starch_sort_host(starch_ctx* c, const void* bed, uint64_t n)
 {
     GUARD(c)
     if (n && !bed) return STARCH_ERR_ARG;
-    sort_run(c, sort_upload(c, bed, n), n, false);
+    const uint8_t* d = sort_upload(c, bed, n);
+    sort_run(c, d, n, false);
     return STARCH_OK;
     END_GUARD(c)
 }
@@ -81,7 +89,8 @@ int starch_sort_check_host(starch_ctx* c, const void* bed, uint64_t n, uint64_t*
 {
     GUARD(c)
     if ((n && !bed) || !first_unsorted_line) return STARCH_ERR_ARG;
-    sort_run(c, sort_upload(c, bed, n), n, true);
+    const uint8_t* d = sort_upload(c, bed, n);
+    sort_run(c, d, n, true);
     *first_unsorted_line = c->sstats.first_unsorted_line;
     return STARCH_OK;
     END_GUARD(c)
@@ -94,7 +103,8 @@ int starch_sort_encode_host(starch_ctx* c, const void* bed, uint64_t n, const st
     const starch_options o = options_of(opt);
     if (!options_ok(o)) return STARCH_ERR_ARG;
     c->have = false;
-    sort_run(c, sort_upload(c, bed, n), n, false);
+    const uint8_t* d = sort_upload(c, bed, n);
+    sort_run(c, d, n, false);
     // the sorted text is in sort_out, which no encoder stage writes
     encode_device(c, c->out_dev, c->out_bytes, o);
     return STARCH_OK;
@@ -164,8 +174,8 @@ void setop_run(starch_ctx* c, const so::BedopsOptions& opt, uint64_t len, const 
     publish(c, c->setop_out, r.out_bytes);
 }
 
-// The inputs (BED text or archives, in host memory) back to back in c->setop_in,
-// each non-empty one ending in '\n'.  Returns the bytes; in_end: where each ends.
+// The inputs (BED text, archives or gzip / BGZF files of BED text, in host memory) back
+// to back in c->setop_in, each non-empty one ending in '\n'.  Returns the bytes; in_end: where each ends.
 uint64_t setop_load_host(starch_ctx* c, const starch_setop_input* inputs, uint64_t ninputs, const char* tool,
                          std::vector<uint64_t>& in_end, uint64_t* archives_out)
 {
@@ -187,6 +197,15 @@ uint64_t setop_load_host(starch_ctx* c, const starch_setop_input* inputs, uint64
                 HIP_CHECK(hipMemcpyAsync(d + len, c->ut_out.p, m, hipMemcpyDeviceToDevice, c->st));
                 HIP_CHECK(hipMemcpyAsync(&last, static_cast<const uint8_t*>(c->ut_out.p) + (m - 1), 1, hipMemcpyDeviceToHost,
                                          c->st));
+                HIP_CHECK(hipStreamSynchronize(c->st));
+            }
+        } else if (gz::is_gzip(a, n)) {
+            m = gunzip_plan(c, a, n);
+            want += m;
+            d = setop_reserve(c, len, want);
+            gunzip_into(c, d + len);
+            if (m) {
+                HIP_CHECK(hipMemcpyAsync(&last, d + len + (m - 1), 1, hipMemcpyDeviceToHost, c->st));
                 HIP_CHECK(hipStreamSynchronize(c->st));
             }
         } else if (n) {
@@ -781,7 +800,8 @@ int text_call(starch_ctx* c, const typename T::Options& opt, bool no_sort, const
     c->have_out = false;
     T::have(c) = false;
     const auto t0 = std::chrono::steady_clock::now();
-    text_run<T>(c, opt, no_sort, host ? sort_upload(c, data, n) : static_cast<const uint8_t*>(data), n, t0);
+    const uint8_t* d = host ? sort_upload(c, data, n) : static_cast<const uint8_t*>(data);
+    text_run<T>(c, opt, no_sort, d, n, t0);
     // the sorted text is in sort_out, which no encoder stage writes
     if (sopt) encode_device(c, c->out_dev, c->out_bytes, *sopt);
     return STARCH_OK;

@@ -1,6 +1,6 @@
 // starch_amd/csrc/api_int.hpp -- what the files behind the C ABI
 // (include/starch_amd.h) share: api_core.hip, api_archive.cpp, api_encode.hip,
-// api_stream.hip, api_decode.hip, api_cat.hip, api_bed.hip, and gather.hip for
+// api_stream.hip, api_decode.hip, api_cat.hip, api_bed.hip, api_gunzip.hip, and gather.hip for
 // the device guard.  Declarations only; each function names the file that
 // defines it.  Everything here has hidden visibility: none of it is a symbol
 // of the shared library.
@@ -116,6 +116,12 @@ void encode_device(starch_ctx* c, const uint8_t* d_bed, uint64_t n, const starch
 
 // ---- api_decode.hip ----
 uint64_t unstarch_to_ut_out(starch_ctx* c, const uint8_t* a, uint64_t n, const char* refuse_gzip);
+
+// ---- api_gunzip.hip: a gzip input of a host entry point ----
+// gz[0, n) (gz::is_gzip) copied to c->dec_in and planned; returns the inflated size
+uint64_t gunzip_plan(starch_ctx* c, const uint8_t* gz, uint64_t n);
+// the planned members inflated into d_out and checked; c->gstats filled
+void gunzip_into(starch_ctx* c, uint8_t* d_out);
 
 }  // namespace api
 #pragma GCC visibility pop

@@ -21,6 +21,7 @@
 #include "bz2.hpp"
 #include "bz2_decode.hpp"
 #include "gz.hpp"
+#include "gz_inflate.hpp"
 #include "sort_bed.hpp"
 #include "bed_setops.hpp"
 #include "bed_map.hpp"
@@ -249,6 +250,11 @@ struct starch_ctx {
     al::AlignWorkspace aligner;
     starch_align_stats astats{};     // the last starch_align_* call
     bool have_astats = false;
+    // gzip and BGZF inputs (gz_inflate.hip): the compressed bytes go to dec_in,
+    // the inflated ones where the caller wants the text
+    gz::Inflater inflater;
+    starch_gunzip_stats gstats{};    // the last inflate: starch_gunzip_*, or a gzip input of a BED command
+    bool have_gstats = false;
     std::string err;
     // last result
     bool have = false;

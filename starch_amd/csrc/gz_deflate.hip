@@ -28,6 +28,7 @@
 // A block is one deflate block (BFINAL on the segment's last), so blocks are
 // bit-contiguous and need no alignment; matches never cross a sub-chunk.
 #include "gz.hpp"
+#include "gz_crc.hpp"
 #include <atomic>
 
 #include <algorithm>
@@ -75,42 +76,14 @@ struct FixedTables {
     uint8_t len_extra[29];
     uint16_t dist_base[30];
     uint8_t dist_extra[30];
-    uint32_t x8pow[48];                        // x^(8 * 2^k) mod P (reflected CRC-32)
 };
 __constant__ FixedTables c_ft;
-__constant__ uint32_t c_crc_tab[256];          // reflected CRC-32 (poly 0xEDB88320), byte at a time
 
 uint32_t rev_bits(uint32_t v, int n)
 {
     uint32_t r = 0;
     for (int i = 0; i < n; ++i) r |= ((v >> i) & 1u) << (n - 1 - i);
     return r;
-}
-
-// GF(2) product of two CRC-32 register values (reflected: bit 31 is x^0)
-__host__ __device__ inline uint32_t gf_mul(uint32_t a, uint32_t b)
-{
-    uint32_t m = 1u << 31, p = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & m) p ^= b;
-        m >>= 1;
-        b = (b & 1u) ? (b >> 1) ^ 0xEDB88320u : b >> 1;
-    }
-    return p;
-}
-
-__device__ __forceinline__ uint32_t x8n(uint64_t n)   // x^(8n) mod P
-{
-    uint32_t r = 1u << 31;                     // x^0
-    for (int k = 0; n; ++k, n >>= 1)
-        if (n & 1u) r = gf_mul(r, c_ft.x8pow[k]);
-    return r;
-}
-
-// CRC register (init 0, no final xor) of A||B from those of A and B
-__device__ __forceinline__ uint32_t crc_cat(uint32_t ra, uint32_t rb, uint64_t len_b)
-{
-    return gf_mul(ra, x8n(len_b)) ^ rb;
 }
 
 __device__ __forceinline__ uint32_t len_sym(uint32_t L)   // 3..258 -> index 0..28 of the length codes
@@ -596,17 +569,8 @@ void upload_tables()
     std::copy(le, le + 29, ft.len_extra);
     std::copy(db, db + 30, ft.dist_base);
     std::copy(de, de + 30, ft.dist_extra);
-    // x^8 mod P, then squarings: x^(8 * 2^k)
-    uint32_t x8 = 1u << 23;                      // reflected x^8
-    for (int k = 0; k < 48; ++k) { ft.x8pow[k] = x8; x8 = gf_mul(x8, x8); }
-    uint32_t tab[256];
-    for (uint32_t i = 0; i < 256; ++i) {
-        uint32_t c = i;
-        for (int j = 0; j < 8; ++j) c = (c & 1u) ? (c >> 1) ^ 0xEDB88320u : c >> 1;
-        tab[i] = c;
-    }
     HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_ft), &ft, sizeof(ft)));
-    HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(c_crc_tab), tab, sizeof(tab)));
+    upload_crc_tables();
     done.fetch_or(bit);
 }
 
