@@ -9,7 +9,7 @@ CPPSRC := $(wildcard $(CSRC)/*.cpp)
 OBJS := $(patsubst $(CSRC)/%.hip,$(BUILD)/%.o,$(HIPSRC)) $(patsubst $(CSRC)/%.cpp,$(BUILD)/%.o,$(CPPSRC))
 HDRS := $(wildcard $(CSRC)/*.hpp) include/starch_amd.h include/starch_bzlib.h
 CLIS := starch3 unstarch starchcat sort-bed bedops bedmap closest-features convert2bed bedmap-elements bedmap-scores \
-	sam2bed psl2bed rmsk2bed starch-zcat
+	sam2bed psl2bed rmsk2bed starch-zcat bam2bed
 FLAGS := -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable --offload-arch=$(ARCH) $(EXTRA)
 
 all: $(BUILD)/libstarch_amd.so $(CLIS:%=$(BUILD)/%) $(BUILD)/starch3_hpp_example oracle

@@ -1244,6 +1244,105 @@ int starch_align_get_stats(starch_ctx* ctx, starch_align_stats* out);
  * whole wave. */
 int starch_align_constants(uint32_t* block_lines, uint32_t* wave_copy_bytes);
 
+/* ---- bam2bed: BAM records to BED, read through BGZF ---------------------------------
+ * The output for a BAM file B is, byte for byte, what starch_align_* with
+ * format sam and the same options writes for the SAM text of B, that is, for
+ * what  samtools view -h  prints: the definition of that text follows, the
+ * rules of sam2bed above then hold on it unchanged.  The compressed bytes are
+ * inflated in HBM, the records are found and formatted there, and the lines go
+ * on to the sort and the encoder from there.  The points that are believed but
+ * unverified against samtools or BEDOPS are marked (*).
+ * Input.  An input that starch_is_gzip accepts is inflated as the gzip section
+ * below says (BGZF wide, generic gzip serially; its errors are those of that
+ * section).  An input that begins BAM\1 is taken as already inflated.  Anything
+ * else is STARCH_ERR_DATA, and so is an inflated input that does not begin
+ * BAM\1.  A missing BGZF EOF marker is not an error.
+ * Header.  BAM\1, l_text (u32), the text, n_ref (u32), then per reference
+ * l_name (u32), the NUL-terminated name and l_ref (u32); all little-endian.  A
+ * truncated header, a name that is not NUL-terminated and an l_name of 0 are
+ * STARCH_ERR_DATA.  The header lines are the lines of the text with its
+ * trailing NUL bytes dropped, cut at '\n'; a last line without '\n' is a line.
+ * They are dropped, or with keep_header written as _header lines exactly as
+ * sam2bed writes them (an empty line is a header line there too).
+ * Records.  A record is block_size (u32) and then block_size bytes, with
+ * block_size >= 32: refID, pos (i32), l_read_name, mapq (u8), bin, n_cigar_op,
+ * flag (u16), l_seq (u32), next_refID, next_pos, tlen (i32), the read name, the
+ * CIGAR (u32 each: count << 4 | operator), SEQ (4 bits a base), QUAL, the tags.
+ * The record must hold what its own counts announce: 32 + l_read_name +
+ * 4 * n_cigar_op + (l_seq + 1) / 2 + l_seq <= block_size.  l_read_name >= 1 and
+ * the name ends in NUL.  refID and next_refID lie in [-1, n_ref).  CIGAR
+ * operators are 0 to 8.  The tag area parses exactly to the record's end: a tag
+ * is two bytes, a type of A c C s S i I f Z H B and its value; B is a subtype of
+ * c C s S i I f, a count (u32) and the elements; Z and H end in NUL inside the
+ * record.  The chain of records must end exactly at the end of the input.  Any
+ * violation is STARCH_ERR_DATA with the text
+ *   bam2bed: record N: <what is wrong>
+ * where N counts from 1 and the lowest bad record is named; nothing is written.
+ * Every record is checked, a dropped one too.
+ * SAM text of a record (SAM specification section 4.2).  QNAME (the name
+ * without its NUL) and FLAG as written.  RNAME is the reference name, or * for
+ * -1.  POS is pos + 1, MAPQ as written.  CIGAR is counts and MIDNSHP=X, or * when
+ * there are no operators.  RNEXT is * for -1, = when it equals a non-negative
+ * refID, otherwise the name.  PNEXT is next_pos + 1; TLEN is signed.  SEQ comes
+ * from =ACMGRSVTWYHKDBN, or * when l_seq = 0.  QUAL is each byte plus 33, or *
+ * when l_seq = 0 or the first byte is 0xFF.  Each tag is TG:t:value: A as its
+ * byte, all six integer types as i: and a signed decimal, Z and H as their
+ * bytes, B as B:s,v,v,...  An f value is C's %g of the float32 (6 significant
+ * digits, trailing zeros stripped, exponent form below 1e-4 and from 1e6 up),
+ * computed exactly in integer arithmetic on mantissa and exponent, with no
+ * floating-point instruction, for every bit pattern; (*) infinities and NaNs
+ * print inf, -inf and nan (a NaN of either sign).  The long-CIGAR convention is
+ * honoured: when n_cigar_op = 2, the first operator is <l_seq>S, the second is N
+ * and a CG:B:I tag is present, the first such tag's array is the CIGAR and that
+ * tag is not printed.  (*) The name and the tag values are copied as they are:
+ * a TAB, a newline or a NUL inside them is not escaped.
+ * Semantics.  On that text the rules of sam2bed hold: the unmapped rule and
+ * all_reads; stop = POS-1 + max(1, reference length); reduced, split and
+ * split_deletions; a mapped record with refID -1 (or (*) a reference whose name
+ * is empty or *) or with pos < 0 is bad, in sam2bed's words.  With reduced,
+ * nothing after column 6 is formatted.
+ * Framing (bed_bam.hip): tile t of the framing is the bytes
+ * [t * T, (t + 1) * T) of the inflated file, header included.
+ * 2^32 records or more, or 2^32 output lines or more, is STARCH_ERR_ARG.  A NULL
+ * context or options, split_deletions without split, and no_sort with
+ * starch_bam_encode_host are STARCH_ERR_ARG, answered before anything touches a
+ * device. */
+typedef struct {
+    uint32_t split;             /* a line per run of M D = X */
+    uint32_t split_deletions;   /* with split: D ends a run too */
+    uint32_t all_reads;         /* unmapped records become _unmapped lines */
+    uint32_t reduced;           /* the first six columns only */
+    uint32_t keep_header;       /* header lines become _header lines */
+    uint32_t no_sort;           /* leave the lines in input order */
+} starch_bam_options;
+/* BAM bytes in host memory, compressed (BGZF, gzip) or not.  The BED is read
+ * through starch_output_size / _copy / _device. */
+int starch_bam_host(starch_ctx* ctx, const void* data, uint64_t n, const starch_bam_options* opt);
+/* INFLATED BAM (it begins BAM\1) in HBM. */
+int starch_bam_device(starch_ctx* ctx, const void* d_data, uint64_t n, const starch_bam_options* opt);
+/* Convert, sort (bopt->no_sort is STARCH_ERR_ARG) and encode from the sorted bytes
+ * while they are in HBM, as starch_align_encode_host does.  sopt == NULL: the
+ * defaults. */
+int starch_bam_encode_host(starch_ctx* ctx, const void* data, uint64_t n, const starch_bam_options* bopt,
+                           const starch_options* sopt);
+typedef struct {
+    uint64_t input_bytes, inflated_bytes;
+    uint64_t references, header_lines, records;   /* records: the unmapped ones too */
+    uint64_t unmapped_dropped;                    /* records left out for FLAG bit 4 */
+    uint64_t tiles;                               /* of the framing */
+    uint64_t wave_records;                        /* records whose l_seq or largest B count reaches the wave threshold */
+    uint64_t lines_out, output_bytes;
+    uint64_t sorted;                              /* 1: the sort ran */
+    /* GPU events (ms_frame holds the header's round trip); ms_total is host clock and holds the upload too */
+    float ms_inflate, ms_frame, ms_parse, ms_write, ms_sort, ms_total;
+} starch_bam_stats;
+/* Of the last successful starch_bam_* call on this context. */
+int starch_bam_get_stats(starch_ctx* ctx, starch_bam_stats* out);
+/* Sizes the kernels switch on: the bytes T of a framing tile, the threads per
+ * block of the per-record kernels (one record each), and the l_seq or B count W
+ * from which a record's SEQ, QUAL and arrays are left to a whole wave. */
+int starch_bam_constants(uint32_t* tile_bytes, uint32_t* block_records, uint32_t* wave_threshold);
+
 /* ---- gzip and BGZF inputs: inflate on the GPU (gz_inflate.hip) ----
  * An input of at least 18 bytes that begins 1f 8b 08 is gzip: one or more
  * RFC 1952 members back to back.  When every member carries the BC extra

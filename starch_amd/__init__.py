@@ -22,7 +22,8 @@ __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_arc
            "mapel_constants", "mapel_fraction", "MAPEL_COLS", "MAPEL_CRITERIA", "MapelOptions", "MapelStats",
            "mapsc_constants", "MAPSC_COLS", "MapscOptions", "MapscStats",
            "convert_constants", "CONVERT_FORMATS", "VCF_CLASSES", "ConvertOptions", "ConvertStats",
-           "align_constants", "ALIGN_FORMATS", "AlignOptions", "AlignStats"]
+           "align_constants", "ALIGN_FORMATS", "AlignOptions", "AlignStats",
+           "bam_constants", "BamOptions", "BamStats"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STARCH_AMD_LIB") or os.path.join(_HERE, "_build", "libstarch_amd.so")
@@ -254,6 +255,19 @@ class AlignStats(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("ms_frame", "ms_parse", "ms_write", "ms_sort", "ms_total")]
 
 
+class BamOptions(ctypes.Structure):
+    """starch_bam_options: the flags of bam2bed()."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("split", "split_deletions", "all_reads", "reduced", "keep_header", "no_sort")]
+
+
+class BamStats(ctypes.Structure):
+    """starch_bam_stats: the last bam2bed()."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("input_bytes", "inflated_bytes", "references", "header_lines", "records",
+                                               "unmapped_dropped", "tiles", "wave_records", "lines_out", "output_bytes",
+                                               "sorted")] + \
+               [(n, ctypes.c_float) for n in ("ms_inflate", "ms_frame", "ms_parse", "ms_write", "ms_sort", "ms_total")]
+
+
 class SortStats(ctypes.Structure):
     """starch_sort_stats: the last sort_bed / sort_check / compress_sorted."""
     _fields_ = [(n, ctypes.c_uint64) for n in ("input_bytes", "n_lines", "n_chromosomes", "already_sorted",
@@ -419,6 +433,11 @@ def load():
                                      ctypes.c_int),
         "starch_align_get_stats": ([vp, ctypes.POINTER(AlignStats)], ctypes.c_int),
         "starch_align_constants": ([ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
+        "starch_bam_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(BamOptions)], ctypes.c_int),
+        "starch_bam_device": ([vp, vp, u64, ctypes.POINTER(BamOptions)], ctypes.c_int),
+        "starch_bam_encode_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(BamOptions), ctypes.POINTER(Options)], ctypes.c_int),
+        "starch_bam_get_stats": ([vp, ctypes.POINTER(BamStats)], ctypes.c_int),
+        "starch_bam_constants": ([ctypes.POINTER(ctypes.c_uint32)] * 3, ctypes.c_int),
         "starch_gunzip_host": ([vp, ctypes.c_char_p, u64], ctypes.c_int),
         "starch_gunzip_device": ([vp, vp, u64], ctypes.c_int),
         "starch_gunzip_plan": ([ctypes.c_char_p, u64, ctypes.POINTER(GunzipMember), u64, pu64,
@@ -1117,6 +1136,42 @@ class Starch:
         records / unmapped_dropped / lines_out / output_bytes / sorted / ms_*."""
         return self._stats(AlignStats, self._L.starch_align_get_stats)
 
+    # ---- bam2bed ----
+    def bam2bed(self, data: bytes, split=False, split_deletions=False, all_reads=False, reduced=False, keep_header=False,
+                sort=True) -> bytes:
+        """bam2bed: BAM (BGZF, any other gzip file of the same bytes, or
+        inflated BAM) -> the BED that align2bed(..., "sam") with the same
+        options gives for the file's SAM text, in sort_bed()'s order unless
+        ``sort`` is False.  The bytes are inflated, cut into records and
+        formatted in HBM; the definition is in include/starch_amd.h.  A record
+        that does not fit it is StarchError -12 naming its number; a bad
+        argument is -2."""
+        o = _bam_options(split, split_deletions, all_reads, reduced, keep_header, sort)
+        _check(self._L.starch_bam_host(self._h, data, len(data), ctypes.byref(o)), self._h)
+        return self._output()
+
+    def bam2bed_device(self, d_ptr: int, n: int, split=False, split_deletions=False, all_reads=False, reduced=False,
+                       keep_header=False, sort=True) -> int:
+        """The same for INFLATED BAM in HBM; returns the output size (output_device_ptr())."""
+        o = _bam_options(split, split_deletions, all_reads, reduced, keep_header, sort)
+        _check(self._L.starch_bam_device(self._h, ctypes.c_void_p(d_ptr), n, ctypes.byref(o)), self._h)
+        return self._output_size()
+
+    def compress_bam(self, data: bytes, split=False, split_deletions=False, all_reads=False, reduced=False, keep_header=False,
+                     emit_index=True) -> bytes:
+        """bam2bed, sort and compress without leaving HBM: the archive
+        compress(bam2bed(data, ...)) gives."""
+        o = _bam_options(split, split_deletions, all_reads, reduced, keep_header, True)
+        so = self._opts(emit_index)
+        _check(self._L.starch_bam_encode_host(self._h, data, len(data), ctypes.byref(o), ctypes.byref(so)), self._h)
+        return self.archive()
+
+    def bam_stats(self) -> dict:
+        """Of the last bam2bed(): input_bytes / inflated_bytes / references /
+        header_lines / records / unmapped_dropped / tiles / wave_records /
+        lines_out / output_bytes / sorted / ms_*."""
+        return self._stats(BamStats, self._L.starch_bam_get_stats)
+
     def cat(self, archives) -> bytes:
         """starchcat: the archives (bytes, in order) merged into one, with this
         instance's note, block_size_100k and base_counts.  A chromosome held
@@ -1402,6 +1457,18 @@ def _align_options(fmt, split, split_deletions, all_reads, reduced, keep_header,
         raise ValueError("align2bed: fmt must be one of %s" % ", ".join(ALIGN_FORMATS))
     return AlignOptions(ALIGN_FORMATS[fmt], bool(split), bool(split_deletions), bool(all_reads), bool(reduced),
                         bool(keep_header), not sort)
+
+
+def bam_constants():
+    """(bytes of a tile of bam2bed's framing, threads per block of its
+    per-record kernels, the l_seq or B count from which a record's columns are
+    left to a whole wave); no GPU needed."""
+    return _constants(load().starch_bam_constants, 3)
+
+
+def _bam_options(split, split_deletions, all_reads, reduced, keep_header, sort):
+    """starch_bam_options; the combination of the flags is left to the library."""
+    return BamOptions(bool(split), bool(split_deletions), bool(all_reads), bool(reduced), bool(keep_header), not sort)
 
 
 def _cat_args(archives):

@@ -1,5 +1,5 @@
 // starch_amd/csrc/api_bed.hip -- the C ABI of sort-bed, bedops, bedmap, closest-features, bedmap-elements,
-// bedmap-scores, convert2bed, sam2bed, psl2bed and rmsk2bed.  The four two-input tools go through pair_host,
+// bedmap-scores, convert2bed, sam2bed, psl2bed, rmsk2bed and bam2bed.  The four two-input tools go through pair_host,
 // pair_device and pair_get_stats, the converters through text_call; a tool keeps its option check, its
 // constants and the stats fields that are its own.
 #include <string.h>
@@ -949,6 +949,115 @@ int starch_align_constants(uint32_t* block_lines, uint32_t* wave_copy_bytes)
 {
     if (block_lines) *block_lines = (uint32_t)al::kThreads;
     if (wave_copy_bytes) *wave_copy_bytes = sb::kWaveCopyBytes;
+    return STARCH_OK;
+}
+
+}  // extern "C"
+
+// ---- bam2bed (include/starch_amd.h; kernels in bed_bam.hip) -----------------------------
+namespace {
+bool bam_options_ok(const starch_bam_options* o, bam::BamOptions* out)
+{
+    if (!o || (o->split_deletions && !o->split)) return false;
+    out->split = o->split ? 1 : 0;
+    out->split_deletions = o->split_deletions ? 1 : 0;
+    out->all_reads = o->all_reads ? 1 : 0;
+    out->reduced = o->reduced ? 1 : 0;
+    out->keep_header = o->keep_header ? 1 : 0;
+    return true;
+}
+
+// The checked call: BAM bytes in host memory (compressed or not), or inflated
+// BAM in HBM (host false); converted into setop_out and, unless no_sort, sorted
+// from there into sort_out; sopt: encode the sorted result with it.
+int bam_call(starch_ctx* c, const bam::BamOptions& opt, bool no_sort, const void* data, uint64_t n, bool host, const starch_options* sopt)
+{
+    GUARD(c)
+    if (sopt) c->have = false;
+    c->have_out = false;
+    c->have_bstats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t input_bytes = n;
+    const uint8_t* d = static_cast<const uint8_t*>(data);
+    float ms_inflate = 0;
+    if (host) {
+        const bool gzip = gz::is_gzip(data, n);
+        if (!gzip && !(n >= 4 && memcmp(data, "BAM\1", 4) == 0))
+            throw StarchError(STARCH_ERR_DATA, "bam2bed: the input is neither gzip nor BAM (it does not begin BAM\\1)");
+        d = sort_upload(c, data, n);   // a gzip input is inflated in HBM; n becomes its inflated size
+        if (gzip) ms_inflate = c->gstats.ms_size + c->gstats.ms_inflate + c->gstats.ms_crc;
+    }
+    bam::BamResult r;
+    c->bammer.run(opt, d, n, c->st, c->setop_out, r);
+    starch_bam_stats& s = c->bstats;
+    s = starch_bam_stats{};
+    s.input_bytes = input_bytes;
+    s.inflated_bytes = n;
+    s.references = r.references;
+    s.header_lines = r.header_lines;
+    s.records = r.records;
+    s.unmapped_dropped = r.unmapped_dropped;
+    s.tiles = r.tiles;
+    s.wave_records = r.wave_records;
+    s.lines_out = r.lines_out;
+    s.output_bytes = r.out_bytes;
+    s.ms_inflate = ms_inflate;
+    s.ms_frame = r.ms_frame;
+    s.ms_parse = r.ms_parse;
+    s.ms_write = r.ms_write;
+    if (no_sort) publish(c, c->setop_out, r.out_bytes);
+    else {
+        sort_run(c, static_cast<const uint8_t*>(c->setop_out.p), r.out_bytes, false);
+        s.sorted = 1;
+        s.ms_sort = c->sstats.ms_total;
+    }
+    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->have_bstats = true;
+    // the sorted text is in sort_out, which no encoder stage writes
+    if (sopt) encode_device(c, c->out_dev, c->out_bytes, *sopt);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+}  // namespace
+
+extern "C" {
+
+int starch_bam_device(starch_ctx* c, const void* d_data, uint64_t n, const starch_bam_options* opt)
+{
+    bam::BamOptions bo;
+    if (!c || !bam_options_ok(opt, &bo) || (n && !d_data)) return STARCH_ERR_ARG;
+    return bam_call(c, bo, opt->no_sort != 0, d_data, n, false, nullptr);
+}
+
+int starch_bam_host(starch_ctx* c, const void* data, uint64_t n, const starch_bam_options* opt)
+{
+    bam::BamOptions bo;
+    if (!c || !bam_options_ok(opt, &bo) || (n && !data)) return STARCH_ERR_ARG;
+    return bam_call(c, bo, opt->no_sort != 0, data, n, true, nullptr);
+}
+
+int starch_bam_encode_host(starch_ctx* c, const void* data, uint64_t n, const starch_bam_options* bopt, const starch_options* sopt)
+{
+    bam::BamOptions bo;
+    if (!c || !bam_options_ok(bopt, &bo) || bopt->no_sort || (n && !data)) return STARCH_ERR_ARG;
+    const starch_options o = options_of(sopt);
+    if (!options_ok(o)) return STARCH_ERR_ARG;
+    return bam_call(c, bo, false, data, n, true, &o);
+}
+
+int starch_bam_get_stats(starch_ctx* c, starch_bam_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_bstats) return STARCH_ERR_STATE;
+    *out = c->bstats;
+    return STARCH_OK;
+}
+
+int starch_bam_constants(uint32_t* tile_bytes, uint32_t* block_records, uint32_t* wave_threshold)
+{
+    if (tile_bytes) *tile_bytes = bam::kTileBytes;
+    if (block_records) *block_records = (uint32_t)bam::kThreads;
+    if (wave_threshold) *wave_threshold = bam::kWaveThreshold;
     return STARCH_OK;
 }
 

@@ -29,6 +29,7 @@
 #include "bed_mapel.hpp"
 #include "bed_mapscore.hpp"
 #include "bed_align.hpp"
+#include "bed_bam.hpp"
 #include "bed_convert.hpp"
 #include "transform.hpp"
 #include "untransform.hpp"
@@ -250,6 +251,10 @@ struct starch_ctx {
     al::AlignWorkspace aligner;
     starch_align_stats astats{};     // the last starch_align_* call
     bool have_astats = false;
+    // bam2bed (bed_bam.hip): reads input (inflated there) or the caller's HBM, writes setop_out
+    bam::BamWorkspace bammer;
+    starch_bam_stats bstats{};       // the last starch_bam_* call
+    bool have_bstats = false;
     // gzip and BGZF inputs (gz_inflate.hip): the compressed bytes go to dec_in,
     // the inflated ones where the caller wants the text
     gz::Inflater inflater;

@@ -1,8 +1,9 @@
-// tools/align2bed_cli.hpp -- what the `sam2bed`, `psl2bed` and `rmsk2bed` commands
-// share: text (a file or stdin) converted to BED on the GPU (starch_align_host),
-// by default in sort-bed's order, to stdout; --output=starch writes the archive
-// starch3 writes for that sorted BED (starch_align_encode_host).  A command
-// names its format, the format options it takes and its help.
+// tools/align2bed_cli.hpp -- what the `sam2bed`, `psl2bed`, `rmsk2bed` and `bam2bed`
+// commands share: an input (a file or stdin) converted to BED on the GPU
+// (starch_align_host, starch_bam_host), by default in sort-bed's order, to
+// stdout; --output=starch writes the archive starch3 writes for that sorted BED
+// (starch_align_encode_host, starch_bam_encode_host).  A command names its
+// format, the format options it takes and its help.
 //
 // Exit codes as convert2bed (tools/convert2bed_cli.cpp): 2 for a bad command line
 // or an option the command does not have (answered before a GPU is opened),
@@ -25,7 +26,10 @@ struct Command {
 static const char* kVersion = "0.1 (mi355x)";
 static const int kUsageError = 2;
 
-static int run(const Command& which, int argc, char** argv)
+// opt: the command's options (starch_align_options with its format set, or
+// starch_bam_options); host and encode: the library calls that take them
+template <class Options, class Host, class Encode>
+static int run_with(const Command& which, Options& opt, Host host, Encode encode, int argc, char** argv)
 {
     enum { O_OUTPUT = 256, O_NOSORT, O_KEEP, O_SPLIT, O_SPLITDEL, O_ALL, O_REDUCED };
     static struct option longs[] = {{"output", required_argument, nullptr, O_OUTPUT},
@@ -38,9 +42,6 @@ static int run(const Command& which, int argc, char** argv)
                                     CLI_COMMON_OPTIONS,
                                     {nullptr, 0, nullptr, 0}};
     const cli::Command cmd = {which.name, kVersion, which.help, kUsageError};
-    starch_align_options opt;
-    memset(&opt, 0, sizeof opt);
-    opt.format = which.format;
     int device = 0;
     bool starch = false;
     opterr = 0;
@@ -61,7 +62,15 @@ static int run(const Command& which, int argc, char** argv)
         }
         if (e != cli::GO_ON) return e;
     }
-    return cli::run_converter(cmd, argc, argv, device, starch, starch_align_host, starch_align_encode_host, &opt);
+    return cli::run_converter(cmd, argc, argv, device, starch, host, encode, &opt);
+}
+
+static int run(const Command& which, int argc, char** argv)
+{
+    starch_align_options opt;
+    memset(&opt, 0, sizeof opt);
+    opt.format = which.format;
+    return run_with(which, opt, starch_align_host, starch_align_encode_host, argc, argv);
 }
 
 }  // namespace align_cli
