@@ -1343,6 +1343,75 @@ int starch_bam_get_stats(starch_ctx* ctx, starch_bam_stats* out);
  * from which a record's SEQ, QUAL and arrays are left to a whole wave. */
 int starch_bam_constants(uint32_t* tile_bytes, uint32_t* block_records, uint32_t* wave_threshold);
 
+/* ---- bigWig and bigBed files: header, chromosomes and block table (bed_bbi.hip) ------
+ * The host's reading of a bigWig / bigBed file: what a converter needs before it
+ * touches a block.  No context and no GPU.  Modelled on UCSC's bbiFile layout;
+ * unverified against UCSC's tools: what follows is the definition.  Only
+ * full-resolution data is described; zoom levels, autoSql and the total summary
+ * are skipped.
+ * File.  All integers are little-endian; a file whose magic reads right only
+ * byte-swapped is refused ("big-endian bigWig/bigBed is not supported").  Header
+ * (64 bytes): magic u32 (0x888FFC26 bigWig, 0x8789F2EB bigBed), version u16,
+ * zoomLevels u16, chromosomeTreeOffset, fullDataOffset, fullIndexOffset u64,
+ * fieldCount, definedFieldCount u16, autoSqlOffset, totalSummaryOffset u64,
+ * uncompressBufSize u32 (0: the blocks are not compressed), reserved u64.
+ * Chromosome B+ tree at chromosomeTreeOffset: magic 0x78CA8C91, blockSize,
+ * keySize, valSize (8) u32, itemCount, reserved u64; nodes are isLeaf u8,
+ * reserved u8, count u16 and count items: key[keySize] then chromId, chromSize
+ * u32 (leaf) or childOffset u64 (inner).  Ids are exactly 0..itemCount-1, each
+ * once; a name is the key up to its first zero byte, not empty, without TAB or
+ * newline.  R-tree at fullIndexOffset: a 48-byte header (magic 0x2468ACE0,
+ * blockSize u32, itemCount u64, four u32 bounds, endFileOffset u64, itemsPerSlot,
+ * reserved u32); nodes as above with leaf items startChromIx, startBase,
+ * endChromIx, endBase u32, dataOffset, dataSize u64 and inner items the same four
+ * u32 and childOffset u64.  The leaf items, ordered by dataOffset, are the block
+ * table: blocks lie inside [fullDataOffset, fullIndexOffset), do not overlap and
+ * have fewer than 2^32 bytes.  Both trees are walked with an explicit stack;
+ * every offset and count is checked against the file size before use and a node
+ * reached twice is an error.  The nodes of a tree are disjoint, so the bytes of
+ * the nodes a walk visits (4 + count items each) may not exceed the file size:
+ * a walk ends on any input, and its time and memory are bounded by the file's
+ * bytes.
+ * Region.  A chromosome, whole or [start, end) with start < end, chooses the
+ * blocks whose R-tree box meets it: (startChromIx, startBase) < (id, end) and
+ * (endChromIx, endBase) > (id, start), compared as pairs.  A chromosome the file
+ * lacks chooses none.
+ * Errors.  A malformed file is STARCH_ERR_DATA with the reason  bbi: <reason> .
+ * A NULL header, a kind above 2, a region without a name and a range with
+ * start >= end are STARCH_ERR_ARG; a forced kind that is not the file's is
+ * STARCH_ERR_DATA. */
+#define STARCH_BBI_AUTO 0
+#define STARCH_BBI_BIGWIG 1
+#define STARCH_BBI_BIGBED 2
+typedef struct {
+    uint32_t kind;              /* STARCH_BBI_*: AUTO takes the magic's word */
+    uint32_t region;            /* 0: everything; 1: the chromosome; 2: [start, end) of it */
+    const char* chrom;          /* region: the name, chrom_len bytes */
+    uint64_t chrom_len;
+    uint64_t start, end;
+} starch_bbi_query;
+typedef struct {
+    uint32_t kind, version, zoom_levels, field_count, defined_field_count, uncompress_buf_size;
+    uint64_t chrom_tree_offset, full_data_offset, full_index_offset;
+    uint64_t n_chroms, names_bytes;               /* names_bytes: all names, each with its NUL */
+    uint64_t n_blocks;                            /* of the whole table */
+    uint64_t n_selected;                          /* blocks the query's region needs (all without one) */
+} starch_bbi_header;
+typedef struct {
+    uint32_t start_chrom, start_base, end_chrom, end_base;
+    uint64_t data_offset, data_size;
+} starch_bbi_block;
+/* hdr is always filled on success.  chrom_sizes[0, chrom_cap) and names[0,
+ * names_cap) receive the sizes by chromId and the NUL-terminated names back to
+ * back; blocks[0, block_cap) the blocks q's region needs (q may be NULL: all), in
+ * table order, and block_index (may be NULL) their indices in the table.  A
+ * short buffer is STARCH_ERR_MEM with hdr filled; NULL buffers with capacity 0
+ * only fill hdr.  STARCH_ERR_DATA leaves the reason in err[0, err_cap) (may be
+ * NULL). */
+int starch_bbi_info(const void* data, uint64_t n, const starch_bbi_query* q, starch_bbi_header* hdr, uint32_t* chrom_sizes,
+                    uint64_t chrom_cap, char* names, uint64_t names_cap, starch_bbi_block* blocks, uint64_t* block_index,
+                    uint64_t block_cap, char* err, uint64_t err_cap);
+
 /* ---- gzip and BGZF inputs: inflate on the GPU (gz_inflate.hip) ----
  * An input of at least 18 bytes that begins 1f 8b 08 is gzip: one or more
  * RFC 1952 members back to back.  When every member carries the BC extra

@@ -23,7 +23,8 @@ __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_arc
            "mapsc_constants", "MAPSC_COLS", "MapscOptions", "MapscStats",
            "convert_constants", "CONVERT_FORMATS", "VCF_CLASSES", "ConvertOptions", "ConvertStats",
            "align_constants", "ALIGN_FORMATS", "AlignOptions", "AlignStats",
-           "bam_constants", "BamOptions", "BamStats"]
+           "bam_constants", "BamOptions", "BamStats",
+           "bbi_info", "BBI_KINDS", "BbiQuery", "BbiHeader", "BbiBlock"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STARCH_AMD_LIB") or os.path.join(_HERE, "_build", "libstarch_amd.so")
@@ -268,6 +269,29 @@ class BamStats(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("ms_inflate", "ms_frame", "ms_parse", "ms_write", "ms_sort", "ms_total")]
 
 
+BBI_KINDS = {"auto": 0, "bigwig": 1, "bigbed": 2}                               # STARCH_BBI_*
+
+
+class BbiQuery(ctypes.Structure):
+    """starch_bbi_query: the kind and region of bbi_info()."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("kind", "region")] + \
+               [("chrom", ctypes.c_char_p)] + [(n, ctypes.c_uint64) for n in ("chrom_len", "start", "end")]
+
+
+class BbiHeader(ctypes.Structure):
+    """starch_bbi_header: what bbi_info() reads of a file's header and trees."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("kind", "version", "zoom_levels", "field_count", "defined_field_count",
+                                               "uncompress_buf_size")] + \
+               [(n, ctypes.c_uint64) for n in ("chrom_tree_offset", "full_data_offset", "full_index_offset", "n_chroms",
+                                               "names_bytes", "n_blocks", "n_selected")]
+
+
+class BbiBlock(ctypes.Structure):
+    """starch_bbi_block: a leaf item of the R-tree."""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("start_chrom", "start_base", "end_chrom", "end_base")] + \
+               [(n, ctypes.c_uint64) for n in ("data_offset", "data_size")]
+
+
 class SortStats(ctypes.Structure):
     """starch_sort_stats: the last sort_bed / sort_check / compress_sorted."""
     _fields_ = [(n, ctypes.c_uint64) for n in ("input_bytes", "n_lines", "n_chromosomes", "already_sorted",
@@ -438,6 +462,9 @@ def load():
         "starch_bam_encode_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(BamOptions), ctypes.POINTER(Options)], ctypes.c_int),
         "starch_bam_get_stats": ([vp, ctypes.POINTER(BamStats)], ctypes.c_int),
         "starch_bam_constants": ([ctypes.POINTER(ctypes.c_uint32)] * 3, ctypes.c_int),
+        "starch_bbi_info": ([ctypes.c_char_p, u64, ctypes.POINTER(BbiQuery), ctypes.POINTER(BbiHeader),
+                             ctypes.POINTER(ctypes.c_uint32), u64, vp, u64, ctypes.POINTER(BbiBlock), pu64, u64, vp, u64],
+                            ctypes.c_int),
         "starch_gunzip_host": ([vp, ctypes.c_char_p, u64], ctypes.c_int),
         "starch_gunzip_device": ([vp, vp, u64], ctypes.c_int),
         "starch_gunzip_plan": ([ctypes.c_char_p, u64, ctypes.POINTER(GunzipMember), u64, pu64,
@@ -1469,6 +1496,49 @@ def bam_constants():
 def _bam_options(split, split_deletions, all_reads, reduced, keep_header, sort):
     """starch_bam_options; the combination of the flags is left to the library."""
     return BamOptions(bool(split), bool(split_deletions), bool(all_reads), bool(reduced), bool(keep_header), not sort)
+
+
+def _bbi_query(kind, region):
+    """starch_bbi_query; region: None, a name or (name, start, end).  The structure keeps the name alive."""
+    o = BbiQuery(BBI_KINDS[kind], 0, None, 0, 0, 0)
+    if region is not None:
+        name = region if isinstance(region, (bytes, str)) else region[0]
+        name = name.encode() if isinstance(name, str) else bytes(name)
+        o.region, o.chrom, o.chrom_len = (1 if isinstance(region, (bytes, str)) else 2), name, len(name)
+        if o.region == 2:
+            o.start, o.end = int(region[1]), int(region[2])
+    return o
+
+
+def bbi_info(data: bytes, region=None) -> dict:
+    """What the host reads of a bigWig / bigBed file; opens no GPU.  kind
+    ("bigwig" or "bigbed"), version, uncompress_buf_size and the other header
+    fields, chroms [(name, size)] by chromId, n_blocks, and blocks: the
+    blocks ``region`` needs (all without one) as dicts with their index in the
+    block table.  A malformed file is StarchError -12 with the reason."""
+    L = load()
+    o = _bbi_query("auto", region)
+    h = BbiHeader()
+    err = ctypes.create_string_buffer(512)
+
+    def call(sizes, ncap, names, mcap, blocks, index, bcap):
+        rc = L.starch_bbi_info(data, len(data), ctypes.byref(o), ctypes.byref(h), sizes, ncap, names, mcap, blocks, index, bcap,
+                               err, len(err))
+        if rc != 0:
+            raise StarchError(rc, (L.starch_strerror(rc) or b"").decode() + ": " + err.value.decode(errors="replace"))
+
+    call(None, 0, None, 0, None, None, 0)
+    sizes = (ctypes.c_uint32 * max(1, h.n_chroms))()
+    names = ctypes.create_string_buffer(max(1, h.names_bytes))
+    blocks = (BbiBlock * max(1, h.n_selected))()
+    index = (ctypes.c_uint64 * max(1, h.n_selected))()
+    call(sizes, h.n_chroms, names, h.names_bytes, blocks, index, h.n_selected)
+    out = _as_dict(h)
+    out["kind"] = {1: "bigwig", 2: "bigbed"}[h.kind]
+    nm = names.raw[:h.names_bytes].split(b"\0")[:h.n_chroms]
+    out["chroms"] = [(nm[k], sizes[k]) for k in range(h.n_chroms)]
+    out["blocks"] = [dict(_as_dict(blocks[k]), index=index[k]) for k in range(h.n_selected)]
+    return out
 
 
 def _cat_args(archives):

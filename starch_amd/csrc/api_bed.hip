@@ -1,5 +1,5 @@
 // starch_amd/csrc/api_bed.hip -- the C ABI of sort-bed, bedops, bedmap, closest-features, bedmap-elements,
-// bedmap-scores, convert2bed, sam2bed, psl2bed, rmsk2bed and bam2bed.  The four two-input tools go through pair_host,
+// bedmap-scores, convert2bed, sam2bed, psl2bed, rmsk2bed and bam2bed, and starch_bbi_info.  The four two-input tools go through pair_host,
 // pair_device and pair_get_stats, the converters through text_call; a tool keeps its option check, its
 // constants and the stats fields that are its own.
 #include <string.h>
@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "api_int.hpp"
+#include "bed_bbi.hpp"
 
 using namespace api;
 
@@ -1059,6 +1060,81 @@ int starch_bam_constants(uint32_t* tile_bytes, uint32_t* block_records, uint32_t
     if (block_records) *block_records = (uint32_t)bam::kThreads;
     if (wave_threshold) *wave_threshold = bam::kWaveThreshold;
     return STARCH_OK;
+}
+
+}  // extern "C"
+
+// ---- bigWig / bigBed files read on the host (include/starch_amd.h; bed_bbi.hip) ----------
+namespace {
+// a mismatch of kind and file is found once the file is read
+bool bbi_query_ok(const starch_bbi_query* q, bbi::Region* out)
+{
+    if (!q || q->kind > STARCH_BBI_BIGBED || q->region > 2) return false;
+    if (q->region && (!q->chrom || !q->chrom_len)) return false;
+    if (q->region == 2 && q->start >= q->end) return false;
+    out->any = q->region != 0;
+    out->whole = q->region != 2;
+    if (q->region) out->chrom.assign(q->chrom, q->chrom_len);
+    out->start = q->start;
+    out->end = q->end;
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
+int starch_bbi_info(const void* data, uint64_t n, const starch_bbi_query* q, starch_bbi_header* hdr, uint32_t* chrom_sizes,
+                    uint64_t chrom_cap, char* names, uint64_t names_cap, starch_bbi_block* blocks, uint64_t* block_index,
+                    uint64_t block_cap, char* err, uint64_t err_cap)
+{
+    if ((n && !data) || !hdr || (chrom_cap && !chrom_sizes) || (names_cap && !names) || (block_cap && !blocks)) return STARCH_ERR_ARG;
+    if (err && err_cap) err[0] = 0;
+    bbi::Region rg;
+    if (q && !bbi_query_ok(q, &rg)) return STARCH_ERR_ARG;
+    try {
+        bbi::Info info;
+        bbi::parse(static_cast<const uint8_t*>(data), n, info);
+        if (q && q->kind != STARCH_BBI_AUTO && q->kind != info.kind)
+            throw StarchError(STARCH_ERR_DATA, std::string("bbi: the file is a ") + (info.kind == bbi::KIND_BIGWIG ? "bigWig" : "bigBed") +
+                                                   ", not the kind that was asked for");
+        int64_t chrom_id = -1;
+        const std::vector<uint64_t> sel = bbi::select(info, rg, &chrom_id);
+        uint64_t names_bytes = 0;
+        for (const bbi::Chrom& ch : info.chroms) names_bytes += ch.name.size() + 1;
+        *hdr = starch_bbi_header{info.kind, info.version, info.zoom_levels, info.field_count, info.defined_field_count,
+                                 info.uncompress_buf_size, info.chrom_tree_offset, info.full_data_offset, info.full_index_offset,
+                                 info.chroms.size(), names_bytes, info.blocks.size(), sel.size()};
+        bool small = false;
+        if (chrom_sizes || chrom_cap) {
+            if (chrom_cap < info.chroms.size()) small = true;
+            else for (uint64_t k = 0; k < info.chroms.size(); ++k) chrom_sizes[k] = info.chroms[k].size;
+        }
+        if (names || names_cap) {
+            if (names_cap < names_bytes) small = true;
+            else {
+                uint64_t at = 0;
+                for (const bbi::Chrom& ch : info.chroms) {
+                    memcpy(names + at, ch.name.c_str(), ch.name.size() + 1);
+                    at += ch.name.size() + 1;
+                }
+            }
+        }
+        if (blocks || block_cap) {
+            if (block_cap < sel.size()) small = true;
+            else for (uint64_t k = 0; k < sel.size(); ++k) {
+                const bbi::Block& b = info.blocks[sel[k]];
+                blocks[k] = starch_bbi_block{b.start_chrom, b.start_base, b.end_chrom, b.end_base, b.data_offset, b.data_size};
+                if (block_index) block_index[k] = sel[k];
+            }
+        }
+        return small ? STARCH_ERR_MEM : STARCH_OK;
+    } catch (const StarchError& e) {
+        if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+        return e.code;
+    } catch (const std::exception& e) {
+        if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
+        return STARCH_ERR_INTERNAL;
+    }
 }
 
 }  // extern "C"
