@@ -1411,6 +1411,13 @@ typedef struct {
 int starch_bbi_info(const void* data, uint64_t n, const starch_bbi_query* q, starch_bbi_header* hdr, uint32_t* chrom_sizes,
                     uint64_t chrom_cap, char* names, uint64_t names_cap, starch_bbi_block* blocks, uint64_t* block_index,
                     uint64_t block_cap, char* err, uint64_t err_cap);
+/* Adler-32 (RFC 1950: the trailer of a compressed block of such a file) of
+ * data[0, n), folded from pieces of `piece` bytes (1 to 2^20), each piece summed
+ * in 64 interleaved shares: the arithmetic of starch_amd/csrc/gz_adler.hpp, which
+ * is written to run unchanged in a kernel, run on the host.  No context and no
+ * GPU.  A NULL adler, bytes announced and none given, and a piece outside its
+ * range are STARCH_ERR_ARG. */
+int starch_bbi_adler32_host(const void* data, uint64_t n, uint32_t piece, uint32_t* adler);
 
 /* ---- gzip and BGZF inputs: inflate on the GPU (gz_inflate.hip) ----
  * An input of at least 18 bytes that begins 1f 8b 08 is gzip: one or more

@@ -465,6 +465,7 @@ def load():
         "starch_bbi_info": ([ctypes.c_char_p, u64, ctypes.POINTER(BbiQuery), ctypes.POINTER(BbiHeader),
                              ctypes.POINTER(ctypes.c_uint32), u64, vp, u64, ctypes.POINTER(BbiBlock), pu64, u64, vp, u64],
                             ctypes.c_int),
+        "starch_bbi_adler32_host": ([ctypes.c_char_p, u64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
         "starch_gunzip_host": ([vp, ctypes.c_char_p, u64], ctypes.c_int),
         "starch_gunzip_device": ([vp, vp, u64], ctypes.c_int),
         "starch_gunzip_plan": ([ctypes.c_char_p, u64, ctypes.POINTER(GunzipMember), u64, pu64,

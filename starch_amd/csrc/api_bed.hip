@@ -10,6 +10,7 @@
 
 #include "api_int.hpp"
 #include "bed_bbi.hpp"
+#include "gz_adler.hpp"
 
 using namespace api;
 
@@ -1135,6 +1136,13 @@ int starch_bbi_info(const void* data, uint64_t n, const starch_bbi_query* q, sta
         if (err && err_cap) snprintf(err, err_cap, "%s", e.what());
         return STARCH_ERR_INTERNAL;
     }
+}
+
+int starch_bbi_adler32_host(const void* data, uint64_t n, uint32_t piece, uint32_t* adler)
+{
+    if ((n && !data) || !adler || piece < 1 || piece > gz::kAdlerMaxPiece) return STARCH_ERR_ARG;
+    *adler = gz::adler32_pieces(static_cast<const uint8_t*>(data), n, piece);
+    return STARCH_OK;
 }
 
 }  // extern "C"
