@@ -469,9 +469,12 @@ __device__ __forceinline__ void run_t(const uint8_t* __restrict__ text, uint64_t
 // T0 lies in [0, CUT_E), T0 = (k + 1) * nblockMAX, in the tile where W
 // crosses T0 and the next one, and stores for every e the first of them at or
 // past T0 + e (its offset in dtab, its text position in ptab).  254: none
-// before the stream ends; 255: not within the two tiles (the walk then
-// searches the text as before).  The walk itself becomes one table read per
-// block, the next row already loaded.
+// before the stream ends, which holds only when the two tiles reach the
+// stream's end and contain no chunk start at T0 + CUT_E or later (for e >=
+// CUT_E - 4 the first start at or past T0 + e can lie at T0 + CUT_E .. T0 + e
+// + 4, beyond the recorded offsets, with text after it); 255: not known from
+// the recorded starts (the walk then searches the text as before).  The walk
+// itself becomes one table read per block, the next row already loaded.
 constexpr int CUT_E = 128;
 constexpr int CUT_WPG = 4;                       // (stream, k) waves per workgroup
 
@@ -522,6 +525,7 @@ __global__ void __launch_bounds__(64 * CUT_WPG) k_cut_tab(const StreamIn* __rest
 #pragma unroll
     for (int i = 0; i < CUT_E / 32; ++i) mk[i] = 0;
     bool to_end = false;                                        // the two tiles reach the stream's end
+    bool past = false;                                          // a chunk start with W - T0 >= CUT_E seen
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const uint64_t tj = lo + (uint64_t)j;
@@ -544,12 +548,16 @@ __global__ void __launch_bounds__(64 * CUT_WPG) k_cut_tab(const StreamIn* __rest
 #pragma unroll
         for (int b = 0; b < 64; ++b) {
             const uint32_t t = (tw[b >> 2] >> (8 * (b & 3))) & 0xffu;
-            if (t == 0 && a + b < tend && W >= T0 && W - T0 < (uint64_t)CUT_E) {
-                const uint32_t o = (uint32_t)(W - T0);
+            if (t == 0 && a + b < tend && W >= T0) {
+                if (W - T0 < (uint64_t)CUT_E) {
+                    const uint32_t o = (uint32_t)(W - T0);
 #pragma unroll
-                for (int i = 0; i < CUT_E / 32; ++i)
-                    if ((o >> 5) == (uint32_t)i) mk[i] |= 1u << (o & 31u);
-                pos_sh[wv][o] = a + (uint64_t)b;
+                    for (int i = 0; i < CUT_E / 32; ++i)
+                        if ((o >> 5) == (uint32_t)i) mk[i] |= 1u << (o & 31u);
+                    pos_sh[wv][o] = a + (uint64_t)b;
+                } else {
+                    past = true;
+                }
             }
             W += rle_w(t);
         }
@@ -557,6 +565,9 @@ __global__ void __launch_bounds__(64 * CUT_WPG) k_cut_tab(const StreamIn* __rest
 #pragma unroll
     for (int i = 0; i < CUT_E / 32; ++i)
         mk[i] = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan_or(mk[i]), 63);
+    // 254 needs proof that no chunk start at or past T0 + e is left: the tiles
+    // reach the stream's end and hold no start past the recorded offsets
+    const uint8_t none = (to_end && __ballot(past) == 0) ? (uint8_t)254 : (uint8_t)255;
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -571,7 +582,7 @@ __global__ void __launch_bounds__(64 * CUT_WPG) k_cut_tab(const StreamIn* __rest
             const uint32_t mm = e <= lo_bit ? mk[i] : (e < lo_bit + 32u ? mk[i] & (~0u << (e - lo_bit)) : 0u);
             if (b < 0 && mm) b = (int)lo_bit + __builtin_ctz(mm);
         }
-        dtab[row + e] = b >= 0 ? (uint8_t)b : (to_end ? (uint8_t)254 : (uint8_t)255);
+        dtab[row + e] = b >= 0 ? (uint8_t)b : none;
         ptab[row + e] = b >= 0 ? pos_sh[wv][b] : end;
     }
 }
