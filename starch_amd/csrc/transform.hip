@@ -5,8 +5,8 @@
 // tokenizing + sscanf (consume_line, hpp:201-345), chromosome segmentation
 // (hpp:325-342, 347-407) and update_transformation_state (hpp:428-504).
 // Normative semantics, including the reference's quirks, are SURVEY.md
-// Appendix A; tests/test_transform_gpu.py checks byte equality against the
-// oracle and the reference goldens.
+// Appendix A; tests/test_gpu_parity.py, test_gpu_transform_fused.py and
+// test_gpu_transform_paths.py check byte equality against the oracle.
 //
 // Layout in HBM (all per-line arrays are struct-of-arrays, indexed by line):
 //   bed      u8[n]          input bytes
@@ -246,11 +246,12 @@ struct LineVals {
     bool aok, bok, newseg;
 };
 
+// The byte-serial parser of the line [ls, le): the definition every other
+// parser here must agree with.  newseg is left true for the caller to decide.
 template <class S>
-__device__ __forceinline__ LineVals parse_vals(const S& bed, const uint64_t* __restrict__ line_end, uint64_t i)
+__device__ __forceinline__ LineVals parse_line_at(const S& bed, uint64_t ls, uint64_t le)
 {
     LineVals r;
-    const uint64_t ls = i ? line_end[i - 1] : 0, le = line_end[i];
     const Fields f = tokenize(bed, ls, le);
     uint64_t len[4];
 #pragma unroll
@@ -260,33 +261,29 @@ __device__ __forceinline__ LineVals parse_vals(const S& bed, const uint64_t* __r
     r.aok = scan_i64(bed, f.b[1], len[1], r.a);
     r.bok = scan_i64(bed, f.b[2], len[2], r.b);
     r.newseg = true;
-    if (i > 0) {
-        const uint64_t ps = (i > 1) ? line_end[i - 2] : 0;
-        const uint64_t pe = chr_end(bed, ps);
-        const uint64_t plen = cstr_len(bed, ps, pe - ps);
-        if (plen == len[0]) {
-            r.newseg = false;
-            for (uint64_t k = 0; k < plen; ++k)
-                if (bed[ps + k] != bed[ls + k]) { r.newseg = true; break; }
-        }
-    }
     r.rem_b = f.b[3];
     r.rem_len = (uint32_t)len[3];
     r.chr_len = (uint32_t)len[0];
     return r;
 }
 
-// start/stop of line i only (the line before a workgroup's first line)
+// line i with newseg from the strcmp against line i-1's chromosome (hpp:325-342)
 template <class S>
-__device__ __forceinline__ void parse_ab(const S& bed, const uint64_t* __restrict__ line_end, uint64_t i, int64_t& a,
-                                         int64_t& b)
+__device__ __forceinline__ LineVals parse_vals(const S& bed, const uint64_t* __restrict__ line_end, uint64_t i)
 {
-    const uint64_t ls = i ? line_end[i - 1] : 0, le = line_end[i];
-    const Fields f = tokenize(bed, ls, le);
-    a = 0;
-    b = 0;
-    scan_i64(bed, f.b[1], cstr_len(bed, f.b[1], f.e[1] - f.b[1]), a);
-    scan_i64(bed, f.b[2], cstr_len(bed, f.b[2], f.e[2] - f.b[2]), b);
+    const uint64_t ls = i ? line_end[i - 1] : 0;
+    LineVals r = parse_line_at(bed, ls, line_end[i]);
+    if (i > 0) {
+        const uint64_t ps = (i > 1) ? line_end[i - 2] : 0;
+        const uint64_t pe = chr_end(bed, ps);
+        const uint64_t plen = cstr_len(bed, ps, pe - ps);
+        if (plen == r.chr_len) {
+            r.newseg = false;
+            for (uint64_t k = 0; k < plen; ++k)
+                if (bed[ps + k] != bed[ls + k]) { r.newseg = true; break; }
+        }
+    }
+    return r;
 }
 
 template <class S>
@@ -312,6 +309,26 @@ __device__ __forceinline__ void parse_line(const S& bed, const uint64_t* __restr
 // LDS.  Longer spans (very long lines) parse straight from global memory.
 constexpr uint32_t kParseCap = 24576;
 
+// LDS staging of bytes [start of line L0-1, end of line L1-1); false when they
+// do not fit in cap bytes (the workgroup then parses from global memory).
+// The copy is 16-B aligned in absolute address terms (bed itself may be
+// unaligned); a0 is bed-relative and may wrap below 0 -- LSrc indexes with
+// modular arithmetic.
+__device__ __forceinline__ bool stage_lines(const uint8_t* __restrict__ bed, const uint64_t* __restrict__ line_end,
+                                            uint64_t L0, uint64_t L1, uint4* tb4, uint32_t cap, uint64_t& a0)
+{
+    const uint64_t rb = L0 >= 2 ? line_end[L0 - 2] : 0;
+    const uint64_t re = line_end[L1 - 1];
+    const uintptr_t abs0 = reinterpret_cast<uintptr_t>(bed + rb) & ~(uintptr_t)15;
+    a0 = (uint64_t)(abs0 - reinterpret_cast<uintptr_t>(bed));
+    const uint64_t nw = (reinterpret_cast<uintptr_t>(bed + re) - abs0 + 15) / 16;
+    if (nw * 16 > cap) return false;
+    const uint4* src = reinterpret_cast<const uint4*>(abs0);
+    for (uint64_t w = threadIdx.x; w < nw; w += kThreads) tb4[w] = src[w];
+    __syncthreads();
+    return true;
+}
+
 __global__ void __launch_bounds__(kThreads)
 k_parse(const uint8_t* __restrict__ bed, const uint64_t* __restrict__ line_end, uint64_t nl,
         int64_t* __restrict__ start, int64_t* __restrict__ stop, uint8_t* __restrict__ flags,
@@ -322,25 +339,14 @@ k_parse(const uint8_t* __restrict__ bed, const uint64_t* __restrict__ line_end, 
     const uint64_t L0 = (uint64_t)blockIdx.x * kThreads;
     const uint64_t i = L0 + threadIdx.x;
     const uint64_t L1 = L0 + kThreads < nl ? L0 + kThreads : nl;
-    const uint64_t rb = L0 >= 2 ? line_end[L0 - 2] : 0;            // start of line L0-1 (or 0)
-    const uint64_t re = line_end[L1 - 1];
-    // 16-B aligned in absolute address terms (bed itself may be unaligned); a0 is
-    // bed-relative and may wrap below 0 -- LSrc indexes with modular arithmetic
-    const uintptr_t abs0 = reinterpret_cast<uintptr_t>(bed + rb) & ~(uintptr_t)15;
-    const uint64_t a0 = (uint64_t)(abs0 - reinterpret_cast<uintptr_t>(bed));
-    const uint64_t nw = (reinterpret_cast<uintptr_t>(bed + re) - abs0 + 15) / 16;
-    if (nw * 16 <= kParseCap) {
-        const uint4* src = reinterpret_cast<const uint4*>(abs0);
-        for (uint64_t w = threadIdx.x; w < nw; w += kThreads) tb4[w] = src[w];
-        __syncthreads();
-        if (i < nl) {
-            LSrc ls{reinterpret_cast<const uint8_t*>(tb4), a0};
-            parse_line(ls, line_end, i, start, stop, flags, rem_beg, rem_len, chr_len, any_fail);
-        }
-    } else if (i < nl) {
-        GSrc gs{bed};
-        parse_line(gs, line_end, i, start, stop, flags, rem_beg, rem_len, chr_len, any_fail);
-    }
+    uint64_t a0 = 0;
+    const bool staged = stage_lines(bed, line_end, L0, L1, tb4, kParseCap, a0);
+    if (i >= nl) return;
+    if (staged)
+        parse_line(LSrc{reinterpret_cast<const uint8_t*>(tb4), a0}, line_end, i, start, stop, flags, rem_beg, rem_len,
+                   chr_len, any_fail);
+    else
+        parse_line(GSrc{bed}, line_end, i, start, stop, flags, rem_beg, rem_len, chr_len, any_fail);
 }
 
 // stale-value propagation: idx[i] = ok ? i+1 : 0  -> inclusive max-scan -> gather
@@ -392,42 +398,6 @@ __device__ __forceinline__ int dec_len(int64_t v)
     return ndig_u64(u) + (v < 0 ? 1 : 0);
 }
 
-struct LineState { int64_t cd, last_cd, v; bool emit_p; };
-
-__device__ __forceinline__ LineState line_state(const int64_t* start, const int64_t* stop, const uint8_t* flags,
-                                                uint64_t i)
-{
-    LineState s;
-    int64_t a = start[i], b = stop[i];
-    s.cd = (int64_t)((uint64_t)b - (uint64_t)a);
-    int64_t last_stop = 0;
-    s.last_cd = 0;
-    if (!(flags[i] & F_NEW_SEG)) {
-        int64_t pa = start[i - 1], pb = stop[i - 1];
-        s.last_cd = (int64_t)((uint64_t)pb - (uint64_t)pa);
-        last_stop = pb;
-    }
-    s.emit_p = (s.cd != s.last_cd);
-    s.v = (last_stop != 0) ? (int64_t)((uint64_t)a - (uint64_t)last_stop) : a;
-    return s;
-}
-
-__global__ void __launch_bounds__(kThreads)
-k_line_len(const int64_t* __restrict__ start, const int64_t* __restrict__ stop, const uint8_t* __restrict__ flags,
-           const uint32_t* __restrict__ rem_len, uint64_t nl, uint32_t* __restrict__ out_len,
-           uint32_t* __restrict__ seg_flag)
-{
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nl) return;
-    LineState s = line_state(start, stop, flags, i);
-    uint32_t L = 0;
-    if (s.emit_p) L += 2 + n_digits_ref(s.cd);          // "p%ld\n" truncated (hpp:440,452)
-    L += dec_len(s.v) + 1;
-    if (rem_len[i]) L += 1 + rem_len[i];
-    out_len[i] = L;
-    seg_flag[i] = (flags[i] & F_NEW_SEG) ? 1u : 0u;
-}
-
 __device__ __forceinline__ uint64_t put_dec(uint8_t* o, int64_t v)
 {
     uint64_t u = (v < 0) ? 0ull - (uint64_t)v : (uint64_t)v;
@@ -443,38 +413,10 @@ __device__ __forceinline__ uint64_t put_dec(uint8_t* o, int64_t v)
     return k + nd;
 }
 
-__global__ void __launch_bounds__(kThreads)
-k_emit(const uint8_t* __restrict__ bed, const int64_t* __restrict__ start, const int64_t* __restrict__ stop,
-       const uint8_t* __restrict__ flags, const uint64_t* __restrict__ rem_beg, const uint32_t* __restrict__ rem_len,
-       const uint64_t* __restrict__ out_off, uint64_t nl, uint8_t* __restrict__ text)
-{
-    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nl) return;
-    LineState s = line_state(start, stop, flags, i);
-    uint8_t* o = text + out_off[i];
-    if (s.emit_p) {
-        int keep = 2 + n_digits_ref(s.cd);
-        uint8_t tmp[24];
-        tmp[0] = 'p';
-        uint64_t k = 1 + put_dec(tmp + 1, s.cd);
-        tmp[k++] = '\n';
-        for (int j = 0; j < keep; ++j) o[j] = tmp[j];
-        o += keep;
-    }
-    o += put_dec(o, s.v);
-    uint32_t rl = rem_len[i];
-    if (rl) {
-        *o++ = '\t';
-        const uint8_t* r = bed + rem_beg[i];
-        for (uint32_t j = 0; j < rl; ++j) o[j] = r[j];
-        o += rl;
-    }
-    *o = '\n';
-}
-
 // --- fused two-pass transform -------------------------------------------------
-// Taken when every line's start and stop parse (the stale-value rule of
-// hpp:306-316 never fires).  Each workgroup owns 256 lines and stages their
+// For the inputs that the single pass (below) hands over or that the host
+// sends here directly, when every line's start and stop parse (the stale-value
+// rule of hpp:306-316 never fires).  Each workgroup owns 256 lines and stages their
 // bytes, plus the line before them, in LDS once per pass.  Pass 1 (k_tf1)
 // reduces the workgroup's output bytes and new-segment count; after a scan over
 // workgroups, pass 2 (k_tf2) re-parses, scans inside the workgroup, builds the
@@ -561,8 +503,37 @@ __device__ __forceinline__ bool dig_fast(const uint8_t* tb, uint32_t b, uint32_t
     return bad == 0;
 }
 
-// Fast parse of the line at stage index r0 (bed offset ls), len bytes incl. '\n'.
-// Fills a, b, chr_len, rem_b, rem_len (newseg is decided by the caller).
+// Fields of one line from its tab mask.  Bit k of the 128-bit mask (tl, th) is
+// staged byte tb[q + k]; the line starts at bit off (bed offset ls), its '\n'
+// is bit nlp, and only tabs inside [off, nlp) are set.  Fills a, b, chr_len,
+// rem_b, rem_len (newseg is decided by the caller); false when the line has
+// fewer than two tabs or a start/stop that is not 1..18 plain digits.
+__device__ __forceinline__ bool swar_fields(const uint8_t* tb, uint64_t tl, uint64_t th, uint32_t q, uint32_t off,
+                                            uint32_t nlp, uint64_t ls, LineVals& r)
+{
+    // the reference's scan does not test the byte after a tab for a tab (tokenize)
+    const uint32_t t1 = next_bit(tl, th, off);
+    if (t1 >= 128u) return false;
+    const uint32_t t2 = next_bit(tl, th, t1 + 2u);
+    if (t2 >= 128u) return false;
+    const uint32_t t3 = next_bit(tl, th, t2 + 2u);
+    const uint32_t e2 = t3 < 128u ? t3 : nlp;
+    if (!dig_fast(tb, q + t1 + 1u, t2 - t1 - 1u, r.a)) return false;
+    if (!dig_fast(tb, q + t2 + 1u, e2 - t2 - 1u, r.b)) return false;
+    r.aok = r.bok = true;
+    r.chr_len = t1 - off;
+    if (t3 < 128u) {
+        r.rem_b = ls + (t3 + 1u - off);
+        r.rem_len = nlp - (t3 + 1u);
+    } else {
+        r.rem_b = ls + (nlp + 1u - off);
+        r.rem_len = 0;
+    }
+    return true;
+}
+
+// Fast parse of the line at stage index r0 (bed offset ls), len bytes incl. '\n':
+// tab and NUL masks by SWAR over the line's 16-byte-aligned 128-byte window.
 __device__ __forceinline__ bool parse_fast(const uint8_t* tb, uint32_t r0, uint32_t len, uint64_t ls, LineVals& r)
 {
     const uint32_t off = r0 & 15u, q = r0 - off, end = off + len;     // window-relative [off, end)
@@ -588,32 +559,14 @@ __device__ __forceinline__ bool parse_fast(const uint8_t* tb, uint32_t r0, uint3
     const uint32_t nlp = end - 1u;                            // the '\n'
     tl &= rl & ~(nlp < 64u ? (1ull << nlp) : 0ull);
     th &= rh & ~(nlp >= 64u ? (1ull << (nlp - 64u)) : 0ull);
-    // the reference's scan does not test the byte after a tab for a tab (tokenize)
-    const uint32_t t1 = next_bit(tl, th, off);
-    if (t1 >= 128u) return false;
-    const uint32_t t2 = next_bit(tl, th, t1 + 2u);
-    if (t2 >= 128u) return false;
-    const uint32_t t3 = next_bit(tl, th, t2 + 2u);
-    const uint32_t e2 = t3 < 128u ? t3 : nlp;
-    if (!dig_fast(tb, q + t1 + 1u, t2 - t1 - 1u, r.a)) return false;
-    if (!dig_fast(tb, q + t2 + 1u, e2 - t2 - 1u, r.b)) return false;
-    r.aok = r.bok = true;
-    r.chr_len = t1 - off;
-    if (t3 < 128u) {
-        r.rem_b = ls + (t3 + 1u - off);
-        r.rem_len = nlp - (t3 + 1u);
-    } else {
-        r.rem_b = ls + len;
-        r.rem_len = 0;
-    }
-    return true;
+    return swar_fields(tb, tl, th, q, off, nlp, ls, r);
 }
 
 // parse_fast with the tab positions read from precomputed LDS bit masks
 // (tabm bit i of word c: staged byte 32c + i is a tab) instead of SWAR over the
 // line's bytes; for tiles with no NUL byte (C-string rules then never apply).
-// Same acceptance rules and results as parse_fast; line at stage offset r0,
-// len bytes incl. its newline (<= 128), bed offset ls.
+// The fields come from the same swar_fields as parse_fast's; line at stage
+// offset r0, len bytes incl. its newline (<= 128), bed offset ls.
 __device__ __forceinline__ bool parse_mask(const uint8_t* tb, const uint32_t* tabm, uint32_t r0, uint32_t len,
                                            uint64_t ls, LineVals& r)
 {
@@ -625,56 +578,7 @@ __device__ __forceinline__ bool parse_mask(const uint8_t* tb, const uint32_t* ta
     uint64_t th = ((uint64_t)__builtin_amdgcn_alignbit(m4, m3, sh) << 32) | __builtin_amdgcn_alignbit(m3, m2, sh);
     tl &= lowbits(e);
     th &= lowbits(e > 64u ? e - 64u : 0u);
-    // the reference's scan does not test the byte after a tab for a tab (tokenize)
-    const uint32_t t1 = next_bit(tl, th, 0);
-    if (t1 >= 128u) return false;
-    const uint32_t t2 = next_bit(tl, th, t1 + 2u);
-    if (t2 >= 128u) return false;
-    const uint32_t t3 = next_bit(tl, th, t2 + 2u);
-    const uint32_t e2 = t3 < 128u ? t3 : e;
-    if (!dig_fast(tb, r0 + t1 + 1u, t2 - t1 - 1u, r.a)) return false;
-    if (!dig_fast(tb, r0 + t2 + 1u, e2 - t2 - 1u, r.b)) return false;
-    r.aok = r.bok = true;
-    r.chr_len = t1;
-    if (t3 < 128u) {
-        r.rem_b = ls + t3 + 1u;
-        r.rem_len = e - (t3 + 1u);
-    } else {
-        r.rem_b = ls + len;
-        r.rem_len = 0;
-    }
-    return true;
-}
-
-// start/stop and chromosome length of line i, byte-serial (the line before a workgroup)
-template <class S>
-__device__ __forceinline__ void parse_abc(const S& bed, const uint64_t* __restrict__ line_end, uint64_t i, int64_t& a,
-                                          int64_t& b, uint32_t& clen)
-{
-    const uint64_t ls = i ? line_end[i - 1] : 0, le = line_end[i];
-    const Fields f = tokenize(bed, ls, le);
-    a = 0;
-    b = 0;
-    scan_i64(bed, f.b[1], cstr_len(bed, f.b[1], f.e[1] - f.b[1]), a);
-    scan_i64(bed, f.b[2], cstr_len(bed, f.b[2], f.e[2] - f.b[2]), b);
-    clen = (uint32_t)cstr_len(bed, f.b[0], f.e[0] - f.b[0]);
-}
-
-// LDS staging of bytes [start of line L0-1, end of line L1-1); false when they
-// do not fit in cap bytes (the workgroup then parses from global memory).
-__device__ __forceinline__ bool stage_lines(const uint8_t* __restrict__ bed, const uint64_t* __restrict__ line_end,
-                                            uint64_t L0, uint64_t L1, uint4* tb4, uint32_t cap, uint64_t& a0)
-{
-    const uint64_t rb = L0 >= 2 ? line_end[L0 - 2] : 0;
-    const uint64_t re = line_end[L1 - 1];
-    const uintptr_t abs0 = reinterpret_cast<uintptr_t>(bed + rb) & ~(uintptr_t)15;
-    a0 = (uint64_t)(abs0 - reinterpret_cast<uintptr_t>(bed));
-    const uint64_t nw = (reinterpret_cast<uintptr_t>(bed + re) - abs0 + 15) / 16;
-    if (nw * 16 > cap) return false;
-    const uint4* src = reinterpret_cast<const uint4*>(abs0);
-    for (uint64_t w = threadIdx.x; w < nw; w += kThreads) tb4[w] = src[w];
-    __syncthreads();
-    return true;
+    return swar_fields(tb, tl, th, r0, 0u, e, ls, r);
 }
 
 struct OutDesc { int64_t cd, v; bool emit_p; uint32_t len; };
@@ -737,16 +641,14 @@ __device__ __forceinline__ bool tf_parse(const uint8_t* __restrict__ bed, const 
         uint64_t pls = 0;
         if (L0 > 0) {
             pls = (L0 > 1) ? line_end[L0 - 2] : 0;
+            const uint64_t ple = line_end[L0 - 1];
             LineVals pr;
-            if (staged && parse_fast(tb, (uint32_t)(pls - a0), (uint32_t)(line_end[L0 - 1] - pls), pls, pr)) {
-                a = pr.a;
-                b = pr.b;
-                clen = pr.chr_len;
-            } else if (staged) {
-                parse_abc(LSrc{tb, a0}, line_end, L0 - 1, a, b, clen);
-            } else {
-                parse_abc(GSrc{bed}, line_end, L0 - 1, a, b, clen);
-            }
+            if (!staged) pr = parse_line_at(GSrc{bed}, pls, ple);
+            else if (!parse_fast(tb, (uint32_t)(pls - a0), (uint32_t)(ple - pls), pls, pr))
+                pr = parse_line_at(LSrc{tb, a0}, pls, ple);
+            a = pr.a;
+            b = pr.b;
+            clen = pr.chr_len;
         }
         sh.a[0] = a;
         sh.b[0] = b;
@@ -811,6 +713,10 @@ k_tf1(const uint8_t* __restrict__ bed, const uint64_t* __restrict__ line_end, ui
     }
 }
 
+// The line writer of every path (hpp:428-504), out_desc(...).len bytes at o:
+// the "p" line cut to 2 + n_digits_ref(cd) bytes when the delta changes, the
+// start (or its distance from the last stop), and a tab and the remainder
+// only when there is one.
 template <class S>
 __device__ __forceinline__ void tf_write(const S& src, const TfLine& t, uint8_t* o)
 {
@@ -845,6 +751,51 @@ __device__ __forceinline__ void tf_write(const S& src, const TfLine& t, uint8_t*
         o += t.r.rem_len;
     }
     *o = '\n';
+}
+
+// General path (stale values propagated into start / stop): line i and its
+// predecessor's start/stop from the per-line arrays, then the same out_desc /
+// tf_write as the other paths.
+__device__ __forceinline__ TfLine line_from_arrays(const int64_t* __restrict__ start, const int64_t* __restrict__ stop,
+                                                   const uint8_t* __restrict__ flags,
+                                                   const uint32_t* __restrict__ rem_len, uint64_t i)
+{
+    TfLine t;
+    t.r.a = start[i];
+    t.r.b = stop[i];
+    t.r.rem_b = 0;
+    t.r.rem_len = rem_len[i];
+    t.r.newseg = (flags[i] & F_NEW_SEG) != 0;
+    t.pa = t.pb = 0;
+    if (!t.r.newseg) {
+        t.pa = start[i - 1];
+        t.pb = stop[i - 1];
+    }
+    return t;
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_line_len(const int64_t* __restrict__ start, const int64_t* __restrict__ stop, const uint8_t* __restrict__ flags,
+           const uint32_t* __restrict__ rem_len, uint64_t nl, uint32_t* __restrict__ out_len,
+           uint32_t* __restrict__ seg_flag)
+{
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nl) return;
+    const TfLine t = line_from_arrays(start, stop, flags, rem_len, i);
+    out_len[i] = out_desc(t.r, t.pa, t.pb).len;
+    seg_flag[i] = t.r.newseg ? 1u : 0u;
+}
+
+__global__ void __launch_bounds__(kThreads)
+k_emit(const uint8_t* __restrict__ bed, const int64_t* __restrict__ start, const int64_t* __restrict__ stop,
+       const uint8_t* __restrict__ flags, const uint64_t* __restrict__ rem_beg, const uint32_t* __restrict__ rem_len,
+       const uint64_t* __restrict__ out_off, uint64_t nl, uint8_t* __restrict__ text)
+{
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nl) return;
+    TfLine t = line_from_arrays(start, stop, flags, rem_len, i);
+    t.r.rem_b = rem_beg[i];
+    tf_write(GSrc{bed}, t, text + out_off[i]);
 }
 
 __global__ void __launch_bounds__(kThreads)
@@ -977,25 +928,6 @@ static_assert(kFT <= 16384, "tested tile sizes: 4, 8, 16 KiB (8 KiB measured fas
 constexpr uint32_t kFSeg = 64;                 // segment records per tile in LDS
 enum : uint32_t { FX_FAIL = 1, FX_FALLBACK = 2, FX_TEXT_CAP = 4, FX_SEG_CAP = 8 };
 
-template <class S>
-__device__ __forceinline__ LineVals parse_line_at(const S& bed, uint64_t ls, uint64_t le)
-{
-    LineVals r;
-    const Fields f = tokenize(bed, ls, le);
-    uint64_t len[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) len[t] = cstr_len(bed, f.b[t], f.e[t] - f.b[t]);
-    r.a = 0;
-    r.b = 0;
-    r.aok = scan_i64(bed, f.b[1], len[1], r.a);
-    r.bok = scan_i64(bed, f.b[2], len[2], r.b);
-    r.newseg = true;
-    r.rem_b = f.b[3];
-    r.rem_len = (uint32_t)len[3];
-    r.chr_len = (uint32_t)len[0];
-    return r;
-}
-
 struct FusedSeg { uint32_t line, name_ls, name_len, text; };
 struct ArenaSeg { uint32_t tile, q, line, name_len; uint64_t name_off; uint32_t text, pad; };
 struct FusedOut {                  // k_tf_fused's outputs (arena form) and the scans over them
@@ -1019,7 +951,7 @@ struct FusedShared {
     uint64_t scan[kFThreads / 64 + 1];
     FusedSeg seg[kFSeg];
     LineKey wlast[kFThreads / 64 + 1];         // [0]: carry into the chunk; [w+1]: wave w's last line
-    uint32_t tile, ffpos, p1, p2, over, nul;
+    uint32_t ffpos, p1, p2, over, nul;
     struct { uint64_t segs; } excl;          // the tile's first record in the segment arena
 };
 
@@ -1043,7 +975,7 @@ __device__ __forceinline__ LineKey shfl_up_key(const LineKey& k)
 __device__ __forceinline__ void fused_lines(FusedShared& S, const uint8_t* tb, uint64_t a0, uint32_t nl,
                                             uint32_t first_ls, bool input_start, uint32_t* __restrict__ xflags,
                                             uint64_t& bytes_out, uint32_t& segs_out, uint32_t prev_ls = 0,
-                                            bool parse_prev = false, bool no_write = false)
+                                            bool parse_prev = false)
 {
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (parse_prev && tid == kFThreads - 1) {      // its slots 2*tid, 2*tid+1 are past nl
@@ -1117,8 +1049,7 @@ __device__ __forceinline__ void fused_lines(FusedShared& S, const uint8_t* tb, u
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             if (!have[u]) continue;
-            if (no_write) { /* timing experiment */ }
-            else if (off + len[u] <= kFOut) tf_write(lsrc, t[u], ob + off);
+            if (off + len[u] <= kFOut) tf_write(lsrc, t[u], ob + off);
             else S.over = 1;
             if (ns[u]) {
                 if (sl < kFSeg) S.seg[sl] = FusedSeg{c0 + 2 * tid + u, ls[u], t[u].r.chr_len, (uint32_t)off};
@@ -1144,23 +1075,12 @@ __device__ __forceinline__ void fused_lines(FusedShared& S, const uint8_t* tb, u
 #ifndef STARCH_TF_WPE
 #define STARCH_TF_WPE 6
 #endif
-// STARCH_TF_PROF (timing experiment, dev builds only): per-wave shader-clock
-// time of k_tf_fused's phases, summed into g_tfprof (printed by run())
-#ifdef STARCH_TF_PROF
-__device__ unsigned long long g_tfprof[8];
-#define TPROF(v) const uint64_t v = __builtin_readcyclecounter()
-#else
-#define TPROF(v)
-#endif
 __global__ void __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(STARCH_TF_WPE)))
-k_tf_fused(const uint8_t* __restrict__ bed, uint64_t n, const FusedOut fo, uint32_t* __restrict__ xflags,
-           uint32_t dbg_mode)
+k_tf_fused(const uint8_t* __restrict__ bed, uint64_t n, const FusedOut fo, uint32_t* __restrict__ xflags)
 {
     __shared__ FusedShared S;
     const uint32_t tid = threadIdx.x, lane = tid & 63;
-    TPROF(p0);
     if (tid == 0) {
-        S.tile = blockIdx.x;
         S.ffpos = 0xFFFFFFFFu;
         S.p1 = 0;
         S.p2 = 0;
@@ -1168,7 +1088,7 @@ k_tf_fused(const uint8_t* __restrict__ bed, uint64_t n, const FusedOut fo, uint3
         S.nul = 0;
     }
     __syncthreads();
-    const uint32_t tile = S.tile;
+    const uint32_t tile = blockIdx.x;
     const uint64_t t0 = (uint64_t)tile * kFT;
     const uint64_t tend = t0 + kFT < n ? t0 + kFT : n;
     const uint64_t s0 = t0 > kFH ? t0 - kFH : 0;
@@ -1180,7 +1100,6 @@ k_tf_fused(const uint8_t* __restrict__ bed, uint64_t n, const FusedOut fo, uint3
         for (uint32_t w = tid; w < nw; w += kFThreads) S.tb4[w] = src[w];
     }
     __syncthreads();
-    TPROF(p1);
     const uint8_t* tb = reinterpret_cast<const uint8_t*>(S.tb4);
     const uint32_t Lt0 = (uint32_t)(t0 - a0), Lend = (uint32_t)(tend - a0), Ls0 = (uint32_t)(s0 - a0);
     // newline / 0xFF masks of 32-byte LDS chunks covering [Lt0, Lend); a thread
@@ -1316,31 +1235,19 @@ k_tf_fused(const uint8_t* __restrict__ bed, uint64_t n, const FusedOut fo, uint3
         S.wlast[0] = pk;
     }
     __syncthreads();
-    TPROF(p2);
     uint64_t bytes = 0;
     uint32_t segs = 0;
-    if (dbg_mode == 1 || dbg_mode == 2) {           // timing experiments: no output (empty tiles)
-        if (tid == 0) {
-            fo.tile_bytes[tile] = 0u;
-            fo.tile_lines[tile] = 0u;
-            fo.tile_segs[tile] = 0u;
-        }
-        if (dbg_mode == 2) return;                  // staging + masks only
-    }
     if (!fallback && nl_tile > 0)
-        fused_lines(S, tb, a0, nl_tile, first_ls, input_start, xflags, bytes, segs, prev_ls, prev_in_lines,
-                    dbg_mode == 3);
-    TPROF(p3);
+        fused_lines(S, tb, a0, nl_tile, first_ls, input_start, xflags, bytes, segs, prev_ls, prev_in_lines);
     fallback = fallback || S.over;
     if (fallback && tid == 0) atomicOr(xflags, FX_FALLBACK);
-    if (dbg_mode == 1) return;                      // timing experiment: parse only (tile counts zeroed above)
-    TPROF(p4);
     // No look-back: the tile's text goes to its fixed slot of the arena and its
     // counts to per-tile arrays; k_tf_place moves it to its final offset after
-    // a scan over the tiles.  (Waiting here for the previous tiles' prefix,
-    // with the workgroup's LDS held, took ~65% of the workgroups' time
-    // (STARCH_TF_PROF); a bump allocator -- one atomic per tile on one counter
-    // -- serialised the tiles' tails: 1.7 of 4.4 ms, STARCH_TF_DBG=1.)
+    // a scan over the tiles.  (Measured with per-phase cycle counters: waiting
+    // here for the previous tiles' prefix, with the workgroup's LDS held, took
+    // ~65% of the workgroups' time.  A bump allocator -- one atomic per tile on
+    // one counter -- serialised the tiles' tails: 1.7 of 4.4 ms, by timing the
+    // kernel with and without its arena write.)
     if (tid == 0) {
         const bool ff = ffpos != 0xFFFFFFFFu;
         fo.tile_bytes[tile] = fallback ? 0u : (uint32_t)bytes;
@@ -1364,14 +1271,6 @@ k_tf_fused(const uint8_t* __restrict__ bed, uint64_t n, const FusedOut fo, uint3
     uint32_t* dst = reinterpret_cast<uint32_t*>(fo.arena + ab);   // 4-byte aligned
     const uint32_t nw4 = ((uint32_t)bytes + 3u) / 4u;
     for (uint32_t w = tid; w < nw4; w += kFThreads) dst[w] = ob4[w];
-#ifdef STARCH_TF_PROF
-    TPROF(p5);
-    if (lane == 0) {
-        atomicAdd(&g_tfprof[3], (unsigned long long)(p4 - p3));
-        atomicAdd(&g_tfprof[4], (unsigned long long)(p5 - p4));
-        atomicAdd(&g_tfprof[5], 1ull);
-    }
-#endif
 }
 
 // after the scans over the tiles (exclusive prefixes of bytes, lines and
@@ -1625,11 +1524,8 @@ void TransformWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, T
         fo.seg_cap = scap;
         HIP_CHECK(hipMemsetAsync(fx, 0, 8 * sizeof(uint64_t), st));
         HIP_CHECK(hipMemsetAsync(fo.first_ff, 0xFF, sizeof(uint32_t), st));
-        // STARCH_TF_DBG (timing experiments only, wrong output): 1 parse without
-        // the arena write, 2 staging + masks only, 3 parse + lengths without text
-        static const uint32_t dbg_mode = getenv("STARCH_TF_DBG") ? (uint32_t)atoi(getenv("STARCH_TF_DBG")) : 0u;
         hipLaunchKernelGGL(k_tf_fused, dim3(ntiles), dim3(kFThreads), 0, st, d_bed, n, fo,
-                           reinterpret_cast<uint32_t*>(fx + 4), dbg_mode);
+                           reinterpret_cast<uint32_t*>(fx + 4));
         scan::excl_sum_u32_to_u64(fo.tile_bytes, fo.bytes_pre, ntiles, fo.bytes_pre + ntiles, b_tmp, st);
         scan::excl_sum_u32_to_u64(fo.tile_lines, fo.lines_pre, ntiles, fo.lines_pre + ntiles, b_tmp, st);
         scan::excl_sum_u32_to_u64(fo.tile_segs, fo.segs_pre, ntiles, fo.segs_pre + ntiles, b_tmp, st);
@@ -1643,28 +1539,12 @@ void TransformWorkspace::run(const uint8_t* d_bed, uint64_t n, hipStream_t st, T
         HIP_CHECK(hipMemcpyAsync(h, fx, sizeof(h), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
         const uint32_t flags = (uint32_t)h[4];
-        static const bool dbg = getenv("STARCH_TF_DEBUG") != nullptr;
-        if (dbg) fprintf(stderr, "[tf] attempt %d flags %u lines %llu segs %llu bytes %llu\n", attempt, flags,
-                         (unsigned long long)h[0], (unsigned long long)h[1], (unsigned long long)h[2]);
         if (flags & (FX_FAIL | FX_FALLBACK)) break;                 // stale values / long lines: two-pass path
         if (flags & (FX_TEXT_CAP | FX_SEG_CAP)) {                     // grow to the exact totals and rerun
             tcap = std::max(tcap, h[2] + 64);
             scap = std::max(scap, h[1] + 1);
             continue;
         }
-#ifdef STARCH_TF_PROF
-        {
-            unsigned long long g[8];
-            HIP_CHECK(hipMemcpyFromSymbol(g, HIP_SYMBOL(g_tfprof), sizeof(g)));
-            static const unsigned long long zero[8] = {};
-            HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_tfprof), zero, sizeof(zero)));
-            const char* nm[5] = {"stage", "masks+nl-scan+halo", "fused_lines", "counts+arena alloc", "arena write"};
-            const double tot = (double)(g[0] + g[1] + g[2] + g[3] + g[4]);
-            for (int q = 0; q < 5; ++q)
-                fprintf(stderr, "[tfprof] %-20s %14llu (%.1f%%)\n", nm[q], g[q], 100.0 * (double)g[q] / (tot ? tot : 1));
-            fprintf(stderr, "[tfprof] waves %llu, cycles per wave-tile %.0f\n", g[5], tot / (double)(g[5] ? g[5] : 1));
-        }
-#endif
         res.n_lines = h[0];
         res.n_segments = h[1];
         res.text_bytes = h[2];
@@ -1684,6 +1564,7 @@ uint64_t TransformWorkspace::index_lines(const uint8_t* d_bed, uint64_t n, hipSt
     uint64_t ntile = ceil_div(n, kTileBytes);
     uint32_t* tile_cnt = b_tile_cnt.as<uint32_t>(ntile + 1);
     uint64_t* tile_off = b_tile_off.as<uint64_t>(ntile + 1);
+    // [0]=nl_total [1]=ff_pos [2]=nl_eff; the callers' slots: [3]=nseg [4]=text_total [5]=any_fail
     uint64_t* scal = b_scal.as<uint64_t>(16);
     HIP_CHECK(hipMemsetAsync(scal, 0, 16 * sizeof(uint64_t), st));
     HIP_CHECK(hipMemsetAsync(scal + 1, 0xff, sizeof(uint64_t), st));
@@ -1710,6 +1591,35 @@ uint64_t TransformWorkspace::index_lines(const uint8_t* d_bed, uint64_t n, hipSt
     return nl;
 }
 
+// The per-line arrays of the nl lines indexed in b_line_end: k_parse fills
+// b_start / b_stop / b_flags / b_rem_beg / b_rem_len / b_chr_len, then a start
+// or stop that did not parse takes the last one that did (stale sscanf values,
+// hpp:306-316; init_start / init_stop before the first).
+void TransformWorkspace::parse_lines(const uint8_t* d_bed, uint64_t nl, hipStream_t st, int64_t init_start,
+                                     int64_t init_stop)
+{
+    const uint64_t* line_end = static_cast<const uint64_t*>(b_line_end.p);
+    const unsigned nb = (unsigned)ceil_div(nl, kThreads);
+    uint32_t* any_fail = reinterpret_cast<uint32_t*>(b_scal.as<uint64_t>(16) + 5);
+    int64_t* start = b_start.as<int64_t>(nl);
+    int64_t* stop = b_stop.as<int64_t>(nl);
+    uint8_t* flags = b_flags.as<uint8_t>(nl);
+    hipLaunchKernelGGL(k_parse, dim3(nb), dim3(kThreads), 0, st, d_bed, line_end, nl, start, stop, flags,
+                       b_rem_beg.as<uint64_t>(nl), b_rem_len.as<uint32_t>(nl), b_chr_len.as<uint32_t>(nl), any_fail);
+    uint64_t* idx = b_idx.as<uint64_t>(nl);
+    for (int w = 0; w < 2; ++w) {
+        hipLaunchKernelGGL(k_ok_index, dim3(nb), dim3(kThreads), 0, st, flags, nl,
+                           (uint8_t)(w == 0 ? F_START_OK : F_STOP_OK), idx);
+        scan::incl_max_u64(idx, nl, b_tmp, st);
+        // gather from a copy to avoid read/write races across blocks
+        int64_t* v = (w == 0) ? start : stop;
+        int64_t* cp = b_vcopy.as<int64_t>(nl);
+        HIP_CHECK(hipMemcpyAsync(cp, v, nl * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(k_gather_stale, dim3(nb), dim3(kThreads), 0, st, cp, idx, nl, w == 0 ? init_start : init_stop,
+                           v);
+    }
+}
+
 void TransformWorkspace::base_counts(const uint8_t* d_bed, uint64_t n, hipStream_t st, int64_t init_start,
                                      int64_t init_stop, std::vector<uint64_t>& unique, std::vector<uint64_t>& nonunique)
 {
@@ -1717,26 +1627,12 @@ void TransformWorkspace::base_counts(const uint8_t* d_bed, uint64_t n, hipStream
     nonunique.clear();
     const uint64_t nl = index_lines(d_bed, n, st, nullptr);
     if (nl == 0) return;
-    const uint64_t* line_end = static_cast<const uint64_t*>(b_line_end.p);
     const unsigned nb = (unsigned)ceil_div(nl, kThreads);
     uint64_t* scal = b_scal.as<uint64_t>(16);
-    uint32_t* any_fail = reinterpret_cast<uint32_t*>(scal + 5);
-    int64_t* start = b_start.as<int64_t>(nl);
-    int64_t* stop = b_stop.as<int64_t>(nl);
-    uint8_t* flags = b_flags.as<uint8_t>(nl);
-    hipLaunchKernelGGL(k_parse, dim3(nb), dim3(kThreads), 0, st, d_bed, line_end, nl, start, stop, flags,
-                       b_rem_beg.as<uint64_t>(nl), b_rem_len.as<uint32_t>(nl), b_chr_len.as<uint32_t>(nl), any_fail);
-    uint64_t* idx = b_idx.as<uint64_t>(nl);
-    for (int w = 0; w < 2; ++w) {   // stale values, as the general path (hpp:306-316)
-        hipLaunchKernelGGL(k_ok_index, dim3(nb), dim3(kThreads), 0, st, flags, nl,
-                           (uint8_t)(w == 0 ? F_START_OK : F_STOP_OK), idx);
-        scan::incl_max_u64(idx, nl, b_tmp, st);
-        int64_t* v = (w == 0) ? start : stop;
-        int64_t* cp = b_vcopy.as<int64_t>(nl);
-        HIP_CHECK(hipMemcpyAsync(cp, v, nl * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(k_gather_stale, dim3(nb), dim3(kThreads), 0, st, cp, idx, nl, w == 0 ? init_start : init_stop,
-                           v);
-    }
+    parse_lines(d_bed, nl, st, init_start, init_stop);
+    const int64_t* start = static_cast<const int64_t*>(b_start.p);
+    const int64_t* stop = static_cast<const int64_t*>(b_stop.p);
+    const uint8_t* flags = static_cast<const uint8_t*>(b_flags.p);
     uint32_t* seg_flag = b_seg_flag.as<uint32_t>(nl);
     uint64_t* seg_ord = b_seg_ord.as<uint64_t>(nl);
     hipLaunchKernelGGL(k_bc_flag, dim3(nb), dim3(kThreads), 0, st, flags, nl, seg_flag);
@@ -1768,34 +1664,12 @@ void TransformWorkspace::run_two_pass(const uint8_t* d_bed, uint64_t n, hipStrea
                                       int64_t init_start, int64_t init_stop)
 {
     res = TransformResult();
-    uint64_t ntile = ceil_div(n, kTileBytes);
-    uint32_t* tile_cnt = b_tile_cnt.as<uint32_t>(ntile + 1);
-    uint64_t* tile_off = b_tile_off.as<uint64_t>(ntile + 1);
-    uint64_t* scal = b_scal.as<uint64_t>(16);      // [0]=nl_total [1]=ff_pos [2]=nl_eff [3]=nseg [4]=text_total [5]=any_fail
-    HIP_CHECK(hipMemsetAsync(scal, 0, 16 * sizeof(uint64_t), st));
-    HIP_CHECK(hipMemsetAsync(scal + 1, 0xff, sizeof(uint64_t), st));
-    if (n > 0) {
-        hipLaunchKernelGGL(k_count_nl, dim3((unsigned)ntile), dim3(kThreads), 0, st, d_bed, n, tile_cnt,
-                           (unsigned long long*)(scal + 1));
-        scan::excl_sum_u32_to_u64(tile_cnt, tile_off, ntile, scal + 0, b_tmp, st);
-    }
-    uint64_t h[2];
-    HIP_CHECK(hipMemcpyAsync(h, scal, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    uint64_t nl = h[0];
-    uint64_t* line_end = b_line_end.as<uint64_t>(nl + 1);
-    if (nl) {
-        hipLaunchKernelGGL(k_index_nl, dim3((unsigned)ntile), dim3(kThreads), 0, st, d_bed, n, tile_off, line_end);
-        if (h[1] != ~0ull) {
-            hipLaunchKernelGGL(k_lines_before, dim3(1), dim3(1), 0, st, line_end, nl,
-                               (const unsigned long long*)(scal + 1), scal + 2);
-            HIP_CHECK(hipMemcpyAsync(&nl, scal + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-        }
-    }
+    const uint64_t nl = index_lines(d_bed, n, st, &res.ff_pos);
     res.n_lines = nl;
-    res.ff_pos = h[1];
-    if (nl == 0) { res.n_segments = 0; res.text_bytes = 0; return; }
+    if (nl == 0) return;
+    const uint64_t* line_end = static_cast<const uint64_t*>(b_line_end.p);
+    uint64_t* scal = b_scal.as<uint64_t>(16);      // (zeroed by index_lines) [3]=nseg [4]=text_total [5]=any_fail
+    uint64_t h[2];
 
     uint32_t* any_fail = reinterpret_cast<uint32_t*>(scal + 5);
     const unsigned nb = (unsigned)ceil_div(nl, kThreads);
@@ -1832,26 +1706,13 @@ void TransformWorkspace::run_two_pass(const uint8_t* d_bed, uint64_t n, hipStrea
     } else {
         // general path: some start/stop does not parse (stale values, hpp:306-316)
         res.general = true;
-        int64_t* start = b_start.as<int64_t>(nl);
-        int64_t* stop = b_stop.as<int64_t>(nl);
-        uint8_t* flags = b_flags.as<uint8_t>(nl);
-        uint64_t* rem_beg = b_rem_beg.as<uint64_t>(nl);
-        uint32_t* rem_len = b_rem_len.as<uint32_t>(nl);
-        uint32_t* chr_len = b_chr_len.as<uint32_t>(nl);
-        hipLaunchKernelGGL(k_parse, dim3(nb), dim3(kThreads), 0, st, d_bed, line_end, nl, start, stop, flags,
-                           rem_beg, rem_len, chr_len, any_fail);
-        uint64_t* idx = b_idx.as<uint64_t>(nl);
-        for (int w = 0; w < 2; ++w) {
-            hipLaunchKernelGGL(k_ok_index, dim3(nb), dim3(kThreads), 0, st, flags, nl,
-                               (uint8_t)(w == 0 ? F_START_OK : F_STOP_OK), idx);
-            scan::incl_max_u64(idx, nl, b_tmp, st);
-            // gather into a copy to avoid read/write races across blocks
-            int64_t* v = (w == 0) ? start : stop;
-            int64_t* cp = b_vcopy.as<int64_t>(nl);
-            HIP_CHECK(hipMemcpyAsync(cp, v, nl * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
-            hipLaunchKernelGGL(k_gather_stale, dim3(nb), dim3(kThreads), 0, st, cp, idx, nl, w == 0 ? init_start : init_stop,
-                               v);
-        }
+        parse_lines(d_bed, nl, st, init_start, init_stop);
+        const int64_t* start = static_cast<const int64_t*>(b_start.p);
+        const int64_t* stop = static_cast<const int64_t*>(b_stop.p);
+        const uint8_t* flags = static_cast<const uint8_t*>(b_flags.p);
+        const uint64_t* rem_beg = static_cast<const uint64_t*>(b_rem_beg.p);
+        const uint32_t* rem_len = static_cast<const uint32_t*>(b_rem_len.p);
+        const uint32_t* chr_len = static_cast<const uint32_t*>(b_chr_len.p);
         uint32_t* out_len = b_out_len.as<uint32_t>(nl);
         uint32_t* seg_flag = b_seg_flag.as<uint32_t>(nl);
         hipLaunchKernelGGL(k_line_len, dim3(nb), dim3(kThreads), 0, st, start, stop, flags, rem_len, nl, out_len,

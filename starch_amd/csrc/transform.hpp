@@ -21,7 +21,7 @@ struct TransformResult {
 struct TransformWorkspace {
     DevBuf b_tile_cnt, b_tile_off, b_scal, b_tmp, b_line_end, b_start, b_stop, b_flags, b_rem_beg, b_rem_len,
         b_chr_len, b_idx, b_vcopy, b_out_len, b_seg_flag, b_out_off, b_seg_ord, b_seg_first, b_seg_info, b_text,
-        b_fstatus, b_faggs, b_fx, b_arena, b_seg_arena;
+        b_faggs, b_fx, b_arena, b_seg_arena;
     double text_ratio = 1.0;          // text bytes per input byte of the last run (single-pass capacity, path choice)
     bool ratio_seen = false;
     uint64_t seg_hint = 0;
@@ -31,12 +31,16 @@ struct TransformWorkspace {
     // values carried into a shard that starts mid-input, hpp:306-307)
     void run(const uint8_t* d_bed, uint64_t n, hipStream_t st, TransformResult& res, int64_t init_start = 0,
              int64_t init_stop = 0);
-    // line-index based path (k_count_nl / k_index_nl, then k_tf1 + k_tf2 or the general path)
-    void run_two_pass(const uint8_t* d_bed, uint64_t n, hipStream_t st, TransformResult& res, int64_t init_start,
-                      int64_t init_stop);
     // line ends of the input up to the first 0xFF (b_line_end); returns the line count
     uint64_t index_lines(const uint8_t* d_bed, uint64_t n, hipStream_t st, uint64_t* ff_pos);
     // per-segment base counts, modulo 2^64; leaves text / seg_info_dev untouched
     void base_counts(const uint8_t* d_bed, uint64_t n, hipStream_t st, int64_t init_start, int64_t init_stop,
                      std::vector<uint64_t>& unique, std::vector<uint64_t>& nonunique);
+
+private:
+    // line-index based path (index_lines, then k_tf1 + k_tf2 or the general path)
+    void run_two_pass(const uint8_t* d_bed, uint64_t n, hipStream_t st, TransformResult& res, int64_t init_start,
+                      int64_t init_stop);
+    // per-line arrays (b_start ... b_chr_len) of the lines in b_line_end, stale values propagated
+    void parse_lines(const uint8_t* d_bed, uint64_t nl, hipStream_t st, int64_t init_start, int64_t init_stop);
 };

@@ -1,6 +1,7 @@
-"""The single-pass transform (k_tf_fused: 8 KiB tiles, LDS halo, decoupled
-look-back) against the oracle on the shapes that exercise its edges: lines
-across tile boundaries at every offset, 0xFF (EOF, hpp:181) in and around
+"""The single-pass transform (k_tf_fused: 8 KiB tiles, LDS halo, fixed arena
+slots placed after a scan over the tiles) against the oracle on the shapes
+that exercise its edges: lines across tile boundaries at every offset, 0xFF
+(EOF, hpp:181) in and around
 tiles, a tile whose output or segment records overflow LDS (direct writes), a
 text buffer that is too small (capacity retry), and the inputs it hands to the
 two-pass path (lines longer than the halo, tiles of > 2048 lines, stale
