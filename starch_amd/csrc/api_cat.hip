@@ -214,18 +214,18 @@ void cat_run(starch_ctx* c, const void* const* archives, const uint64_t* lens, u
                 sum += groups[todo[k]].text_bytes;
                 gs.push_back(todo[k]);
             }
-            try {
-                cat_batch(c, in, groups, gs, o, piece, hold, cs);
-            } catch (const StarchError& e) {
+            Caught e;
+            e.run([&] { cat_batch(c, in, groups, gs, o, piece, hold, cs); });
+            if (e.code) {
                 c->have = false;
                 const bool oom = e.code == STARCH_ERR_MEM ||
-                                 (e.code == STARCH_ERR_DEVICE && strstr(e.what(), "out of memory") != nullptr);
-                if (!oom) throw;
+                                 (e.code == STARCH_ERR_DEVICE && strstr(e.msg.c_str(), "out of memory") != nullptr);
+                if (!oom) e.rethrow();
                 (void)hipGetLastError();
                 std::string nm;
                 json_str(nm, groups[gs[0]].name.data(), groups[gs[0]].name.size());
                 throw StarchError(STARCH_ERR_MEM, "cat: the batch starting at chromosome " + nm + " does not fit (" +
-                                                      e.what() + "); lower STARCH_CAT_BATCH_BYTES");
+                                                      e.msg + "); lower STARCH_CAT_BATCH_BYTES");
             }
         }
     }

@@ -192,9 +192,6 @@ void finish_names(starch_ctx* c, PendingNames& pn)
 
 namespace {
 
-// transform + bzip2 over units.  L_ARCHIVE: magic + streams + index in
-// c->archive (the whole-input result); L_STREAMS: the streams alone, back to
-// back from offset 0 of c->part (one shard of a multi-GPU run).
 // Encoder lanes of a one-transform encode (STARCH_DEV_LANES, default 2): the
 // segments split into contiguous runs of about equal text, each planned
 // (RLE1 .. tables) by its own encoder on its own stream and host thread, so
@@ -227,16 +224,6 @@ std::vector<uint64_t> lane_cuts(const std::vector<SegInfo>& si, uint64_t tbytes,
     return cuts;
 }
 
-void merge_counters(bz::Stats& a, const bz::Stats& b)
-{
-    a.n_blocks += b.n_blocks;
-    a.rle_bytes += b.rle_bytes;
-    a.bwt_rounds += b.bwt_rounds;
-    a.periodic_blocks += b.periodic_blocks;
-    a.bwt_tied += b.bwt_tied;
-    a.dedup_blocks += b.dedup_blocks;
-}
-
 // per stage, the wall time during which any lane ran it (union of intervals)
 void stage_union(const std::vector<bz::Encoder::Interval>& iv, bz::Stats& st)
 {
@@ -265,6 +252,74 @@ void stage_union(const std::vector<bz::Encoder::Interval>& iv, bz::Stats& st)
 
 namespace api {
 
+void Caught::rethrow(const std::string& prefix) const
+{
+    if (code) throw StarchError(code, std::string(prefix).append(msg));
+}
+
+starch_stats stats_of(const bz::Stats& b, float ms_transform, float ms_total)
+{
+    starch_stats s{};
+    s.n_blocks = b.n_blocks, s.rle_bytes = b.rle_bytes, s.bwt_rounds = b.bwt_rounds;
+    s.periodic_blocks = b.periodic_blocks, s.bwt_tied = b.bwt_tied, s.dedup_blocks = b.dedup_blocks;
+    s.ms_transform = ms_transform, s.ms_total = ms_total;
+    s.ms_rle = b.rle, s.ms_bwt = b.bwt, s.ms_mtf = b.mtf, s.ms_tables = b.tables, s.ms_emit = b.emit;
+    return s;
+}
+
+void add_stats(starch_stats& t, const starch_stats& x, bool concurrent)
+{
+    for (uint64_t starch_stats::*f : {&starch_stats::n_lines, &starch_stats::text_bytes, &starch_stats::n_blocks,
+                                      &starch_stats::rle_bytes, &starch_stats::bwt_rounds,
+                                      &starch_stats::periodic_blocks, &starch_stats::bwt_tied,
+                                      &starch_stats::dedup_blocks})
+        t.*f += x.*f;
+    for (float starch_stats::*f : {&starch_stats::ms_transform, &starch_stats::ms_rle, &starch_stats::ms_bwt,
+                                   &starch_stats::ms_mtf, &starch_stats::ms_tables, &starch_stats::ms_emit,
+                                   &starch_stats::ms_total})
+        t.*f = concurrent ? std::max(t.*f, x.*f) : t.*f + x.*f;
+}
+
+std::vector<bz::StreamIn> streams_of(const std::vector<SegInfo>& si)
+{
+    std::vector<bz::StreamIn> sin(si.size());
+    for (size_t s = 0; s < si.size(); ++s) {
+        sin[s].text_off = si[s].text_off;
+        sin[s].text_len = si[s].text_len;
+        sin[s].final_run_joins = 1;
+        sin[s].group = (uint32_t)s;
+    }
+    return sin;
+}
+
+void append_segments(std::vector<starch_segment>& dst_segs, std::vector<std::string>& dst_names,
+                     const std::vector<starch_segment>& segs, const std::vector<std::string>& names,
+                     uint64_t stream_base)
+{
+    for (size_t s = 0; s < segs.size(); ++s) {
+        dst_segs.push_back(segs[s]);
+        dst_segs.back().stream_offset += stream_base;
+        dst_names.push_back(names[s]);
+    }
+}
+
+void install_archive(starch_ctx* c, std::vector<starch_segment>& segs, std::vector<std::string>& names,
+                     const starch_stats& stats, uint64_t bytes)
+{
+    c->segs.swap(segs);
+    c->names.swap(names);
+    c->stats = stats;
+    c->stats.archive_bytes = bytes;
+    c->text_bytes = 0;
+    c->text_dev = nullptr;
+    c->archive_bytes = bytes;
+    c->have = true;
+    c->streamed = false;
+}
+
+// transform + bzip2 over units.  L_ARCHIVE: magic + streams + index in
+// c->archive (the whole-input result); L_STREAMS: the streams alone, back to
+// back from offset 0 of c->part (one shard of a multi-GPU run).
 void encode_units(starch_ctx* c, const uint8_t* d_base, const std::vector<UnitIn>& units, const starch_options& opt,
                   Layout lay, bool planned, bool split_ok)
 {
@@ -321,13 +376,7 @@ void encode_units(starch_ctx* c, const uint8_t* d_base, const std::vector<UnitIn
         c->have = true;
         return;
     }
-    std::vector<bz::StreamIn> sin(nseg);
-    for (uint64_t s = 0; s < nseg; ++s) {
-        sin[s].text_off = si[s].text_off;
-        sin[s].text_len = si[s].text_len;
-        sin[s].final_run_joins = 1;
-        sin[s].group = (uint32_t)s;
-    }
+    std::vector<bz::StreamIn> sin = streams_of(si);
     std::vector<bz::StreamOut> outs;
     bz::Stats bst;
     const bool gzip = opt.compression_method == STARCH_METHOD_GZIP;
@@ -340,8 +389,7 @@ void encode_units(starch_ctx* c, const uint8_t* d_base, const std::vector<UnitIn
     if (gzip) {
         c->genc.plan(text, sin, c->st, outs, &bst);
     } else if (nl) {
-        std::vector<int> code(nl, 0);
-        std::vector<std::string> msg(nl);
+        std::vector<Caught> err(nl);
         std::vector<std::vector<bz::StreamIn>> li(nl);
         for (size_t i = 0; i < nl; ++i) {
             ln[i] = lane_ctx(c, (int)i);
@@ -351,25 +399,19 @@ void encode_units(starch_ctx* c, const uint8_t* d_base, const std::vector<UnitIn
             for (auto& x : li[i]) x.group -= (uint32_t)s0;
         }
         auto plan_lane = [&](size_t i) {
-            try {
+            err[i].run([&] {
                 Ctx g(ln[i]);
                 ln[i]->enc.plan(text, li[i], opt.block_size_100k, ln[i]->st, lo[i], &lst[i]);
-            } catch (const StarchError& e) {
-                code[i] = e.code;
-                msg[i] = e.what();
-            } catch (const std::exception& e) {
-                code[i] = STARCH_ERR_INTERNAL;
-                msg[i] = e.what();
-            }
+            });
         };
         for (size_t i = 1; i < nl; ++i) HIP_CHECK(hipStreamWaitEvent(ln[i]->st, e1, 0));   // the text is written
         for (size_t i = 1; i < nl; ++i) ln[i]->worker.start([&plan_lane, i] { plan_lane(i); });
         plan_lane(0);
         for (size_t i = 1; i < nl; ++i) ln[i]->worker.wait();
         for (size_t i = 0; i < nl; ++i)
-            if (code[i]) {
+            if (err[i].code) {
                 for (size_t j = 1; j < nl; ++j) (void)hipStreamSynchronize(ln[j]->st);
-                throw StarchError(code[i], msg[i]);
+                err[i].rethrow();
             }
         uint64_t end = 0;
         for (size_t i = 0; i < nl; ++i) {
@@ -381,7 +423,7 @@ void encode_units(starch_ctx* c, const uint8_t* d_base, const std::vector<UnitIn
                 outs.push_back(o);
             }
             end += b;
-            if (i) merge_counters(lst[0], lst[i]);
+            if (i) lst[0].add_counters(lst[i]);
         }
         bst = lst[0];
     } else {
@@ -440,19 +482,7 @@ void encode_units(starch_ctx* c, const uint8_t* d_base, const std::vector<UnitIn
     if (lay == L_ARCHIVE) c->archive_bytes = total;
     else c->part_bytes = total;
     c->stats.archive_bytes = total;
-    c->stats.n_blocks = bst.n_blocks;
-    c->stats.rle_bytes = bst.rle_bytes;
-    c->stats.bwt_rounds = bst.bwt_rounds;
-    c->stats.periodic_blocks = bst.periodic_blocks;
-    c->stats.bwt_tied = bst.bwt_tied;
-    c->stats.dedup_blocks = bst.dedup_blocks;
-    c->stats.ms_transform = ms_t;
-    c->stats.ms_rle = bst.rle;
-    c->stats.ms_bwt = bst.bwt;
-    c->stats.ms_mtf = bst.mtf;
-    c->stats.ms_tables = bst.tables;
-    c->stats.ms_emit = bst.emit;
-    c->stats.ms_total = ms_all;
+    add_stats(c->stats, stats_of(bst, ms_t, ms_all));   // (to the input, lines, segments and text set above)
     c->have = true;
 }
 
@@ -461,26 +491,6 @@ void encode_device(starch_ctx* c, const uint8_t* d_bed, uint64_t n, const starch
 {
     std::vector<UnitIn> u(1, UnitIn{0, n, 0, 0, 0});
     encode_units(c, d_bed, u, opt, L_ARCHIVE, false, true);
-}
-
-// a batch's counters and times added to a run's
-void add_stats(starch_stats& t, const starch_stats& x)
-{
-    t.n_lines += x.n_lines;
-    t.text_bytes += x.text_bytes;
-    t.n_blocks += x.n_blocks;
-    t.rle_bytes += x.rle_bytes;
-    t.bwt_rounds += x.bwt_rounds;
-    t.periodic_blocks += x.periodic_blocks;
-    t.bwt_tied += x.bwt_tied;
-    t.dedup_blocks += x.dedup_blocks;
-    t.ms_transform += x.ms_transform;
-    t.ms_rle += x.ms_rle;
-    t.ms_bwt += x.ms_bwt;
-    t.ms_mtf += x.ms_mtf;
-    t.ms_tables += x.ms_tables;
-    t.ms_emit += x.ms_emit;
-    t.ms_total += x.ms_total;
 }
 
 starch_ctx* lane_ctx(starch_ctx* c, int i)
@@ -669,8 +679,7 @@ bool encode_host_pipelined(starch_ctx* c, const uint8_t* bed, uint64_t n, const 
         hout->done.assign(batches.size(), 0);
         hout->lane = lane;
     }
-    std::vector<int> codes(nl, 0);
-    std::vector<std::string> errs(nl);
+    std::vector<Caught> err(nl);
     // every batch crosses PCIe in input order on one copy stream, into one
     // device buffer, so the first batch arrives at full link rate
     if (!c->cst) HIP_CHECK(hipStreamCreateWithFlags(&c->cst, hipStreamNonBlocking));
@@ -691,18 +700,13 @@ bool encode_host_pipelined(starch_ctx* c, const uint8_t* bed, uint64_t n, const 
     }
     auto work = [&](int i) {
         try {
-            Ctx g(lane[i]);
-            run_lane(lane[i], d_in, plan, batches, ev, mine[i], opt, res, i, stop, hout.get());
-        } catch (const FFInBatch&) {
+            err[i].run([&] {
+                Ctx g(lane[i]);
+                run_lane(lane[i], d_in, plan, batches, ev, mine[i], opt, res, i, stop, hout.get());
+            });
+            if (err[i].code) stop = true;
+        } catch (const FFInBatch&) {   // not an error: the caller falls back
             saw_ff = true;
-            stop = true;
-        } catch (const StarchError& e) {
-            codes[i] = e.code;
-            errs[i] = e.what();
-            stop = true;
-        } catch (const std::exception& e) {
-            codes[i] = STARCH_ERR_INTERNAL;
-            errs[i] = e.what();
             stop = true;
         }
     };
@@ -715,21 +719,18 @@ bool encode_host_pipelined(starch_ctx* c, const uint8_t* bed, uint64_t n, const 
     (void)hipStreamSynchronize(c->cst);
     for (int i = 0; i < nl; ++i) (void)hipStreamSynchronize(lane[i]->st);   // device-to-host writes queued by other lanes
     for (auto& e : ev) (void)hipEventDestroy(e);
-    for (int i = 0; i < nl; ++i)
-        if (codes[i]) throw StarchError(codes[i], errs[i]);
+    for (auto& e : err) e.rethrow();
     if (saw_ff) return false;
-    // archive: magic, the batches' streams in input order, index
+    // archive: magic, the batches' streams in input order, index; one copy per
+    // run of batches adjacent in a lane's collect buffer
     uint64_t end = 4;
     std::vector<starch_segment> segs;
     std::vector<std::string> names;
+    std::vector<shard::CopyRun> runs;
     starch_stats st{};
     for (auto& r : res) {
-        for (size_t s = 0; s < r.segs.size(); ++s) {
-            starch_segment g = r.segs[s];
-            g.stream_offset += end;
-            segs.push_back(g);
-            names.push_back(r.names[s]);
-        }
+        append_segments(segs, names, r.segs, r.names, end);
+        shard::add_run(runs, r.lane, r.coll_off, end, r.bytes);
         end += r.bytes;
         add_stats(st, r.stats);   // (ms_total is set below)
     }
@@ -737,18 +738,10 @@ bool encode_host_pipelined(starch_ctx* c, const uint8_t* bed, uint64_t n, const 
     if (opt.emit_index) idx = index_of(segs, names, end, opt);
     uint8_t* arch = c->archive.as<uint8_t>(align_up(end + idx.size() + 64, 256));
     HIP_CHECK(hipMemcpyAsync(arch, kMagic, 4, hipMemcpyHostToDevice, c->st));
-    uint64_t o = 4;
-    for (size_t k = 0; k < res.size();) {   // one copy per run of batches adjacent in a lane's collect buffer
-        const int ln = res[k].lane;
-        uint64_t len = res[k].bytes;
-        size_t k2 = k + 1;
-        while (k2 < res.size() && res[k2].lane == ln && res[k2].coll_off == res[k].coll_off + len) len += res[k2++].bytes;
-        if (len)
-            HIP_CHECK(hipMemcpyAsync(arch + o, static_cast<uint8_t*>(lane[ln]->collect.p) + res[k].coll_off, len,
+    for (auto& r : runs)
+        if (r.len)
+            HIP_CHECK(hipMemcpyAsync(arch + r.dst_off, static_cast<uint8_t*>(lane[r.src]->collect.p) + r.src_off, r.len,
                                      hipMemcpyDeviceToDevice, c->st));
-        o += len;
-        k = k2;
-    }
     if (!idx.empty()) HIP_CHECK(hipMemcpyAsync(arch + end, idx.data(), idx.size(), hipMemcpyHostToDevice, c->st));
     if (hout) {   // every batch went out already (all lanes finished); magic and index from the host
         if (hout->overflow || hout->off != end || end + idx.size() > hout_cap) {
@@ -763,16 +756,8 @@ bool encode_host_pipelined(starch_ctx* c, const uint8_t* bed, uint64_t n, const 
     HIP_CHECK(hipStreamSynchronize(c->st));
     st.input_bytes = n;
     st.n_segments = segs.size();
-    st.archive_bytes = end + idx.size();
     st.ms_total = std::chrono::duration<float, std::milli>(clk::now() - t0).count();
-    c->segs.swap(segs);
-    c->names.swap(names);
-    c->stats = st;
-    c->text_bytes = 0;
-    c->text_dev = nullptr;
-    c->archive_bytes = st.archive_bytes;
-    c->have = true;
-    c->streamed = false;
+    install_archive(c, segs, names, st, end + idx.size());
     return true;
 }
 
@@ -815,11 +800,10 @@ void encode_multi(starch_ctx* const* ctxs, int nctx, const uint8_t* bed, uint64_
         mine[s].push_back(UnitIn{dev_bytes[s], plan[k].length, plan[k].init_start, plan[k].init_stop, k});
         dev_bytes[s] += plan[k].length;
     }
-    std::vector<std::string> errs(nctx);
-    std::vector<int> codes(nctx, 0);
+    std::vector<Caught> err(nctx);
     auto work = [&](int s) {
         starch_ctx* c = ctxs[s];
-        try {
+        err[s].run([&] {
             Ctx g(c);
             uint8_t* d = c->input.as<uint8_t>(dev_bytes[s] + 64);
             for (auto& u : mine[s]) {
@@ -827,13 +811,7 @@ void encode_multi(starch_ctx* const* ctxs, int nctx, const uint8_t* bed, uint64_
                 if (u.len) HIP_CHECK(hipMemcpyAsync(d + u.off, bed + src, u.len, hipMemcpyHostToDevice, c->st));
             }
             encode_units(c, d, mine[s], opt, L_STREAMS);
-        } catch (const StarchError& e) {
-            codes[s] = e.code;
-            errs[s] = e.what();
-        } catch (const std::exception& e) {
-            codes[s] = STARCH_ERR_INTERNAL;
-            errs[s] = e.what();
-        }
+        });
     };
     {
         std::vector<std::thread> th;
@@ -841,8 +819,7 @@ void encode_multi(starch_ctx* const* ctxs, int nctx, const uint8_t* bed, uint64_
         work(0);
         for (auto& t : th) t.join();
     }
-    for (int s = 0; s < nctx; ++s)
-        if (codes[s]) throw StarchError(codes[s], "shard " + std::to_string(s) + ": " + errs[s]);
+    for (int s = 0; s < nctx; ++s) err[s].rethrow("shard " + std::to_string(s) + ": ");
     // gather: archive order = unit order
     std::vector<uint64_t> unit_of, bytes;
     std::vector<std::pair<int, uint64_t>> src;   // (shard, segment) of each gathered segment
@@ -858,9 +835,11 @@ void encode_multi(starch_ctx* const* ctxs, int nctx, const uint8_t* bed, uint64_
     shard::layout(unit_of.data(), bytes.data(), nseg, 4, order, offset, &end);
     std::vector<starch_segment> segs(nseg);
     std::vector<std::string> names(nseg);
+    std::vector<shard::CopyRun> runs;   // one copy per run of segments adjacent both in the part and in the archive
     for (uint64_t k = 0; k < nseg; ++k) {
         const auto& sj = src[order[k]];
         segs[k] = ctxs[sj.first]->segs[sj.second];
+        shard::add_run(runs, sj.first, segs[k].stream_offset, offset[order[k]], bytes[order[k]]);
         segs[k].stream_offset = offset[order[k]];
         names[k] = ctxs[sj.first]->names[sj.second];
     }
@@ -876,63 +855,24 @@ void encode_multi(starch_ctx* const* ctxs, int nctx, const uint8_t* bed, uint64_
             if (c->device != c0->device) (void)hipDeviceEnablePeerAccess(c->device, 0);
             (void)hipGetLastError();   // already enabled / not supported: the copy still works
         }
-        // one copy per run of segments that are adjacent both in the part and in the archive
-        for (uint64_t k = 0; k < nseg;) {
-            const auto& sj = src[order[k]];
-            starch_ctx* c = ctxs[sj.first];
-            const uint64_t s_off = c->segs[sj.second].stream_offset, d_off = offset[order[k]];
-            uint64_t len = bytes[order[k]], k2 = k + 1;
-            while (k2 < nseg) {
-                const auto& sn = src[order[k2]];
-                if (sn.first != sj.first || c->segs[sn.second].stream_offset != s_off + len ||
-                    offset[order[k2]] != d_off + len)
-                    break;
-                len += bytes[order[k2]];
-                ++k2;
-            }
-            if (len) {
-                if (c->device == c0->device)
-                    HIP_CHECK(hipMemcpyAsync(out + d_off, static_cast<uint8_t*>(c->part.p) + s_off, len,
-                                             hipMemcpyDeviceToDevice, c0->st));
-                else
-                    HIP_CHECK(hipMemcpyPeerAsync(out + d_off, c0->device, static_cast<uint8_t*>(c->part.p) + s_off,
-                                                 c->device, len, c0->st));
-            }
-            k = k2;
+        for (auto& r : runs) {
+            if (!r.len) continue;
+            starch_ctx* c = ctxs[r.src];
+            const uint8_t* from = static_cast<uint8_t*>(c->part.p) + r.src_off;
+            if (c->device == c0->device)
+                HIP_CHECK(hipMemcpyAsync(out + r.dst_off, from, r.len, hipMemcpyDeviceToDevice, c0->st));
+            else
+                HIP_CHECK(hipMemcpyPeerAsync(out + r.dst_off, c0->device, from, c->device, r.len, c0->st));
         }
         if (!idx.empty()) HIP_CHECK(hipMemcpyAsync(out + end, idx.data(), idx.size(), hipMemcpyHostToDevice, c0->st));
     }
     HIP_CHECK(hipStreamSynchronize(c0->st));
     starch_stats st{};
+    for (int s = 0; s < nctx; ++s) add_stats(st, ctxs[s]->stats, true);   // (ms_total is set below)
     st.input_bytes = n;
-    for (int s = 0; s < nctx; ++s) {
-        const starch_stats& x = ctxs[s]->stats;
-        st.n_lines += x.n_lines;
-        st.n_segments += x.n_segments;
-        st.text_bytes += x.text_bytes;
-        st.n_blocks += x.n_blocks;
-        st.rle_bytes += x.rle_bytes;
-        st.bwt_rounds += x.bwt_rounds;
-        st.periodic_blocks += x.periodic_blocks;
-        st.bwt_tied += x.bwt_tied;
-        st.dedup_blocks += x.dedup_blocks;
-        st.ms_transform = std::max(st.ms_transform, x.ms_transform);
-        st.ms_rle = std::max(st.ms_rle, x.ms_rle);
-        st.ms_bwt = std::max(st.ms_bwt, x.ms_bwt);
-        st.ms_mtf = std::max(st.ms_mtf, x.ms_mtf);
-        st.ms_tables = std::max(st.ms_tables, x.ms_tables);
-        st.ms_emit = std::max(st.ms_emit, x.ms_emit);
-    }
-    st.archive_bytes = total;
+    st.n_segments = nseg;
     st.ms_total = std::chrono::duration<float, std::milli>(clk::now() - t0).count();
-    c0->segs.swap(segs);
-    c0->names.swap(names);
-    c0->stats = st;
-    c0->text_bytes = 0;
-    c0->text_dev = nullptr;
-    c0->archive_bytes = total;
-    c0->have = true;
-    c0->streamed = false;
+    install_archive(c0, segs, names, st, total);
 }
 
 }  // namespace
@@ -1196,13 +1136,11 @@ static void transform_only(starch_ctx* c, const uint8_t* d, uint64_t n, int64_t 
     finish_names(c, pnames);
     float ms = 0;
     HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-    c->stats = starch_stats{};
+    c->stats = stats_of(bz::Stats(), ms, ms);
     c->stats.input_bytes = n;
     c->stats.n_lines = tr.n_lines;
     c->stats.n_segments = tr.n_segments;
     c->stats.text_bytes = tr.text_bytes;
-    c->stats.ms_transform = ms;
-    c->stats.ms_total = ms;
     c->text_bytes = tr.text_bytes;
     c->text_dev = c->tf.text;
     c->archive_bytes = 0;

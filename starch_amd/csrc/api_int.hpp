@@ -1,8 +1,8 @@
 // starch_amd/csrc/api_int.hpp -- what the files behind the C ABI
 // (include/starch_amd.h) share: api_core.hip, api_archive.cpp, api_encode.hip,
 // api_stream.hip, api_decode.hip, api_cat.hip, api_bed.hip, api_gunzip.hip, and gather.hip for
-// the device guard.  Declarations only; each function names the file that
-// defines it.  Everything here has hidden visibility: none of it is a symbol
+// the device guard and install_archive.  Declarations and a few inline helpers
+// (the guards, Caught); each function names the file that defines it.  Everything here has hidden visibility: none of it is a symbol
 // of the shared library.
 #pragma once
 #include "ctx.hpp"
@@ -46,6 +46,20 @@ struct Ctx {   // device guard
     }                                                    \
     catch (const StarchError& e) { return api::fail(c, e); }  \
     catch (const std::exception& e) { (c)->err = e.what(); return STARCH_ERR_INTERNAL; }
+
+// A worker's error, kept until every worker has been joined: run() records
+// what f throws, rethrow() throws it again.  Anything else passes through run().
+struct Caught {
+    int code = 0;
+    std::string msg;
+    template <class F> void run(F&& f)
+    {
+        try { f(); }
+        catch (const StarchError& e) { code = e.code; msg = e.what(); }
+        catch (const std::exception& e) { code = STARCH_ERR_INTERNAL; msg = e.what(); }
+    }
+    void rethrow(const std::string& prefix = "") const;   // (api_encode.hip)
+};
 
 inline uint64_t align_up(uint64_t x, uint64_t a) { return (x + a - 1) / a * a; }
 
@@ -109,7 +123,21 @@ struct PendingNames {
 void fetch_names(starch_ctx* c, const uint8_t* d_base, const std::vector<SegInfo>& si, PendingNames& pn);
 void finish_names(starch_ctx* c, PendingNames& pn);
 starch_ctx* lane_ctx(starch_ctx* c, int i);
-void add_stats(starch_stats& t, const starch_stats& x);
+// an encode's counters and stage times (every other field zero)
+starch_stats stats_of(const bz::Stats& b, float ms_transform, float ms_total);
+// x's lines, text, counters and times added to t's (concurrent, as shards on several devices: the
+// longest of each time stays instead); input_bytes, n_segments and archive_bytes are the caller's
+void add_stats(starch_stats& t, const starch_stats& x, bool concurrent = false);
+// whole streams over the segments' text, one group each
+std::vector<bz::StreamIn> streams_of(const std::vector<SegInfo>& si);
+// a batch's segments and names appended, its stream offsets moved by stream_base
+void append_segments(std::vector<starch_segment>& dst_segs, std::vector<std::string>& dst_names,
+                     const std::vector<starch_segment>& segs, const std::vector<std::string>& names,
+                     uint64_t stream_base);
+// an archive put together from several encodes becomes the context's result: segs and names
+// swapped in, stats with archive_bytes = bytes, no text
+void install_archive(starch_ctx* c, std::vector<starch_segment>& segs, std::vector<std::string>& names,
+                     const starch_stats& stats, uint64_t bytes);
 void encode_units(starch_ctx* c, const uint8_t* d_base, const std::vector<UnitIn>& units, const starch_options& opt,
                   Layout lay, bool planned = false, bool split_ok = false);
 void encode_device(starch_ctx* c, const uint8_t* d_bed, uint64_t n, const starch_options& opt);

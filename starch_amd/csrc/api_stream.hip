@@ -135,13 +135,7 @@ void stream_encode_pieces(starch_ctx* c, const uint8_t* d, uint64_t n, int64_t i
         si[0].text_len += R;
         T = Tb;
     }
-    std::vector<bz::StreamIn> sin(nseg);
-    for (uint64_t s = 0; s < nseg; ++s) {
-        sin[s].text_off = si[s].text_off;
-        sin[s].text_len = si[s].text_len;
-        sin[s].final_run_joins = 1;
-        sin[s].group = (uint32_t)s;
-    }
+    std::vector<bz::StreamIn> sin = streams_of(si);
     if (cont) {
         sin[0].cont = 1;
         sin[0].phase = os.phase;
@@ -184,8 +178,7 @@ void stream_encode_pieces(starch_ctx* c, const uint8_t* d, uint64_t n, int64_t i
         const bz::StreamOut& o = outs[s];
         const bool is_cont = s == 0 && cont, is_open = s + 1 == nseg && open;
         const uint8_t* b = part + o.out_off;
-        const uint64_t bits = ((o.frame >> 8) & 7u) + ((o.frame & 1u) ? 32u : 0u) + o.block_bits +
-                              ((o.frame & 2u) ? 80u : 0u);
+        const uint64_t bits = bz::frame_bits(o.frame) + o.block_bits;
         const uint64_t full = is_open ? bits / 8 : o.bytes;   // an open piece keeps its last partial byte
         const size_t at = m.ready.size();
         m.ready.insert(m.ready.end(), b, b + full);
@@ -230,23 +223,11 @@ void stream_encode_pieces(starch_ctx* c, const uint8_t* d, uint64_t n, int64_t i
     if (!open) os.rest_len = 0;
     ++m.batches;
     ++m.seq_commit;                   // (pieces start with every earlier batch appended)
-    starch_stats& t = m.stats;
-    t.n_lines += tr.n_lines - (ctx ? 1 : 0);
-    t.text_bytes += tr.text_bytes - o_ctx;
-    t.n_blocks += bst.n_blocks;
-    t.rle_bytes += bst.rle_bytes;
-    t.bwt_rounds += bst.bwt_rounds;
-    t.periodic_blocks += bst.periodic_blocks;
-    t.bwt_tied += bst.bwt_tied;
-    t.dedup_blocks += bst.dedup_blocks;
-    t.ms_transform += ms_t;
-    t.ms_rle += bst.rle;
-    t.ms_bwt += bst.bwt;
-    t.ms_mtf += bst.mtf;
-    t.ms_tables += bst.tables;
-    t.ms_emit += bst.emit;
-    t.ms_total += ms_all;
-    stream_flush(m);                  // batches after it that finished first
+    starch_stats x = stats_of(bst, ms_t, ms_all);
+    x.n_lines = tr.n_lines - (ctx ? 1 : 0);
+    x.text_bytes = tr.text_bytes - o_ctx;
+    add_stats(m.stats, x);
+    stream_flush(m);                 // batches after it that finished first
 }
 
 // append the next batch in hand-over order to the ready bytes (m.mu held)
@@ -254,13 +235,8 @@ void stream_append(starch_ctx::Streaming& m, const uint8_t* b, uint64_t nb, cons
                    const std::vector<std::string>& names, const starch_stats& x)
 {
     m.ready.insert(m.ready.end(), b, b + nb);
-    for (size_t s = 0; s < segs.size(); ++s) {
-        starch_segment g = segs[s];
-        g.stream_offset += m.stream_end;
-        g.unit = m.batches;
-        m.segs.push_back(g);
-        m.names.push_back(names[s]);
-    }
+    append_segments(m.segs, m.names, segs, names, m.stream_end);
+    for (size_t s = m.segs.size() - segs.size(); s < m.segs.size(); ++s) m.segs[s].unit = m.batches;
     m.stream_end += nb;
     ++m.batches;
     ++m.seq_commit;
@@ -337,22 +313,13 @@ void stream_worker(starch_ctx* c, int lane)
             m.lj[lane].pending = false;
             m.lj[lane].busy = true;
         }
-        int code = 0;
-        std::string msg;
-        try {
-            stream_encode(c, lane, j);
-        } catch (const StarchError& e) {
-            code = e.code;
-            msg = e.what();
-        } catch (const std::exception& e) {
-            code = STARCH_ERR_INTERNAL;
-            msg = e.what();
-        }
+        Caught err;
+        err.run([&] { stream_encode(c, lane, j); });
         {
             std::lock_guard<std::mutex> lk(m.mu);
             m.lj[lane].busy = false;
             m.buf_busy[j.bufi] = false;
-            if (code && !m.err) { m.err = code; m.err_msg = msg; }
+            if (err.code && !m.err) { m.err = err.code; m.err_msg = err.msg; }   // the session keeps its first error
         }
         m.cv.notify_all();
     }
@@ -654,20 +621,15 @@ int starch_stream_end(starch_ctx* c)
     m.fed = 0;
     m.held_n = 0;
     m.ctx_len = 0;
+    uint64_t bytes = m.opt.reference_compat ? 4 : m.stream_end;
     if (m.opt.emit_index && !m.opt.reference_compat) {
         const std::string idx = index_of(m.segs, m.names, m.stream_end, m.opt);
         m.ready.insert(m.ready.end(), idx.begin(), idx.end());
-        m.stats.archive_bytes = m.stream_end + idx.size();
-    } else {
-        m.stats.archive_bytes = m.opt.reference_compat ? 4 : m.stream_end;
+        bytes += idx.size();
     }
     m.stats.n_segments = m.segs.size();
-    c->segs = m.segs;
-    c->names = m.names;
-    c->stats = m.stats;
-    c->archive_bytes = m.stats.archive_bytes;
-    c->have = true;
-    c->streamed = true;
+    install_archive(c, m.segs, m.names, m.stats, bytes);   // (the session's lists go to the context)
+    c->streamed = true;                                     // the archive's bytes are read with starch_stream_read
     return STARCH_OK;
     END_GUARD(c)
 }

@@ -55,11 +55,20 @@ struct StreamOut {
     uint32_t frame;            // bit 0: header, bit 1: trailer, bits 8..10: phase (see StreamIn)
     uint64_t block_bits;       // bits of the blocks alone (no header, trailer or padding)
 };
+// bits of a stream piece before its first block (phase + 32 header bits), and
+// around its blocks altogether (+ 80 trailer bits)
+inline uint64_t frame_head_bits(uint32_t frame) { return ((frame >> 8) & 7u) + ((frame & 1u) ? 32u : 0u); }
+inline uint64_t frame_bits(uint32_t frame) { return frame_head_bits(frame) + ((frame & 2u) ? 80u : 0u); }
 
 struct Stats {                 // per-stage device timings (ms) from HIP events
     float rle = 0, bwt = 0, mtf = 0, tables = 0, emit = 0;
     uint64_t n_blocks = 0, rle_bytes = 0, bwt_rounds = 0, periodic_blocks = 0, bwt_tied = 0;
     uint64_t dedup_blocks = 0;     // blocks that reused a byte-identical block's results
+    void add_counters(const Stats& x)   // (encoder lanes: their stage times are merged as intervals)
+    {
+        n_blocks += x.n_blocks, rle_bytes += x.rle_bytes, bwt_rounds += x.bwt_rounds;
+        periodic_blocks += x.periodic_blocks, bwt_tied += x.bwt_tied, dedup_blocks += x.dedup_blocks;
+    }
 };
 
 // Every periodic block of a batch replays at once: one HIP stream per block
@@ -131,6 +140,16 @@ public:
     };
 
 private:
+    // plan()'s stages, in the order they run, and what they hand on
+    // (bz2_encoder.hip); internal: no symbols of the library
+#define BZ_LOCAL __attribute__((visibility("hidden")))
+    struct BZ_LOCAL Plan;
+    BZ_LOCAL void plan_rle(Plan& p);      // RLE1, block cut, descriptors read back
+    BZ_LOCAL bool plan_frames(Plan& p);   // stream frames; false: no blocks, the streams are sized
+    BZ_LOCAL void plan_dedupe(Plan& p);   // exact-block reuse: the distinct blocks
+    BZ_LOCAL void plan_sort(Plan& p);     // per batch: block sort, MTF, tables
+    BZ_LOCAL void plan_adopt(Plan& p);    // results into every block; stream sizes
+#undef BZ_LOCAL
     DevBuf b_streams, b_tiles, b_tile_sum, b_tile_carry, b_tile_w, b_tile_wpre, b_tile_block, b_cut_tab, b_seg_tile0, b_seg_nblk,
         b_blk_tmp, b_blk, b_blkbytes, b_scal, b_tmp, b_bwt, b_mtfv, b_freq, b_sel, b_tabs, b_gbits, b_souts,
         b_fallback, b_bwt3, b_crc, b_dedupe, b_rep_bytes, b_rep_blk, b_last;

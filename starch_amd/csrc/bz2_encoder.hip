@@ -86,6 +86,71 @@ Encoder::PinnedCtr::~PinnedCtr()
     if (p) (void)hipHostFree(p);
 }
 
+struct Encoder::Plan {
+    hipStream_t st;
+    std::vector<StreamOut>& outs;
+    Stats* stats;
+    uint32_t nb = 0;                       // blocks
+    BlockDesc* d_blocks = nullptr;         // every block, and its RLE1 bytes
+    uint8_t* d_blkbytes = nullptr;
+    std::vector<BlockDesc> hb;             // every block, on the host
+    std::vector<uint32_t> reps, src_of;    // the distinct blocks; block -> its index among them
+    bool reuse = false;
+    uint32_t nr = 0;                       // distinct blocks: what the sort, MTF and tables run over
+    BlockDesc* d_bl = nullptr;
+    const uint8_t* d_bytes = nullptr;
+    BlockDesc* hr = nullptr;               // their descriptors, read back (pinned)
+    unsigned long long* d_stats = nullptr; // the sort's counters
+};
+
+// Candidate duplicates: blocks grouped by (nblock, blockCRC, inUse), or by nblock alone; every
+// later block of a group paired with the group's first (its representative): (block, representative)
+static std::vector<uint32_t> dedupe_pairs(const std::vector<BlockDesc>& hb, bool key_n_only)
+{
+    const uint32_t nb = (uint32_t)hb.size();
+    std::vector<uint32_t> order(nb);
+    for (uint32_t b = 0; b < nb; ++b) order[b] = b;
+    auto key_less = [&](uint32_t x, uint32_t y) {
+        const BlockDesc &a = hb[x], &c = hb[y];
+        if (a.n != c.n) return a.n < c.n;
+        if (!key_n_only) {
+            if (a.crc != c.crc) return a.crc < c.crc;
+            int m = memcmp(a.in_use, c.in_use, sizeof(a.in_use));
+            if (m) return m < 0;
+        }
+        return x < y;
+    };
+    auto key_eq = [&](uint32_t x, uint32_t y) {
+        const BlockDesc &a = hb[x], &c = hb[y];
+        return a.n == c.n && (key_n_only || (a.crc == c.crc && !memcmp(a.in_use, c.in_use, sizeof(a.in_use))));
+    };
+    std::sort(order.begin(), order.end(), key_less);
+    std::vector<uint32_t> pairs;
+    for (uint32_t i = 1, r = order[0]; i < nb; ++i) {
+        if (key_eq(order[i], r)) { pairs.push_back(order[i]); pairs.push_back(r); }
+        else r = order[i];
+    }
+    return pairs;
+}
+
+// The data index space once the byte compares are back (mis[p]: pair p differs): the distinct blocks in
+// block order (reps) and every block's index among them (src_of).  Returns how many blocks reuse another's.
+static uint32_t dedupe_map(uint32_t nb, const std::vector<uint32_t>& pairs, const std::vector<uint32_t>& mis,
+                           std::vector<uint32_t>& reps, std::vector<uint32_t>& src_of)
+{
+    std::vector<uint32_t> rep_of(nb);
+    uint32_t ndup = 0;
+    for (uint32_t b = 0; b < nb; ++b) rep_of[b] = b;
+    for (size_t p = 0; p < mis.size(); ++p)
+        if (!mis[p]) { rep_of[pairs[2 * p]] = pairs[2 * p + 1]; ++ndup; }
+    reps.clear();
+    src_of.resize(nb);
+    for (uint32_t b = 0; b < nb; ++b)
+        if (rep_of[b] == b) { src_of[b] = (uint32_t)reps.size(); reps.push_back(b); }
+    for (uint32_t b = 0; b < nb; ++b) src_of[b] = src_of[rep_of[b]];
+    return ndup;
+}
+
 void Encoder::plan(const uint8_t* d_text, const std::vector<StreamIn>& streams, int bs100k, hipStream_t st,
                    std::vector<StreamOut>& outs, Stats* stats)
 {
@@ -96,7 +161,6 @@ void Encoder::plan(const uint8_t* d_text, const std::vector<StreamIn>& streams, 
     bs100k_ = bs100k;
     streams_ = streams;
     nstreams_ = (uint32_t)streams.size();
-    const uint32_t nblock_max = 100000u * (uint32_t)bs100k - 19u;     // bz:bzlib.c:194
     blk_stride_ = round_up(100000ull * bs100k + 64, 256);
     ngroups_ = 0;
     for (uint32_t s = 0; s < nstreams_; ++s) {
@@ -107,8 +171,22 @@ void Encoder::plan(const uint8_t* d_text, const std::vector<StreamIn>& streams, 
     outs.assign(ngroups_, StreamOut());
     nblocks_ = 0;
     if (nstreams_ == 0) return;
+    Plan p{st, outs, stats};
+    plan_rle(p);
+    if (!plan_frames(p)) return;
+    plan_dedupe(p);
+    plan_sort(p);
+    plan_adopt(p);
+}
 
-    EvTimer t_rle(st, stats, &pend_, 0);
+void Encoder::plan_rle(Plan& p)
+{
+    const hipStream_t st = p.st;
+    const std::vector<StreamIn>& streams = streams_;
+    const uint8_t* d_text = text_;
+    std::vector<StreamOut>& outs = p.outs;
+    const uint32_t nblock_max = 100000u * (uint32_t)bs100k_ - 19u;     // bz:bzlib.c:194
+    EvTimer t_rle(st, p.stats, &pend_, 0);
     StreamIn* d_streams = b_streams.as<StreamIn>(nstreams_);
     HIP_CHECK(hipMemcpyAsync(d_streams, streams.data(), nstreams_ * sizeof(StreamIn), hipMemcpyHostToDevice, st));
     std::vector<uint64_t> tile0(nstreams_ + 1, 0);
@@ -126,7 +204,7 @@ void Encoder::plan(const uint8_t* d_text, const std::vector<StreamIn>& streams, 
     uint32_t* d_carry = b_tile_carry.as<uint32_t>(ntiles + 1);
     uint32_t* d_tw = b_tile_w.as<uint32_t>(ntiles + 1);
     uint64_t* d_twpre = b_tile_wpre.as<uint64_t>(ntiles + 1);
-    uint64_t* d_scal = b_scal.as<uint64_t>(nstreams_ + 16);
+    p.d_stats = reinterpret_cast<unsigned long long*>(b_scal.as<uint64_t>(nstreams_ + 16));   // the sort's counters
     HIP_CHECK(hipMemsetAsync(d_twpre, 0, (ntiles + 1) * sizeof(uint64_t), st));
     if (ntiles) {
         rle_tiles(d_tile0, d_streams, nstreams_, ntiles, d_tiles, st);
@@ -154,11 +232,11 @@ void Encoder::plan(const uint8_t* d_text, const std::vector<StreamIn>& streams, 
     uint32_t* d_first = reinterpret_cast<uint32_t*>(b_souts.as<uint64_t>(nstreams_ + 2));
     uint32_t* d_nb = d_first + nstreams_;
     rle_block_first(d_nblk, nstreams_, d_first, d_nb, st);
-    BlockDesc* d_blocks = b_blk.as<BlockDesc>(nb_max + 1);
+    BlockDesc* d_blocks = p.d_blocks = b_blk.as<BlockDesc>(nb_max + 1);
     // tile -> block of its first byte
     uint32_t* d_tile_block = b_tile_block.as<uint32_t>(ntiles + 1);
     rle_compact(d_btmp, d_slot0, d_nblk, d_first, nstreams_, d_blocks, d_streams, d_tile0, d_tile_block, st);
-    uint8_t* d_blkbytes = b_blkbytes.as<uint8_t>(nb_max * blk_stride_ + 64);
+    uint8_t* d_blkbytes = p.d_blkbytes = b_blkbytes.as<uint8_t>(nb_max * blk_stride_ + 64);
     if (ntiles) {
         rle_emit(d_text, d_tiles, ntiles, d_twpre, d_tile0, d_carry, d_streams, d_first, d_nblk, d_tile_block, d_blocks,
                  d_blkbytes, blk_stride_, st);
@@ -192,8 +270,15 @@ void Encoder::plan(const uint8_t* d_text, const std::vector<StreamIn>& streams, 
             --outs[o.group].n_blocks;
         }
     }
-    nblocks_ = nb;
-    if (stats) stats->n_blocks += nb;
+    nblocks_ = p.nb = nb;
+    if (p.stats) p.stats->n_blocks += nb;
+    p.hb = std::vector<BlockDesc>(hbp, hbp + nb);
+}
+
+bool Encoder::plan_frames(Plan& p)
+{
+    const std::vector<StreamIn>& streams = streams_;
+    std::vector<StreamOut>& outs = p.outs;
     // frame of each output stream (whole stream: header + trailer, phase 0)
     for (uint32_t s = 0; s < nstreams_; ++s) {
         StreamOut& g = outs[streams[s].group];
@@ -205,98 +290,77 @@ void Encoder::plan(const uint8_t* d_text, const std::vector<StreamIn>& streams, 
         }
         if (last && !streams[s].open) g.frame |= 2u;
     }
-    auto frame_bits = [](const StreamOut& o) {
-        return (uint64_t)((o.frame >> 8) & 7u) + ((o.frame & 1u) ? 32u : 0u) + ((o.frame & 2u) ? 80u : 0u);
-    };
-    if (nb == 0) {
+    if (p.nb == 0) {
         for (uint32_t g = 0; g < ngroups_; ++g) {   // header + trailer (bz:compress.c:622-666)
             outs[g].block_bits = 0;
-            outs[g].bytes = (frame_bits(outs[g]) + 7) / 8;
+            outs[g].bytes = (frame_bits(outs[g].frame) + 7) / 8;
         }
         uint64_t off = 0;
         for (uint32_t g = 0; g < ngroups_; ++g) { outs[g].out_off = off; off += outs[g].bytes; }
-        return;
     }
+    return p.nb != 0;
+}
 
-    // ---- exact block reuse (bz2_dedupe.hip) ------------------------------------
-    // Group candidate duplicates by (nblock, blockCRC, inUse), confirm each with a
-    // byte compare against its representative, and run the block sort, MTF and
-    // tables once per distinct block.  STARCH_DEDUPE=0 disables it.
-    std::vector<BlockDesc> hb(hbp, hbp + nb);
+// Exact block reuse (bz2_dedupe.hip): group candidate duplicates by (nblock,
+// blockCRC, inUse), confirm each with a byte compare against its
+// representative, and run the block sort, MTF and tables once per distinct
+// block.  STARCH_DEDUPE=0 disables it.
+void Encoder::plan_dedupe(Plan& p)
+{
+    const hipStream_t st = p.st;
+    const uint32_t nb = p.nb;
+    const std::vector<BlockDesc>& hb = p.hb;
     const char* env_d = getenv("STARCH_DEDUPE");
     const bool dedupe_on = !(env_d && !strcmp(env_d, "0"));
     // STARCH_DEDUPE_KEY=n groups by nblock only (tests: forces byte-compare rejections)
     const char* env_k = getenv("STARCH_DEDUPE_KEY");
     const bool key_n_only = env_k && !strcmp(env_k, "n");
-    std::vector<uint32_t> rep_of(nb);
-    uint32_t ndup = 0;
-    for (uint32_t b = 0; b < nb; ++b) rep_of[b] = b;
-    if (dedupe_on && nb > 1) {
-        std::vector<uint32_t> order(nb);
-        for (uint32_t b = 0; b < nb; ++b) order[b] = b;
-        auto key_less = [&](uint32_t x, uint32_t y) {
-            const BlockDesc &a = hb[x], &c = hb[y];
-            if (a.n != c.n) return a.n < c.n;
-            if (!key_n_only) {
-                if (a.crc != c.crc) return a.crc < c.crc;
-                int m = memcmp(a.in_use, c.in_use, sizeof(a.in_use));
-                if (m) return m < 0;
-            }
-            return x < y;
-        };
-        auto key_eq = [&](uint32_t x, uint32_t y) {
-            const BlockDesc &a = hb[x], &c = hb[y];
-            return a.n == c.n && (key_n_only || (a.crc == c.crc && !memcmp(a.in_use, c.in_use, sizeof(a.in_use))));
-        };
-        std::sort(order.begin(), order.end(), key_less);
-        std::vector<uint32_t> pairs;
-        for (uint32_t i = 1, r = order[0]; i < nb; ++i) {
-            if (key_eq(order[i], r)) { pairs.push_back(order[i]); pairs.push_back(r); }
-            else r = order[i];
-        }
-        const uint32_t npairs = (uint32_t)(pairs.size() / 2);
-        if (npairs) {
-            uint32_t* d_pairs = b_dedupe.as<uint32_t>(3ull * npairs + 2 * nb + 16);
-            uint32_t* d_mis = d_pairs + 2ull * npairs;
-            HIP_CHECK(hipMemcpyAsync(d_pairs, pairs.data(), pairs.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                     st));
-            launch_block_equal(d_blkbytes, blk_stride_, d_pairs, npairs, d_blocks, d_mis, st);
-            std::vector<uint32_t> mis(npairs);
-            HIP_CHECK(hipMemcpyAsync(mis.data(), d_mis, npairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            for (uint32_t p = 0; p < npairs; ++p)
-                if (!mis[p]) { rep_of[pairs[2 * p]] = pairs[2 * p + 1]; ++ndup; }
-        }
+    std::vector<uint32_t> pairs, mis;
+    if (dedupe_on && nb > 1) pairs = dedupe_pairs(hb, key_n_only);
+    const uint32_t npairs = (uint32_t)(pairs.size() / 2);
+    if (npairs) {
+        uint32_t* d_pairs = b_dedupe.as<uint32_t>(3ull * npairs + 2 * nb + 16);
+        uint32_t* d_mis = d_pairs + 2ull * npairs;
+        HIP_CHECK(hipMemcpyAsync(d_pairs, pairs.data(), pairs.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+        launch_block_equal(p.d_blkbytes, blk_stride_, d_pairs, npairs, p.d_blocks, d_mis, st);
+        mis.resize(npairs);
+        HIP_CHECK(hipMemcpyAsync(mis.data(), d_mis, npairs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
     }
-    // data index space: the distinct blocks, in block order
-    const bool reuse = ndup > 0;
-    std::vector<uint32_t> reps, src_of(nb);
-    for (uint32_t b = 0; b < nb; ++b)
-        if (rep_of[b] == b) { src_of[b] = (uint32_t)reps.size(); reps.push_back(b); }
-    for (uint32_t b = 0; b < nb; ++b) src_of[b] = src_of[rep_of[b]];
-    const uint32_t nr = (uint32_t)reps.size();
-    BlockDesc* d_bl = d_blocks;              // blocks the sort / MTF / tables run over
-    const uint8_t* d_bytes = d_blkbytes;
+    const uint32_t ndup = dedupe_map(nb, pairs, mis, p.reps, p.src_of);
+    const std::vector<uint32_t>&reps = p.reps, &src_of = p.src_of;
+    const uint32_t nr = p.nr = (uint32_t)reps.size();
+    p.reuse = ndup > 0;
+    p.d_bl = p.d_blocks;                     // blocks the sort / MTF / tables run over
+    p.d_bytes = p.d_blkbytes;
     src_of_dev_ = nullptr;
     src_of_host_.clear();
-    if (reuse) {
+    if (p.reuse) {
         src_of_host_ = src_of;
         uint32_t* d_idx = b_dedupe.as<uint32_t>(2ull * nb + 16);
         HIP_CHECK(hipMemcpyAsync(d_idx, reps.data(), nr * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipMemcpyAsync(d_idx + nb, src_of.data(), nb * sizeof(uint32_t), hipMemcpyHostToDevice, st));
         src_of_dev_ = d_idx + nb;
         uint8_t* d_rbytes = b_rep_bytes.as<uint8_t>((uint64_t)nr * blk_stride_ + 64);
-        launch_gather_blocks(d_blkbytes, blk_stride_, d_idx, nr, d_rbytes, st);
+        launch_gather_blocks(p.d_blkbytes, blk_stride_, d_idx, nr, d_rbytes, st);
         std::vector<BlockDesc> hr(nr);
         for (uint32_t k = 0; k < nr; ++k) hr[k] = hb[reps[k]];
-        d_bl = b_rep_blk.as<BlockDesc>(nr + 1);
-        HIP_CHECK(hipMemcpyAsync(d_bl, hr.data(), nr * sizeof(BlockDesc), hipMemcpyHostToDevice, st));
+        p.d_bl = b_rep_blk.as<BlockDesc>(nr + 1);
+        HIP_CHECK(hipMemcpyAsync(p.d_bl, hr.data(), nr * sizeof(BlockDesc), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipStreamSynchronize(st));    // hr leaves scope
-        d_bytes = d_rbytes;
-        if (stats) stats->dedup_blocks += ndup;
+        p.d_bytes = d_rbytes;
+        if (p.stats) p.stats->dedup_blocks += ndup;
     }
+}
 
-    // ---- per-batch: block sort, MTF, tables (over the distinct blocks) -------
+// per batch: block sort, MTF, tables (over the distinct blocks)
+void Encoder::plan_sort(Plan& p)
+{
+    const hipStream_t st = p.st;
+    Stats* const stats = p.stats;
+    const uint32_t nb = p.nb, nr = p.nr;
+    BlockDesc* const d_bl = p.d_bl;
+    const uint8_t* const d_bytes = p.d_bytes;
     size_t free_b = 0, total_b = 0;
     const uint64_t mtf_stride = blk_stride_ + 16;
     uint16_t* d_mtfv = b_mtfv.as<uint16_t>((uint64_t)nr * mtf_stride);
@@ -336,9 +400,9 @@ void Encoder::plan(const uint8_t* d_text, const std::vector<StreamIn>& streams, 
         scr.U2 = scr.U + S * batch;
         scr.LL = reinterpret_cast<uint8_t*>(scr.U2 + S * batch);
     }
-    unsigned long long* d_stats = reinterpret_cast<unsigned long long*>(d_scal);
+    unsigned long long* const d_stats = p.d_stats;
     HIP_CHECK(hipMemsetAsync(d_stats, 0, 4 * sizeof(uint64_t), st));
-    BlockDesc* hr = h_hr_.as<BlockDesc>(nr);
+    BlockDesc* hr = p.hr = h_hr_.as<BlockDesc>(nr);
     uint32_t* d_which = reinterpret_cast<uint32_t*>(b_fallback.as<uint32_t>(batch + 1));
     for (uint32_t b0 = 0; b0 < nr; b0 += batch) {
         uint32_t cnt = std::min(batch, nr - b0);
@@ -354,7 +418,7 @@ void Encoder::plan(const uint8_t* d_text, const std::vector<StreamIn>& streams, 
             bool wide = false;
             mtf_need = 0;                  // alphabet classes of the batch (launch_mtf / launch_tables)
             for (uint32_t k = 0; k < cnt; ++k) {
-                const BlockDesc& bd = hb[reuse ? reps[b0 + k] : b0 + k];
+                const BlockDesc& bd = p.hb[p.reuse ? p.reps[b0 + k] : b0 + k];
                 uint32_t nin = 0;
                 for (int j = 0; j < 8; ++j) nin += (uint32_t)__builtin_popcount(bd.in_use[j]);
                 wide = wide || (!wide_off && nin >= 17 && nin <= 20);
@@ -392,16 +456,26 @@ void Encoder::plan(const uint8_t* d_text, const std::vector<StreamIn>& streams, 
             launch_tables(d_bl, b0, cnt, d_mtfv, mtf_stride, d_tabs, d_sel, d_gbits, scr, st, mtf_need);
         }
     }
-    HIP_CHECK(hipMemcpyAsync(hr, d_bl, nr * sizeof(BlockDesc), hipMemcpyDeviceToHost, st));
+}
+
+void Encoder::plan_adopt(Plan& p)
+{
+    const hipStream_t st = p.st;
+    Stats* const stats = p.stats;
+    const uint32_t nb = p.nb;
+    std::vector<BlockDesc>& hb = p.hb;
+    std::vector<StreamOut>& outs = p.outs;
+    const BlockDesc* hr = p.hr;            // (plan_sort read the periodic flags into it batch by batch)
+    HIP_CHECK(hipMemcpyAsync(p.hr, p.d_bl, p.nr * sizeof(BlockDesc), hipMemcpyDeviceToHost, st));
     uint64_t* hstats = reinterpret_cast<uint64_t*>(h_wtot_.as<uint64_t>(std::max<uint64_t>(nstreams_, 4)));
-    HIP_CHECK(hipMemcpyAsync(hstats, d_stats, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(hstats, p.d_stats, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     // every block takes the sort / MTF / table results of its data block; its
     // position fields (text range, stream, RLE offset) stay its own
-    if (!reuse) memcpy(hb.data(), hr, nb * sizeof(BlockDesc));
+    if (!p.reuse) memcpy(hb.data(), hr, nb * sizeof(BlockDesc));
     else {
         for (uint32_t b = 0; b < nb; ++b) {
-            BlockDesc o = hr[src_of[b]];
+            BlockDesc o = hr[p.src_of[b]];
             o.in_beg = hb[b].in_beg;
             o.in_end = hb[b].in_end;
             o.w_beg = hb[b].w_beg;
@@ -409,7 +483,7 @@ void Encoder::plan(const uint8_t* d_text, const std::vector<StreamIn>& streams, 
             o.stream = hb[b].stream;
             hb[b] = o;
         }
-        HIP_CHECK(hipMemcpyAsync(d_blocks, hb.data(), nb * sizeof(BlockDesc), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(p.d_blocks, hb.data(), nb * sizeof(BlockDesc), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipStreamSynchronize(st));
     }
     if (stats) {
@@ -423,7 +497,7 @@ void Encoder::plan(const uint8_t* d_text, const std::vector<StreamIn>& streams, 
         uint64_t bits = 0;
         for (uint32_t k = 0; k < outs[s].n_blocks; ++k) bits += hb[outs[s].first_block + k].bits;
         outs[s].block_bits = bits;
-        bits += frame_bits(outs[s]);
+        bits += frame_bits(outs[s].frame);
         outs[s].bytes = (bits + 7) / 8;
         outs[s].out_off = off;
         off += outs[s].bytes;
@@ -443,7 +517,7 @@ void Encoder::emit(uint8_t* d_out, uint64_t out_cap, uint64_t out_base, std::vec
     HIP_CHECK(hipMemsetAsync(d_out + out_base, 0, total, st));
     // absolute bit offsets of every block
     for (uint32_t s = 0; s < ngroups_; ++s) {
-        uint64_t pos = (out_base + outs[s].out_off) * 8 + ((outs[s].frame >> 8) & 7u) + ((outs[s].frame & 1u) ? 32u : 0u);
+        uint64_t pos = (out_base + outs[s].out_off) * 8 + frame_head_bits(outs[s].frame);
         for (uint32_t k = 0; k < outs[s].n_blocks; ++k) {
             BlockDesc& b = host_blocks_[outs[s].first_block + k];
             b.bit_off = pos;

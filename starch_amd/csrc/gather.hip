@@ -228,16 +228,10 @@ void gather(Transport& t, const std::vector<starch_segment>& segs, const std::ve
     for (uint64_t k = 0; k < nseg; ++k) { unit_of[k] = g[k].s.unit; bytes[k] = g[k].s.stream_bytes; }
     uint64_t end = 4;
     shard::layout(unit_of.data(), bytes.data(), nseg, 4, order, offset, &end);
-    // runs: (rank, source offset, archive offset, length), adjacent on both sides
-    struct Run { int rank; uint64_t src, dst, len; };
-    std::vector<Run> runs;
+    std::vector<shard::CopyRun> runs;   // by source rank, adjacent on both sides
     for (uint64_t k = 0; k < nseg; ++k) {
         const G& x = g[order[k]];
-        if (!runs.empty() && runs.back().rank == x.rank && runs.back().src + runs.back().len == x.s.stream_offset &&
-            runs.back().dst + runs.back().len == offset[order[k]])
-            runs.back().len += x.s.stream_bytes;
-        else
-            runs.push_back(Run{x.rank, x.s.stream_offset, offset[order[k]], x.s.stream_bytes});
+        shard::add_run(runs, x.rank, x.s.stream_offset, offset[order[k]], x.s.stream_bytes);
     }
 
     std::string idx;
@@ -265,16 +259,16 @@ void gather(Transport& t, const std::vector<starch_segment>& segs, const std::ve
         t.put(arch, archive::kMagic, 4);
         if (compat) runs.clear();   // the reference writes only the magic (hpp:765-769)
         for (auto& r : runs)
-            if (r.rank == 0 && r.len) t.copy(arch + r.dst, streams + r.src, r.len);
+            if (r.src == 0 && r.len) t.copy(arch + r.dst_off, streams + r.src_off, r.len);
     } else if (opt.reference_compat) {
         runs.clear();
     }
     // 3. grouped point-to-point: every stream byte crosses xGMI once
     t.group_begin();
     for (auto& r : runs) {
-        if (!r.len || r.rank == 0) continue;
-        if (t.rank == 0) t.recv(arch + r.dst, r.len, r.rank);
-        else if (r.rank == t.rank) t.send(streams + r.src, r.len, 0);
+        if (!r.len || r.src == 0) continue;
+        if (t.rank == 0) t.recv(arch + r.dst_off, r.len, r.src);
+        else if (r.src == t.rank) t.send(streams + r.src_off, r.len, 0);
     }
     t.group_end();
     if (t.rank == 0 && !idx.empty()) t.put(arch + end, idx.data(), idx.size());
@@ -452,10 +446,15 @@ void tcp_bootstrap(int rank, int world, const char* host, int port, ncclUniqueId
 
 thread_local std::string g_comm_err;
 
-int comm_fail(const std::exception& e, int code)
+// the body of an entry point that has no context: its status, or the thrown
+// error's code with the text kept for starch_comm_last_error
+template <class F> int comm_guard(F&& body)
 {
-    g_comm_err = e.what();
-    return code;
+    api::Caught e;
+    int rc = STARCH_OK;
+    e.run([&] { rc = body(); });
+    if (e.code) g_comm_err = e.msg;
+    return e.code ? e.code : rc;
 }
 
 }  // namespace
@@ -467,21 +466,19 @@ const char* starch_comm_last_error(void) { return g_comm_err.c_str(); }
 int starch_comm_id(void* id)
 {
     if (!id) return STARCH_ERR_ARG;
-    try {
+    return comm_guard([&]() -> int {
         ncclUniqueId u;
         nccl_check(rccl().GetUniqueId(&u), "unique id");
         memcpy(id, &u, sizeof(u));
         return STARCH_OK;
-    } catch (const StarchError& e) {
-        return comm_fail(e, e.code);
-    }
+    });
 }
 
 int starch_comm_create(int device, int rank, int world, const void* id, starch_comm** out)
 {
     if (!out || !id || world < 1 || rank < 0 || rank >= world) return STARCH_ERR_ARG;
     *out = nullptr;
-    try {
+    return comm_guard([&]() -> int {
         api::Ctx g(device);
         ncclUniqueId u;
         memcpy(&u, id, sizeof(u));
@@ -496,28 +493,20 @@ int starch_comm_create(int device, int rank, int world, const void* id, starch_c
         }
         *out = m;
         return STARCH_OK;
-    } catch (const StarchError& e) {
-        return comm_fail(e, e.code);
-    } catch (const std::exception& e) {
-        return comm_fail(e, STARCH_ERR_INTERNAL);
-    }
+    });
 }
 
 int starch_comm_create_tcp(int device, int rank, int world, const char* host, int port, starch_comm** out)
 {
     if (!out || world < 1 || rank < 0 || rank >= world || port <= 0 || port > 65535 || (rank && !host))
         return STARCH_ERR_ARG;
-    try {
+    return comm_guard([&]() -> int {
         ncclUniqueId u;
         memset(&u, 0, sizeof(u));
         if (rank == 0) nccl_check(rccl().GetUniqueId(&u), "unique id");
         if (world > 1) tcp_bootstrap(rank, world, host, port, &u, 600);
         return starch_comm_create(device, rank, world, &u, out);
-    } catch (const StarchError& e) {
-        return comm_fail(e, e.code);
-    } catch (const std::exception& e) {
-        return comm_fail(e, STARCH_ERR_INTERNAL);
-    }
+    });
 }
 
 const char* starch_rccl_library(void)
@@ -547,31 +536,19 @@ int starch_gather_archive(starch_ctx* c, starch_comm* m, const starch_options* o
     if (m->device != c->device) return STARCH_ERR_ARG;
     // a second gather would read archive offsets as offsets into the shard streams
     if (!c->have || c->streamed || c->gathered) return STARCH_ERR_STATE;
-    starch_options o;
-    starch_options_init(&o);
-    if (opt) o = *opt;
-    try {
-        api::Ctx g(c->device);
-        RcclTransport t(m, c);
-        Gathered r;
-        gather(t, c->segs, c->names, static_cast<const uint8_t*>(c->part.p), o, r);
-        if (m->rank == 0) {
-            c->segs.swap(r.segs);
-            c->names.swap(r.names);
-            c->archive_bytes = r.bytes;
-            c->gathered = true;
-        } else {
-            c->archive_bytes = 0;   // rank 0 holds the archive; this rank keeps its own segments
-        }
-        c->stats.archive_bytes = c->archive_bytes;
-        return STARCH_OK;
-    } catch (const StarchError& e) {
-        c->err = e.what();
-        return e.code;
-    } catch (const std::exception& e) {
-        c->err = e.what();
-        return STARCH_ERR_INTERNAL;
+    const starch_options o = api::options_of(opt);
+    GUARD(c)
+    RcclTransport t(m, c);
+    Gathered r;
+    gather(t, c->segs, c->names, static_cast<const uint8_t*>(c->part.p), o, r);
+    if (m->rank == 0) {
+        api::install_archive(c, r.segs, r.names, c->stats, r.bytes);
+        c->gathered = true;
+    } else {
+        c->archive_bytes = c->stats.archive_bytes = 0;   // rank 0 holds the archive; this rank keeps its own segments
     }
+    return STARCH_OK;
+    END_GUARD(c)
 }
 
 int starch_gather_host(const starch_host_comm* comm, const starch_segment* segs, const char* const* names,
@@ -584,9 +561,7 @@ int starch_gather_host(const starch_host_comm* comm, const starch_segment* segs,
         return STARCH_ERR_ARG;
     *archive = nullptr;
     *len = 0;
-    starch_options o;
-    starch_options_init(&o);
-    if (opt) o = *opt;
+    const starch_options o = api::options_of(opt);
     try {
         std::vector<starch_segment> s(segs, segs + nseg);
         std::vector<std::string> n(nseg);
@@ -606,9 +581,11 @@ int starch_gather_host(const starch_host_comm* comm, const starch_segment* segs,
         }
         return STARCH_OK;
     } catch (const StarchError& e) {
-        return comm_fail(e, e.code);
+        g_comm_err = e.what();
+        return e.code;
     } catch (const std::exception& e) {
-        return comm_fail(e, STARCH_ERR_INTERNAL);
+        g_comm_err = e.what();
+        return STARCH_ERR_INTERNAL;
     }
 }
 

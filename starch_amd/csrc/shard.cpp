@@ -260,4 +260,16 @@ void layout(const uint64_t* unit_of, const uint64_t* bytes, uint64_t nseg, uint6
     *end = pos;
 }
 
+void add_run(std::vector<CopyRun>& runs, int src, uint64_t src_off, uint64_t dst_off, uint64_t len)
+{
+    if (!runs.empty()) {
+        CopyRun& r = runs.back();
+        if (r.src == src && r.src_off + r.len == src_off && r.dst_off + r.len == dst_off) {
+            r.len += len;
+            return;
+        }
+    }
+    runs.push_back(CopyRun{src, src_off, dst_off, len});
+}
+
 }  // namespace shard

@@ -29,5 +29,18 @@ void assign_lpt(const std::vector<Unit>& units, int nshards, std::vector<int32_t
 // archive order of gathered segments (stable by unit) and their byte offsets from `base`
 void layout(const uint64_t* unit_of, const uint64_t* bytes, uint64_t nseg, uint64_t base, std::vector<uint64_t>& order,
             std::vector<uint64_t>& offset, uint64_t* end);
+// The copies that carry out a layout: len bytes from offset src_off of source
+// `src` (a lane, a shard, a rank) to archive offset dst_off.  add_run appends
+// a piece: it extends the last run when it comes from the same source and
+// continues it there and in the archive, and starts a new run otherwise, so
+// pieces given in archive order make one copy per run adjacent on both sides.
+// A piece of no bytes follows the same rule; a run may thus have len 0.
+// (Internal to the library: neither is a symbol of it.)
+struct __attribute__((visibility("hidden"))) CopyRun {
+    int src;
+    uint64_t src_off, dst_off, len;
+};
+__attribute__((visibility("hidden"))) void add_run(std::vector<CopyRun>& runs, int src, uint64_t src_off,
+                                                   uint64_t dst_off, uint64_t len);
 
 }  // namespace shard

@@ -94,3 +94,52 @@ def test_archive_layout_orders_by_unit():
     assert order == [0, 2, 3, 1]
     assert off == [4, 26, 14, 19]
     assert end == 56
+
+
+_RUNS_MAIN = r'''
+#include <stdio.h>
+#include "shard.hpp"
+int main(int argc, char** argv)
+{
+    std::vector<shard::CopyRun> runs;
+    for (int k = 1; k + 3 < argc; k += 4)
+        shard::add_run(runs, atoi(argv[k]), strtoull(argv[k + 1], 0, 10), strtoull(argv[k + 2], 0, 10),
+                       strtoull(argv[k + 3], 0, 10));
+    for (auto& r : runs)
+        printf("%d %llu %llu %llu\n", r.src, (unsigned long long)r.src_off, (unsigned long long)r.dst_off,
+               (unsigned long long)r.len);
+    return 0;
+}
+'''
+
+
+def test_copy_runs_join_pieces_adjacent_on_both_sides(tmp_path):
+    """shard::add_run (the copies that carry out a layout; internal to the library, so driven from a
+    stand-alone program built from shard.cpp): pieces are (source, source offset, archive offset, length)."""
+    import os
+    import subprocess
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "starch_amd", "csrc")
+    (tmp_path / "m.cpp").write_text("#include <stdlib.h>\n" + _RUNS_MAIN)
+    exe = tmp_path / "runs"
+    r = subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + csrc, str(tmp_path / "m.cpp"),
+                        os.path.join(csrc, "shard.cpp"), "-lpthread", "-o", str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+    def runs(*pieces):
+        out = subprocess.run([str(exe)] + [str(x) for p in pieces for x in p], capture_output=True, text=True, check=True)
+        return [tuple(int(x) for x in ln.split()) for ln in out.stdout.splitlines()]
+
+    assert runs() == []
+    # adjacent at the source and in the archive: one copy
+    assert runs((0, 0, 4, 10), (0, 10, 14, 6)) == [(0, 0, 4, 16)]
+    # adjacent at the source only (another source's piece lies between them in the archive)
+    assert runs((0, 0, 4, 10), (0, 10, 20, 6)) == [(0, 0, 4, 10), (0, 10, 20, 6)]
+    # adjacent in the archive only
+    assert runs((0, 0, 4, 10), (0, 12, 14, 6)) == [(0, 0, 4, 10), (0, 12, 14, 6)]
+    # different sources, though the offsets continue
+    assert runs((0, 0, 4, 10), (1, 10, 14, 6)) == [(0, 0, 4, 10), (1, 10, 14, 6)]
+    # a piece of no bytes in the middle: the same source's joins the run, another source's ends it
+    assert runs((0, 0, 4, 10), (0, 10, 14, 0), (0, 10, 14, 6)) == [(0, 0, 4, 16)]
+    assert runs((0, 0, 4, 10), (1, 0, 14, 0), (0, 10, 14, 6)) == [(0, 0, 4, 10), (1, 0, 14, 0), (0, 10, 14, 6)]
+    # a piece of no bytes first: a run of no bytes that the next piece extends
+    assert runs((2, 8, 4, 0), (2, 8, 4, 5)) == [(2, 8, 4, 5)]
