@@ -19,7 +19,7 @@ struct BwtScratch {            // 40 bytes per rotation per batch slot (+ 1 for 
 
 void launch_bwt(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blkbytes, uint64_t stride,
                 const BwtScratch& scr, unsigned long long* stats, hipStream_t st);
-// v3 (default): batch-wide segmented sort + doubling on ties (bz2_bwt3.hip).
+// v3 (default): batch-wide segmented sort + doubling on ties (bz2_bwt3.hip; kernels in bwt3_*.hip).
 // hctr: pinned host memory of >= 32 u32; stats[0..2] += rounds, periodic, tied rotations.
 // Returns false when no block needed prefix doubling (then none is periodic).
 bool launch_bwt3(BlockDesc* blocks, uint32_t b0, uint32_t nb, const uint8_t* blkbytes, uint64_t stride,

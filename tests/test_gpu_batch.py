@@ -39,7 +39,7 @@ def test_small_bwt_batches_bit_identical(tmp_path, cap):
 @pytest.mark.gpu
 def test_wide_top_digit_bit_identical(tmp_path):
     """Blocks of 17..20 symbols (narrowPeak text) sort with the 8192-bin
-    mixed-radix top-level digit (bz2_bwt3.hip top_digit); STARCH_WIDE=0 forces
+    mixed-radix top-level digit (bwt3_round0.hip top_digit); STARCH_WIDE=0 forces
     the binary 12-bit digit.  Any exact sort gives bzip2's order, so both must
     produce the same archive, also for a batch mixing 17..20-symbol blocks with
     smaller and larger alphabets."""

@@ -1,5 +1,5 @@
 """GPU block sort stress: full 900 KB blocks whose rotations stress every path
-of the batch-wide sort (bz2_bwt3.hip) -- tie groups resolved by doubling,
+of the batch-wide sort (bz2_bwt3.hip, bwt3_*.hip) -- tie groups resolved by doubling,
 huge equal-key groups, periodic blocks, every key width (2..256 symbols).
 Checked byte-for-byte against the CPU oracle's bzip2 -N stream (fallbackSort
 order), which the reference's own libbz2 pins (test_oracle.py)."""

@@ -1,4 +1,4 @@
-"""Round 0 of the block sort (bz2_bwt3.hip): the top-level bucket scatter
+"""Round 0 of the block sort (bwt3_round0.hip): the top-level bucket scatter
 (k3_scatter_lds) and the workgroup sort of the 1025..2048 class (k3_sort_lds),
 at the smallest shapes where they can go wrong -- stage and tile edges of the
 scatter, singleton and L-class buckets (the flag word of the write-out),

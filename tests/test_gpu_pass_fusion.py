@@ -1,4 +1,4 @@
-"""The fused passes round the leaf sorts: k3_pss_hist (bz2_bwt3.hip: packed
+"""The fused passes round the leaf sorts: k3_pss_hist (bwt3_round0.hip: packed
 symbol stream + top-level histogram in one kernel) and k_mtf_pre / k_mtf_scan
 (bz2_mtf.hip: three MTF launches instead of five).  Small texts, each
 compressed through the library and compared byte for byte with the CPU path
@@ -29,7 +29,7 @@ def _const(path, pattern):
     return m
 
 
-PTILE = int(_const("bz2_bwt3.hip", r"constexpr int PTILE = (\d+);").group(1))
+PTILE = int(_const("bwt3_int.hpp", r"constexpr int PTILE = (\d+);").group(1))
 # the chunk lengths launch_mtf picks by batch size; a one-block batch takes the shortest
 _CS = _const("bz2_mtf.hip", r"const uint32_t cs = nb >= 256 \? MCS : nb >= 64 \? (\d+)u : nb >= 8 \? (\d+)u : (\d+)u;")
 MCS = int(_const("bz2_mtf.hip", r"constexpr uint32_t MCS = (\d+);").group(1))

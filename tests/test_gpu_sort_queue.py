@@ -9,8 +9,9 @@ oracle/_ref is built, the oracle otherwise).
 The shapes: more blocks than XCDs with one and two encoder lanes; one block
 and three (queues cut by 64-item runs, most of them empty, so waves steal from
 their first pop); class lists shorter than a chunk and a multiple of the chunk
-plus one; S lists that are empty at the top level; and an input whose ties
-need text rounds and prefix doubling (the DBL instantiations).
+plus one; S lists that are empty at the top level; an input whose ties
+need text rounds and prefix doubling (the DBL instantiations); and one block
+whose sort needs more launches than the host's pool of queue sets holds.
 
 List lengths come from a model of the top level only (_top_level: the groups
 are the rotations that share their first three symbols, for 4-bit alphabets
@@ -194,3 +195,30 @@ def test_text_rounds_and_doubling(ctx):
     _check(ctx, data)
     st = ctx.stats()
     assert st["bwt_rounds"] > 0 and st["bwt_tied"] > 0
+
+
+# lines per run of equal gaps; the gap (1..9) is the run's own digit in the transformed text
+POOL_RUNS = [100, 250, 400, 600, 1400, 3200, 7000, 14000, 20000]
+
+
+def test_queue_pool_wraps(ctx):
+    """One -1 block whose sort takes more persistent launches than the queue pool has sets (64 per
+    batch, launch_bwt3's next_q), so the pool is cleared and reused in mid-sort.  Nine runs of
+    intervals of one width, run k with gaps of k bases: the text of run k is its digit and a
+    newline repeated, so its rotations tie in two groups of the run's length, one group in
+    every size class from S to L, and prefix doubling peels them over a dozen rounds with most class
+    lists in use in each: every list of every round is binned with a queue set of its own.
+    (Checked once with a host-side print in next_q and read_ctr: 71 counter reads, every leaf
+    class in both key forms, the pool cleared once.)"""
+    lines, pos = [], 1000
+    for gap, n in enumerate(POOL_RUNS, 1):
+        for _ in range(n):
+            lines.append(b"chrZ\t%d\t%d\n" % (pos, pos + 50))
+            pos += 50 + gap
+    data = b"".join(lines)
+    osegs = _check(ctx, data, level=1)
+    assert _blocks(osegs, 1) == 1
+    t = osegs[0][2]
+    for gap, n in enumerate(POOL_RUNS, 1):
+        assert (b"%d\n" % gap) * (n - 1) in t          # the runs are there as described
+    assert ctx.stats()["bwt_rounds"] >= 10

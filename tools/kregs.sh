@@ -1,6 +1,6 @@
 #!/usr/bin/env bash
 # register / LDS / spill summary of the kernels in a built object (dev tool):
-#   tools/kregs.sh starch_amd/_build/bz2_bwt3.o [name-regex]
+#   tools/kregs.sh starch_amd/_build/bwt3_leaf.o [name-regex]    (block sort: bwt3_round0 / part / leaf / rounds)
 set -e
 T=$(mktemp -d)
 /opt/rocm/lib/llvm/bin/llvm-objcopy --dump-section=.hip_fatbin=$T/fat.bin "$1"
