@@ -1419,6 +1419,86 @@ int starch_bbi_info(const void* data, uint64_t n, const starch_bbi_query* q, sta
  * range are STARCH_ERR_ARG. */
 int starch_bbi_adler32_host(const void* data, uint64_t n, uint32_t piece, uint32_t* adler);
 
+/* ---- bigwig2bed, bigbed2bed: the blocks of a bigWig / bigBed file to BED on the GPU ----
+ * (bed_bbi_dev.hip; zlib blocks through gz_inflate.hip.)  Modelled on UCSC's
+ * bigWigToBedGraph / bigBedToBed, unverified against UCSC's tools: what follows,
+ * which tests/bbi_oracle.py formats independently, is the definition.
+ * The file is read on the host as starch_bbi_info reads it.  The blocks that the
+ * query's region needs are uploaded as one range of the file, from the first of
+ * them to the end of the last, and nothing else of the file is.
+ * Compressed files (uncompressBufSize != 0).  A block is a zlib stream (RFC
+ * 1950): CMF, FLG, raw deflate data, Adler-32 big-endian.  From the bytes, on the
+ * host: at least 6 bytes, CM = 8, (CMF * 256 + FLG) % 31 = 0, FDICT clear.  On
+ * the device, one wave per block with the decoder of the gzip inflater: the
+ * deflate data must end exactly at the trailer, and the Adler-32 of the output
+ * (folded from pieces of 4096 bytes, starch_amd/csrc/gz_adler.hpp) must equal it.
+ * Every block inflates into a slot of uncompressBufSize bytes; when that is
+ * above 2^20, or the slots together above 2^30 bytes, a first walk over the
+ * deflate symbols sizes the slots and nothing is copied until they are known.  A
+ * block that would inflate past uncompressBufSize is an error and writes nothing
+ * behind its slot.
+ * bigWig.  A block is one section: chromId, chromStart, chromEnd, itemStep,
+ * itemSpan u32, type u8 (1 bedGraph, 2 variableStep, 3 fixedStep), reserved u8,
+ * itemCount u16, then items of 12 (start, end, value), 8 (start, value) or 4
+ * (value) bytes; a value is a float32.  The section's size must be 24 +
+ * itemCount * item bytes, its type 1 to 3, its chromId below the chromosome
+ * count.  A record's end is start + itemSpan for types 2 and 3, a type 3 start
+ * is chromStart + i * itemStep; both are kept in 64 bits.  start < end for every
+ * record.  A record becomes  chrom TAB start TAB end TAB value , the value as C's
+ * %g of the float32, computed exactly as bam2bed computes its f tags (inf, -inf,
+ * nan for a NaN of either sign).
+ * bigBed.  A block is records back to back: chromId, start, end u32, then the
+ * rest of the line and a zero byte.  The first zero byte at 12 bytes or more from
+ * a record's start ends it; the block must end exactly on such a byte.  chromId is
+ * below the chromosome count, start <= end, the rest holds no newline.  A record
+ * becomes  chrom TAB start TAB end , then TAB and the rest when it is not empty.
+ * Region.  With a region only records on its chromosome are written, and of a
+ * range only those with start < range end and end > range start; the others are
+ * dropped on the GPU.
+ * Order.  Block order, then record order; sorted as sort-bed sorts unless
+ * no_sort.
+ * Errors.  A bad block is STARCH_ERR_DATA with  bigwig2bed: block N: <reason>
+ * (bigbed2bed: for a bigBed file), N being the block's number in the file's table
+ * and the lowest bad block of the stage that found one (the zlib stage runs
+ * before the records are looked at); nothing is written.  A malformed header or
+ * tree is starch_bbi_info's  bbi: <reason> .  2^32 records or more is
+ * STARCH_ERR_ARG.  q may be NULL: the whole file, of either kind. */
+int starch_bbi_host(starch_ctx* ctx, const void* data, uint64_t n, const starch_bbi_query* q, uint32_t no_sort);
+/* The same for a file in HBM.  The whole file is read back to the host, where
+ * the header and the trees are walked, and the selected blocks are copied again
+ * into the context's padded input buffer, as starch_gunzip_device does. */
+int starch_bbi_device(starch_ctx* ctx, const void* d_data, uint64_t n, const starch_bbi_query* q, uint32_t no_sort);
+/* Convert, sort and encode from the sorted bytes while they are in HBM, as
+ * starch_bam_encode_host does.  sopt == NULL: the defaults. */
+int starch_bbi_encode_host(starch_ctx* ctx, const void* data, uint64_t n, const starch_bbi_query* q, const starch_options* sopt);
+typedef struct {
+    uint64_t input_bytes, uploaded_bytes, inflated_bytes;
+    uint64_t kind, compressed;                    /* STARCH_BBI_*; 1: zlib blocks */
+    uint64_t blocks;                              /* selected and converted */
+    uint64_t sized;                               /* 1: the slots came from the sizing walk */
+    uint64_t records;                             /* of those blocks, dropped ones too */
+    uint64_t wave_records;                        /* written bigBed records whose rest reaches the wave threshold */
+    uint64_t lines_out, output_bytes;
+    uint64_t sorted;                              /* 1: the sort ran */
+    /* GPU events; ms_total is host clock and holds the host's reading of the file too */
+    float ms_upload, ms_size, ms_inflate, ms_adler, ms_frame, ms_parse, ms_write, ms_sort, ms_total;
+} starch_bbi_stats;
+/* Of the last successful conversion on this context. */
+int starch_bbi_get_stats(starch_ctx* ctx, starch_bbi_stats* out);
+/* The threads per block of the per-record kernels (one record each), the bytes
+ * of a bigBed rest from which its whole wave checks and copies it, the largest
+ * uncompressBufSize that sizes the slots directly, and the bytes of an Adler-32
+ * piece. */
+int starch_bbi_constants(uint32_t* block_records, uint32_t* wave_rest, uint32_t* modest_slot, uint32_t* adler_piece);
+/* The zlib stage alone, for a compressed file: the selected blocks inflated and
+ * checked as above, block k into its slot and `gap` bytes of 0xA5 left behind
+ * every slot.  The slots and gaps are read through starch_output_*;
+ * starch_bbi_inflate_table gives, in table order, every slot's offset there and
+ * the bytes its block inflated to, and whether the zero padding behind the
+ * uploaded input is still zero.  A file that is not compressed is STARCH_ERR_ARG. */
+int starch_bbi_inflate_host(starch_ctx* ctx, const void* data, uint64_t n, const starch_bbi_query* q, uint32_t gap);
+int starch_bbi_inflate_table(starch_ctx* ctx, uint64_t* off, uint64_t* len, uint64_t cap, uint64_t* n_blocks, uint64_t* input_pad_ok);
+
 /* ---- gzip and BGZF inputs: inflate on the GPU (gz_inflate.hip) ----
  * An input of at least 18 bytes that begins 1f 8b 08 is gzip: one or more
  * RFC 1952 members back to back.  When every member carries the BC extra

@@ -24,7 +24,7 @@ __all__ = ["Starch", "StarchError", "load", "gen_bed", "build_index", "parse_arc
            "convert_constants", "CONVERT_FORMATS", "VCF_CLASSES", "ConvertOptions", "ConvertStats",
            "align_constants", "ALIGN_FORMATS", "AlignOptions", "AlignStats",
            "bam_constants", "BamOptions", "BamStats",
-           "bbi_info", "BBI_KINDS", "BbiQuery", "BbiHeader", "BbiBlock"]
+           "bbi_info", "BBI_KINDS", "BbiQuery", "BbiHeader", "BbiBlock", "BbiStats", "bbi_constants"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("STARCH_AMD_LIB") or os.path.join(_HERE, "_build", "libstarch_amd.so")
@@ -292,6 +292,14 @@ class BbiBlock(ctypes.Structure):
                [(n, ctypes.c_uint64) for n in ("data_offset", "data_size")]
 
 
+class BbiStats(ctypes.Structure):
+    """starch_bbi_stats: the last bbi2bed()."""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("input_bytes", "uploaded_bytes", "inflated_bytes", "kind", "compressed", "blocks",
+                                               "sized", "records", "wave_records", "lines_out", "output_bytes", "sorted")] + \
+               [(n, ctypes.c_float) for n in ("ms_upload", "ms_size", "ms_inflate", "ms_adler", "ms_frame", "ms_parse", "ms_write",
+                                              "ms_sort", "ms_total")]
+
+
 class SortStats(ctypes.Structure):
     """starch_sort_stats: the last sort_bed / sort_check / compress_sorted."""
     _fields_ = [(n, ctypes.c_uint64) for n in ("input_bytes", "n_lines", "n_chromosomes", "already_sorted",
@@ -465,6 +473,13 @@ def load():
         "starch_bbi_info": ([ctypes.c_char_p, u64, ctypes.POINTER(BbiQuery), ctypes.POINTER(BbiHeader),
                              ctypes.POINTER(ctypes.c_uint32), u64, vp, u64, ctypes.POINTER(BbiBlock), pu64, u64, vp, u64],
                             ctypes.c_int),
+        "starch_bbi_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(BbiQuery), ctypes.c_uint32], ctypes.c_int),
+        "starch_bbi_device": ([vp, vp, u64, ctypes.POINTER(BbiQuery), ctypes.c_uint32], ctypes.c_int),
+        "starch_bbi_encode_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(BbiQuery), ctypes.POINTER(Options)], ctypes.c_int),
+        "starch_bbi_get_stats": ([vp, ctypes.POINTER(BbiStats)], ctypes.c_int),
+        "starch_bbi_constants": ([ctypes.POINTER(ctypes.c_uint32)] * 4, ctypes.c_int),
+        "starch_bbi_inflate_host": ([vp, ctypes.c_char_p, u64, ctypes.POINTER(BbiQuery), ctypes.c_uint32], ctypes.c_int),
+        "starch_bbi_inflate_table": ([vp, pu64, pu64, u64, pu64, pu64], ctypes.c_int),
         "starch_bbi_adler32_host": ([ctypes.c_char_p, u64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)], ctypes.c_int),
         "starch_gunzip_host": ([vp, ctypes.c_char_p, u64], ctypes.c_int),
         "starch_gunzip_device": ([vp, vp, u64], ctypes.c_int),
@@ -1200,6 +1215,58 @@ class Starch:
         lines_out / output_bytes / sorted / ms_*."""
         return self._stats(BamStats, self._L.starch_bam_get_stats)
 
+    # ---- bigwig2bed, bigbed2bed ----
+    def bbi2bed(self, data: bytes, region=None, sort=True, kind="auto") -> bytes:
+        """bigwig2bed / bigbed2bed: a bigWig or bigBed file -> BED, in
+        sort_bed()'s order unless ``sort`` is False (then in block order).
+        bigWig gives chrom, start, end, value (%g of the float32); bigBed
+        chrom, start, end and the rest of the record.  ``region`` (a name, or
+        (name, start, end)) restricts the upload to the blocks it needs and the
+        lines to the records that meet it.  The blocks are inflated, checked
+        and formatted in HBM; the definition is in include/starch_amd.h.  A bad
+        block is StarchError -12 naming its number; ``kind`` ("bigwig",
+        "bigbed") refuses a file of the other kind."""
+        q = _bbi_query(kind, region)
+        _check(self._L.starch_bbi_host(self._h, data, len(data), ctypes.byref(q), 0 if sort else 1), self._h)
+        return self._output()
+
+    def bbi2bed_device(self, d_ptr: int, n: int, region=None, sort=True, kind="auto") -> int:
+        """The same for a file in HBM (it is read back for the host's walk of its
+        trees); returns the output size (output_device_ptr())."""
+        q = _bbi_query(kind, region)
+        _check(self._L.starch_bbi_device(self._h, ctypes.c_void_p(d_ptr), n, ctypes.byref(q), 0 if sort else 1), self._h)
+        return self._output_size()
+
+    def compress_bbi(self, data: bytes, region=None, emit_index=True, kind="auto") -> bytes:
+        """bbi2bed, sort and compress without leaving HBM: the archive
+        compress(bbi2bed(data, region)) gives."""
+        q = _bbi_query(kind, region)
+        so = self._opts(emit_index)
+        _check(self._L.starch_bbi_encode_host(self._h, data, len(data), ctypes.byref(q), ctypes.byref(so)), self._h)
+        return self.archive()
+
+    def bbi_stats(self) -> dict:
+        """Of the last bbi2bed(): input_bytes / uploaded_bytes / inflated_bytes /
+        kind / compressed / blocks / sized / records / wave_records / lines_out /
+        output_bytes / sorted / ms_*."""
+        return self._stats(BbiStats, self._L.starch_bbi_get_stats)
+
+    def bbi_inflate(self, data: bytes, region=None, gap=0):
+        """The zlib stage of bbi2bed() alone, on a compressed file: (area,
+        [(offset, length)], pad_ok).  Block k of the region's blocks inflated
+        to area[offset:offset + length]; behind every slot lie ``gap`` bytes of
+        0xA5; pad_ok: the zero padding behind the uploaded input is intact."""
+        q = _bbi_query("auto", region)
+        _check(self._L.starch_bbi_inflate_host(self._h, data, len(data), ctypes.byref(q), gap), self._h)
+        area = self._output()
+        n, ok = ctypes.c_uint64(), ctypes.c_uint64()
+        rc = self._L.starch_bbi_inflate_table(self._h, None, None, 0, ctypes.byref(n), ctypes.byref(ok))
+        if rc not in (0, -3):
+            _check(rc, self._h)
+        off, ln = (ctypes.c_uint64 * max(1, n.value))(), (ctypes.c_uint64 * max(1, n.value))()
+        _check(self._L.starch_bbi_inflate_table(self._h, off, ln, n.value, ctypes.byref(n), ctypes.byref(ok)), self._h)
+        return area, [(off[k], ln[k]) for k in range(n.value)], bool(ok.value)
+
     def cat(self, archives) -> bytes:
         """starchcat: the archives (bytes, in order) merged into one, with this
         instance's note, block_size_100k and base_counts.  A chromosome held
@@ -1497,6 +1564,13 @@ def bam_constants():
 def _bam_options(split, split_deletions, all_reads, reduced, keep_header, sort):
     """starch_bam_options; the combination of the flags is left to the library."""
     return BamOptions(bool(split), bool(split_deletions), bool(all_reads), bool(reduced), bool(keep_header), not sort)
+
+
+def bbi_constants():
+    """(threads per block of bbi2bed's per-record kernels, the bytes of a bigBed
+    rest from which its whole wave copies it, the largest uncompressBufSize
+    that sizes the slots directly, the bytes of an Adler-32 piece); no GPU needed."""
+    return _constants(load().starch_bbi_constants, 4)
 
 
 def _bbi_query(kind, region):

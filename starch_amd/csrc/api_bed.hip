@@ -1,5 +1,5 @@
 // starch_amd/csrc/api_bed.hip -- the C ABI of sort-bed, bedops, bedmap, closest-features, bedmap-elements,
-// bedmap-scores, convert2bed, sam2bed, psl2bed, rmsk2bed and bam2bed, and starch_bbi_info.  The four two-input tools go through pair_host,
+// bedmap-scores, convert2bed, sam2bed, psl2bed, rmsk2bed, bam2bed, bigwig2bed and bigbed2bed (with starch_bbi_info).  The four two-input tools go through pair_host,
 // pair_device and pair_get_stats, the converters through text_call; a tool keeps its option check, its
 // constants and the stats fields that are its own.
 #include <string.h>
@@ -1142,6 +1142,266 @@ int starch_bbi_adler32_host(const void* data, uint64_t n, uint32_t piece, uint32
 {
     if ((n && !data) || !adler || piece < 1 || piece > gz::kAdlerMaxPiece) return STARCH_ERR_ARG;
     *adler = gz::adler32_pieces(static_cast<const uint8_t*>(data), n, piece);
+    return STARCH_OK;
+}
+
+}  // extern "C"
+
+// ---- bigwig2bed, bigbed2bed (include/starch_amd.h; kernels in bed_bbi_dev.hip, zlib blocks through gz_inflate.hip) ----
+namespace {
+constexpr uint32_t kBbiModestSlot = 1u << 20;   // an uncompressBufSize up to which every block gets a slot of that size ...
+constexpr uint64_t kBbiModestArea = 1ull << 30;   // ... while all the slots together stay below this
+
+struct BbiStaged {         // a file's selected blocks in HBM, inflated when the file is compressed
+    bbidev::Input in;
+    uint64_t uploaded = 0, inflated = 0, sized = 0, slot_bytes = 0;   // slot_bytes: the slots and the gaps behind them
+    float ms_upload = 0, ms_size = 0, ms_inflate = 0, ms_adler = 0;
+    bool compressed = false;
+};
+
+const char* bbi_tool(uint32_t kind) { return kind == bbi::KIND_BIGWIG ? "bigwig2bed" : "bigbed2bed"; }
+
+[[noreturn]] void bbi_bad_block(uint32_t kind, uint64_t index, const std::string& why)
+{
+    throw StarchError(STARCH_ERR_DATA, std::string(bbi_tool(kind)) + ": block " + std::to_string(index) + ": " + why);
+}
+
+// The file read on the host, the blocks of q's region uploaded as one range (from
+// the first selected block to the end of the last) into dec_in and, when the file
+// is compressed, inflated into c->input: block k into a slot, `gap` bytes apart.
+// The region's lines are chosen later, on the device.
+void bbi_stage(starch_ctx* c, const uint8_t* file, uint64_t n, const starch_bbi_query* q, const bbi::Region& rg, uint32_t gap,
+               BbiStaged& s)
+{
+    bbi::Info info;
+    bbi::parse(file, n, info);
+    if (q && q->kind != STARCH_BBI_AUTO && q->kind != info.kind)
+        throw StarchError(STARCH_ERR_DATA, std::string("bbi: the file is a ") + (info.kind == bbi::KIND_BIGWIG ? "bigWig" : "bigBed") +
+                                               ", not the kind that was asked for");
+    int64_t chrom_id = -1;
+    const std::vector<uint64_t> sel = bbi::select(info, rg, &chrom_id);
+    bbidev::Input& in = s.in;
+    in.kind = info.kind;
+    for (const bbi::Chrom& ch : info.chroms) in.chroms.push_back(ch.name);
+    in.rg = bbirec::Region{rg.any ? (rg.whole ? 1u : 2u) : 0u, chrom_id < 0 ? bbirec::kNoChrom : (uint32_t)chrom_id, rg.start, rg.end};
+    in.index = sel;
+    s.compressed = info.uncompress_buf_size != 0;
+    if (sel.empty()) return;
+    const uint64_t up0 = info.blocks[sel.front()].data_offset;
+    const uint64_t up_n = info.blocks[sel.back()].data_offset + info.blocks[sel.back()].data_size - up0;
+    uint8_t* d_in = c->dec_in.as<uint8_t>(up_n + gz::kInPad);   // 8-byte aligned, with the inflater's read-ahead padding
+    {
+        StageTimer<2> tm;
+        tm.start(c->st);
+        HostRegistration reg(file + up0, up_n, 256ull << 20);
+        reg.h2d(d_in, file + up0, up_n, c->st);
+        HIP_CHECK(hipMemsetAsync(d_in + up_n, 0, gz::kInPad, c->st));
+        tm.finish(1, c->st, {&s.ms_upload});
+    }
+    s.uploaded = up_n;
+    const uint64_t B = sel.size();
+    in.off.resize(B);
+    in.len.resize(B);
+    if (!s.compressed) {
+        for (uint64_t k = 0; k < B; ++k) {
+            in.off[k] = info.blocks[sel[k]].data_offset - up0;
+            in.len[k] = info.blocks[sel[k]].data_size;
+        }
+        in.d = d_in;
+        return;
+    }
+    // zlib blocks (RFC 1950): the two header bytes are checked here, from the file's bytes
+    const uint64_t ubs = info.uncompress_buf_size;
+    std::vector<gz::Member> tab(B);
+    for (uint64_t k = 0; k < B; ++k) {
+        const bbi::Block& b = info.blocks[sel[k]];
+        const uint8_t* p = file + b.data_offset;
+        if (b.data_size < 6) bbi_bad_block(info.kind, sel[k], "shorter than a zlib header and trailer");
+        if ((p[0] & 15u) != 8u) bbi_bad_block(info.kind, sel[k], "zlib compression method is not 8 (deflate)");
+        if (((uint32_t)p[0] * 256u + p[1]) % 31u != 0) bbi_bad_block(info.kind, sel[k], "zlib header check fails (CMF * 256 + FLG is no multiple of 31)");
+        if (p[1] & 0x20u) bbi_bad_block(info.kind, sel[k], "zlib preset dictionary (FDICT) is not supported");
+        const uint8_t* t = p + b.data_size - 4;
+        gz::Member m{};
+        m.in_off = b.data_offset - up0;
+        m.in_len = b.data_size;
+        m.out_len = ubs;
+        m.crc = ((uint32_t)t[0] << 24) | ((uint32_t)t[1] << 16) | ((uint32_t)t[2] << 8) | t[3];
+        m.hdr_len = 2;
+        tab[k] = m;
+    }
+    std::vector<gz::TableResult> res;
+    auto check = [&] {
+        for (uint64_t k = 0; k < B; ++k)
+            if (res[k].err) bbi_bad_block(info.kind, sel[k], gz::inflate_error_text(res[k].err));
+    };
+    if (ubs > kBbiModestSlot || ubs * B > kBbiModestArea) {   // a declared size far above what blocks hold: the slots are what the blocks inflate to
+        c->zinflater.run(d_in, up_n, tab, 4, false, false, nullptr, c->st, res);
+        check();
+        for (uint64_t k = 0; k < B; ++k) tab[k].out_len = res[k].produced;
+        s.sized = 1;
+        s.ms_size = c->zinflater.ms_inflate;
+    }
+    uint64_t total = 0;
+    for (gz::Member& m : tab) {
+        m.out_off = total;
+        total += m.out_len + gap;
+    }
+    uint8_t* d_out = c->input.as<uint8_t>(total + 64);
+    if (gap) HIP_CHECK(hipMemsetAsync(d_out, 0xA5, total, c->st));   // (starch_bbi_inflate_host: the guard behind every slot)
+    c->zinflater.run(d_in, up_n, tab, 4, true, true, d_out, c->st, res);
+    check();
+    s.ms_inflate = c->zinflater.ms_inflate;
+    s.ms_adler = c->zinflater.ms_check;
+    for (uint64_t k = 0; k < B; ++k) {
+        in.off[k] = tab[k].out_off;
+        in.len[k] = res[k].produced;
+        s.inflated += res[k].produced;
+    }
+    in.d = d_out;
+    c->bbi_slot_off.assign(B, 0);
+    for (uint64_t k = 0; k < B; ++k) c->bbi_slot_off[k] = tab[k].out_off;
+    c->bbi_slot_len = in.len;
+    s.slot_bytes = total;
+}
+
+// The checked call: the file's bytes in host memory; converted into setop_out
+// and, unless no_sort, sorted from there into sort_out; sopt: encode the sorted
+// result with it.
+int bbi_call(starch_ctx* c, const void* data, uint64_t n, const starch_bbi_query* q, const bbi::Region& rg, bool no_sort,
+             const starch_options* sopt)
+{
+    GUARD(c)
+    if (sopt) c->have = false;
+    c->have_out = false;
+    c->have_bbstats = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    BbiStaged sg;
+    bbi_stage(c, static_cast<const uint8_t*>(data), n, q, rg, 0, sg);
+    bbidev::Result r;
+    c->bbier.run(sg.in, c->st, c->setop_out, r);
+    starch_bbi_stats& s = c->bbstats;
+    s = starch_bbi_stats{};
+    s.input_bytes = n;
+    s.uploaded_bytes = sg.uploaded;
+    s.inflated_bytes = sg.compressed ? sg.inflated : sg.uploaded;
+    s.kind = sg.in.kind;
+    s.compressed = sg.compressed ? 1 : 0;
+    s.blocks = r.blocks;
+    s.sized = sg.sized;
+    s.records = r.records;
+    s.wave_records = r.wave_records;
+    s.lines_out = r.lines_out;
+    s.output_bytes = r.out_bytes;
+    s.ms_upload = sg.ms_upload;
+    s.ms_size = sg.ms_size;
+    s.ms_inflate = sg.ms_inflate;
+    s.ms_adler = sg.ms_adler;
+    s.ms_frame = r.ms_frame;
+    s.ms_parse = r.ms_parse;
+    s.ms_write = r.ms_write;
+    if (no_sort) publish(c, c->setop_out, r.out_bytes);
+    else {
+        sort_run(c, static_cast<const uint8_t*>(c->setop_out.p), r.out_bytes, false);
+        s.sorted = 1;
+        s.ms_sort = c->sstats.ms_total;
+    }
+    s.ms_total = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c->have_bbstats = true;
+    // the sorted text is in sort_out, which no encoder stage writes
+    if (sopt) encode_device(c, c->out_dev, c->out_bytes, *sopt);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+}  // namespace
+
+extern "C" {
+
+int starch_bbi_host(starch_ctx* c, const void* data, uint64_t n, const starch_bbi_query* q, uint32_t no_sort)
+{
+    bbi::Region rg;
+    if (!c || (n && !data) || (q && !bbi_query_ok(q, &rg))) return STARCH_ERR_ARG;
+    return bbi_call(c, data, n, q, rg, no_sort != 0, nullptr);
+}
+
+int starch_bbi_device(starch_ctx* c, const void* d_data, uint64_t n, const starch_bbi_query* q, uint32_t no_sort)
+{
+    bbi::Region rg;
+    if (!c || (n && !d_data) || (q && !bbi_query_ok(q, &rg))) return STARCH_ERR_ARG;
+    std::vector<uint8_t> h(n);                 // the header and the trees are read on the host
+    {
+        GUARD(c)
+        if (n) HIP_CHECK(hipMemcpyAsync(h.data(), d_data, n, hipMemcpyDeviceToHost, c->st));
+        HIP_CHECK(hipStreamSynchronize(c->st));
+        END_GUARD(c)
+    }
+    return bbi_call(c, h.data(), n, q, rg, no_sort != 0, nullptr);
+}
+
+int starch_bbi_encode_host(starch_ctx* c, const void* data, uint64_t n, const starch_bbi_query* q, const starch_options* sopt)
+{
+    bbi::Region rg;
+    if (!c || (n && !data) || (q && !bbi_query_ok(q, &rg))) return STARCH_ERR_ARG;
+    const starch_options o = options_of(sopt);
+    if (!options_ok(o)) return STARCH_ERR_ARG;
+    return bbi_call(c, data, n, q, rg, false, &o);
+}
+
+int starch_bbi_get_stats(starch_ctx* c, starch_bbi_stats* out)
+{
+    if (!c || !out) return STARCH_ERR_ARG;
+    if (!c->have_bbstats) return STARCH_ERR_STATE;
+    *out = c->bbstats;
+    return STARCH_OK;
+}
+
+int starch_bbi_constants(uint32_t* block_records, uint32_t* wave_rest, uint32_t* modest_slot, uint32_t* adler_piece)
+{
+    if (block_records) *block_records = (uint32_t)bbidev::kThreads;
+    if (wave_rest) *wave_rest = bbidev::kWaveRest;
+    if (modest_slot) *modest_slot = kBbiModestSlot;
+    if (adler_piece) *adler_piece = gz::kAdlerPiece;
+    return STARCH_OK;
+}
+
+int starch_bbi_inflate_host(starch_ctx* c, const void* data, uint64_t n, const starch_bbi_query* q, uint32_t gap)
+{
+    bbi::Region rg;
+    if (!c || (n && !data) || (q && !bbi_query_ok(q, &rg))) return STARCH_ERR_ARG;
+    GUARD(c)
+    c->have_out = false;
+    c->bbi_slot_off.clear();
+    c->bbi_slot_len.clear();
+    c->bbi_pad_ok = 0;
+    BbiStaged sg;
+    bbi_stage(c, static_cast<const uint8_t*>(data), n, q, rg, gap, sg);
+    if (!sg.compressed) throw StarchError(STARCH_ERR_ARG, "bbi: the file's blocks are not compressed");
+    if (sg.in.off.empty()) {
+        publish(c, c->input, 0);
+        c->bbi_pad_ok = 1;
+        return STARCH_OK;
+    }
+    uint8_t pad[gz::kInPad];
+    HIP_CHECK(hipMemcpyAsync(pad, static_cast<const uint8_t*>(c->dec_in.p) + sg.uploaded, sizeof pad, hipMemcpyDeviceToHost, c->st));
+    HIP_CHECK(hipStreamSynchronize(c->st));
+    c->bbi_pad_ok = 1;
+    for (uint8_t v : pad)
+        if (v) c->bbi_pad_ok = 0;
+    publish(c, c->input, sg.slot_bytes);
+    return STARCH_OK;
+    END_GUARD(c)
+}
+
+int starch_bbi_inflate_table(starch_ctx* c, uint64_t* off, uint64_t* len, uint64_t cap, uint64_t* n_blocks, uint64_t* input_pad_ok)
+{
+    if (!c || !n_blocks || (cap && (!off || !len))) return STARCH_ERR_ARG;
+    if (!c->have_out) return STARCH_ERR_STATE;
+    *n_blocks = c->bbi_slot_off.size();
+    if (input_pad_ok) *input_pad_ok = c->bbi_pad_ok;
+    if (cap < c->bbi_slot_off.size()) return STARCH_ERR_MEM;
+    for (uint64_t k = 0; k < c->bbi_slot_off.size(); ++k) {
+        off[k] = c->bbi_slot_off[k];
+        len[k] = c->bbi_slot_len[k];
+    }
     return STARCH_OK;
 }
 

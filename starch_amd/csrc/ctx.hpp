@@ -30,6 +30,7 @@
 #include "bed_mapscore.hpp"
 #include "bed_align.hpp"
 #include "bed_bam.hpp"
+#include "bed_bbi_dev.hpp"
 #include "bed_convert.hpp"
 #include "transform.hpp"
 #include "untransform.hpp"
@@ -255,6 +256,14 @@ struct starch_ctx {
     bam::BamWorkspace bammer;
     starch_bam_stats bstats{};       // the last starch_bam_* call
     bool have_bstats = false;
+    // bigwig2bed, bigbed2bed (bed_bbi_dev.hip): the selected blocks go to dec_in, their inflated
+    // bytes to input (slot after slot, through zinflater); writes setop_out
+    bbidev::Workspace bbier;
+    gz::TableInflater zinflater;
+    starch_bbi_stats bbstats{};      // the last starch_bbi_* conversion
+    bool have_bbstats = false;
+    std::vector<uint64_t> bbi_slot_off, bbi_slot_len;   // the last starch_bbi_inflate_host
+    uint64_t bbi_pad_ok = 0;
     // gzip and BGZF inputs (gz_inflate.hip): the compressed bytes go to dec_in,
     // the inflated ones where the caller wants the text
     gz::Inflater inflater;

@@ -1,7 +1,7 @@
 // starch_amd/csrc/gz_adler.hpp -- Adler-32 (RFC 1950) from pieces: __host__
 // __device__ functions, so that a kernel over the inflated blocks of a bigWig /
-// bigBed file and the host run the same arithmetic.  No kernel calls them yet;
-// starch_bbi_adler32_host (api_bed.hip) runs them on the host.
+// bigBed file and the host run the same arithmetic: k_tab_adler (gz_inflate.hip) on the
+// device, starch_bbi_adler32_host (api_bed.hip) on the host.
 //
 // A piece x[0, n) is summed without the leading 1 of Adler-32:
 //   a = sum x[i],   w = sum i * x[i],   b = n * a - w = sum (n - i) * x[i]

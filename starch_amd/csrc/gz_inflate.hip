@@ -21,12 +21,18 @@
 //                 16-byte stores.
 //   k_gz_crc_chunks, k_gz_crc_members   CRC-32 of every member's output,
 //                 folded from 4 KiB pieces (gz_crc.hpp), against its trailer.
+//   k_tab_inflate, k_tab_adler   the same decoder over a table its caller made
+//                 (TableInflater: the zlib blocks of a bigWig / bigBed file):
+//                 header and trailer lengths are the table's and the caller's,
+//                 a member's out_len is a slot it may not pass, and the check
+//                 is Adler-32, folded from 4 KiB pieces (gz_adler.hpp).
 // The inputs are untrusted.  Every loop iteration consumes input bits or ends
 // the member, the bit position is checked against the member's extent, every
 // output write against the member's slot, every match distance against the
 // bytes the member has produced; a violation sets the member's error word and
 // stops that member only.
 #include "gz_inflate.hpp"
+#include "gz_adler.hpp"
 #include "gz_crc.hpp"
 
 #include <algorithm>
@@ -43,7 +49,7 @@ static_assert(W % 16 == 0 && W >= 32768 + 258 + 16 && W >= kFlushBytes + 2 * 258
 enum Err : uint32_t {
     E_OK = 0, E_MAGIC, E_FLG, E_HDR_TRUNC, E_TRAILING, E_BTYPE, E_STORED_LEN, E_TRUNC, E_HLIT, E_HDIST, E_CL_SET,
     E_REP_FIRST, E_REP_PAST, E_NO_EOB, E_LIT_OVER, E_LIT_INCOMPLETE, E_DIST_OVER, E_DIST_INCOMPLETE, E_LIT_SYM,
-    E_DIST_SYM, E_BAD_CODE, E_DIST_FAR, E_OUT_OVER, E_EXTENT, E_ISIZE, E_CRC, E_COUNT
+    E_DIST_SYM, E_BAD_CODE, E_DIST_FAR, E_OUT_OVER, E_EXTENT, E_ISIZE, E_CRC, E_ADLER, E_COUNT
 };
 const char* const kErrText[E_COUNT] = {
     "ok",
@@ -72,6 +78,7 @@ const char* const kErrText[E_COUNT] = {
     "the deflate data does not end at the trailer",
     "ISIZE does not match the bytes produced",
     "CRC-32 mismatch",
+    "Adler-32 mismatch",
 };
 
 struct Result {                  // per member, written by k_gz_inflate and k_gz_crc_members
@@ -570,6 +577,59 @@ __global__ void __launch_bounds__(256) k_gz_crc_members(const Member* __restrict
     if (tid == 0 && res[s].err == E_OK && ~(rs[0] ^ gf_mul(0xFFFFFFFFu, x8n(total))) != tab[s].crc) res[s].err = E_CRC;
 }
 
+// ---- a caller-made table (TableInflater): zlib blocks, or any framing around raw deflate data ----
+// One wave per member, as k_gz_inflate: the deflate data begins hdr_len bytes into
+// the member and must end exactly `trailer` bytes before its end.  out_len is the
+// member's slot: a member that would inflate past it ends in E_OUT_OVER and has
+// written nothing behind the slot.  Without COPY nothing is written at all and
+// res[m].produced is what the member inflates to (the sizing walk).
+template <bool COPY>
+__global__ void __launch_bounds__(64) k_tab_inflate(const uint8_t* __restrict__ in, uint64_t in_cap,
+                                                    const Member* __restrict__ tab, uint32_t nmem, uint32_t trailer,
+                                                    uint8_t* __restrict__ out, TableResult* __restrict__ res)
+{
+    __shared__ __attribute__((aligned(16))) Lds L;
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t m = blockIdx.x; m < nmem; m += gridDim.x) {
+        const Member mb = tab[m];
+        Bits b;
+        b.in = in;
+        b.cap = in_cap;
+        start_bits(b, mb.in_off + mb.hdr_len, lane);
+        uint32_t nblk[3] = {0, 0, 0};
+        uint64_t produced = 0;
+        const uint64_t end_byte = mb.in_off + mb.in_len - trailer;   // (the host made in_len >= hdr_len + trailer)
+        uint32_t err = inflate_body<COPY>(b, end_byte, L, COPY ? out + mb.out_off : nullptr, mb.out_len, &produced, nblk, lane);
+        if (!err && (bits_used(b) + 7) / 8 != end_byte) err = E_EXTENT;
+        if (lane == 0) res[m] = TableResult{err, 0, produced};
+        __syncthreads();             // the next member reuses the tables and the ring
+    }
+}
+
+// Adler-32 of every good member's output against tab[m].crc: one wave per
+// member, piece after piece of kAdlerPiece bytes, every piece summed in the
+// lanes' shares and folded (gz_adler.hpp).
+__global__ void __launch_bounds__(64) k_tab_adler(const uint8_t* __restrict__ out, const Member* __restrict__ tab, uint32_t nmem,
+                                                  TableResult* __restrict__ res)
+{
+    const uint32_t lane = threadIdx.x;
+    for (uint32_t m = blockIdx.x; m < nmem; m += gridDim.x) {
+        if (res[m].err) continue;
+        const uint64_t n = res[m].produced;
+        const uint8_t* x = out + tab[m].out_off;
+        AdlerSum s{0, 0, 0};
+        for (uint64_t at = 0; at < n; at += kAdlerPiece) {
+            const uint32_t len = (uint32_t)(n - at < kAdlerPiece ? n - at : kAdlerPiece);
+            uint64_t a = 0, w = 0;
+            adler_share(x + at, len, lane, &a, &w);
+            a = wave_reduce_add<uint64_t>(a);
+            w = wave_reduce_add<uint64_t>(w);
+            s = adler_fold(s, adler_piece(a, w, len));
+        }
+        if (lane == 0 && adler_value(s) != tab[m].crc) res[m].err = E_ADLER;
+    }
+}
+
 [[noreturn]] void bad_member(uint64_t k, uint64_t off, uint32_t err)
 {
     throw StarchError(-12, "gunzip: member " + std::to_string(k) + " at byte " + std::to_string(off) + ": " +
@@ -719,6 +779,41 @@ void Inflater::inflate(uint8_t* d_out, hipStream_t st)
         stats.fixed_blocks += r.fixed;
         stats.dynamic_blocks += r.dynamic;
     }
+}
+
+const char* inflate_error_text(uint32_t err) { return err < E_COUNT ? kErrText[err] : "unknown error word"; }
+
+void TableInflater::run(const uint8_t* d_in, uint64_t n, const std::vector<Member>& tab, uint32_t trailer, bool copy, bool adler,
+                        uint8_t* d_out, hipStream_t st, std::vector<TableResult>& res)
+{
+    const uint32_t nmem = (uint32_t)tab.size();
+    res.assign(nmem, TableResult{});
+    ms_inflate = ms_check = 0;
+    if (!nmem) return;
+    if (tab.size() >= (1ull << 31)) throw StarchError(-2, "inflate: 2^31 members or more");
+    if ((reinterpret_cast<uintptr_t>(d_in) & 7u) != 0) throw StarchError(-2, "inflate: the device input must be 8-byte aligned");
+    for (const Member& m : tab)
+        if (m.in_off + m.in_len > n || m.in_len < (uint64_t)m.hdr_len + trailer)
+            throw StarchError(-2, "inflate: a member of the table lies outside the input or is shorter than its framing");
+    Member* d_tab = b_table.as<Member>(nmem);
+    TableResult* d_res = b_res.as<TableResult>(nmem);
+    HIP_CHECK(hipMemcpyAsync(d_tab, tab.data(), nmem * sizeof(Member), hipMemcpyHostToDevice, st));
+    int dev = 0, cus = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const uint32_t grid = std::min<uint32_t>(nmem, (uint32_t)std::max(cus, 1) * 4u);   // four one-wave workgroups fit a CU's LDS
+    const uint64_t in_cap = (n + kInPad) & ~7ull;
+    tm_.start(st);
+    if (copy) hipLaunchKernelGGL(k_tab_inflate<true>, dim3(grid), dim3(64), 0, st, d_in, in_cap, d_tab, nmem, trailer, d_out, d_res);
+    else hipLaunchKernelGGL(k_tab_inflate<false>, dim3(grid), dim3(64), 0, st, d_in, in_cap, d_tab, nmem, trailer, d_out, d_res);
+    HIP_CHECK(hipGetLastError());
+    tm_.mark(1, st);
+    if (copy && adler) {
+        hipLaunchKernelGGL(k_tab_adler, dim3(std::min<uint32_t>(nmem, 65536u)), dim3(64), 0, st, d_out, d_tab, nmem, d_res);
+        HIP_CHECK(hipGetLastError());
+    }
+    HIP_CHECK(hipMemcpyAsync(res.data(), d_res, nmem * sizeof(TableResult), hipMemcpyDeviceToHost, st));
+    tm_.finish(2, st, {&ms_inflate, &ms_check});
 }
 
 }  // namespace gz

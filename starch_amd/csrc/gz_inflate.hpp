@@ -65,4 +65,33 @@ private:
     DevBuf b_table, b_res, b_chunk0, b_creg, b_cnt;
 };
 
+// ---- a caller-made member table: raw deflate data inside any framing (the zlib blocks of a bigWig / bigBed file) ----
+struct TableResult {             // per member
+    uint32_t err, pad;           // 0, or an error word: inflate_error_text
+    uint64_t produced;           // the bytes it inflates to
+};
+const char* inflate_error_text(uint32_t err);
+
+// The inflater's decoder over a table the caller made, one wave per member.
+// Of a Member: in_off, in_len and hdr_len frame the deflate data, which must end
+// exactly `trailer` bytes before the member's end (8 for gzip, 4 for zlib);
+// out_off and out_len are the member's slot in d_out: a member that inflates past
+// out_len is an error and writes nothing behind its slot; crc is the Adler-32
+// expected of the output when adler is set (RFC 1950's trailer, which the caller
+// reads: it is big-endian).  isize is unused.
+class TableInflater {
+public:
+    // d_in: the input in HBM, 8-byte aligned, n bytes with kInPad readable zero
+    // bytes after them.  copy false: the sizing walk, nothing is written and
+    // d_out may be NULL.  res[m]: the member's error word and size.  Throws only
+    // for a table that does not fit the input.
+    void run(const uint8_t* d_in, uint64_t n, const std::vector<Member>& tab, uint32_t trailer, bool copy, bool adler,
+             uint8_t* d_out, hipStream_t st, std::vector<TableResult>& res);
+    float ms_inflate = 0, ms_check = 0;
+
+private:
+    DevBuf b_table, b_res;
+    StageTimer<3> tm_;
+};
+
 }  // namespace gz
